@@ -32,7 +32,11 @@ Stability: every control-plane process is pinned to its own physical core, the i
 (shared) host as sampled at start (``--pin``, utils/cpuset.py), and the per-wave distribution is reported next to
 ``value`` (``wave_pods_per_s``: p50 and IQR).
 
-After the timed region rank 0 runs, as extra keys outside ``value``:
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--dump-outputs DIR`` also writes
+what the last timed wave computed (each pod's device and gpu-mem, the ledger's per-device use, the HBM stamp check)
+as ``DIR/<name>.npy``, so that two builds can be compared output for output (``dump_outputs`` below).
+
+With ``--full`` rank 0 also runs, after the timed region and as extra keys outside ``value``:
 ``device_plugin_path``: the same waves with kubelet + device plugin played by the shipped gRPC
 ``GpuSharePlugin`` over its unix socket (the kubelet stand-in in gsxtools/agent.py) instead of the
 compiled node agent; ``device_plugin_path_native_kubelet``: the compiled kubelet stand-in calling the shipped
@@ -639,6 +643,13 @@ def parse():
     # (1 MiB put two in each unit: verify 11.9 -> 7.2 us per admission on MI355X, profiles/r02_stride_ab/)
     ap.add_argument("--stamp-stride", type=int, default=2 << 20)
     ap.add_argument("--json-out", default="")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the rows that take runs of their own: the latency sweep with "
+                         "the reference-client and comparison rows (--sweep) and the open-loop rows (--open-loop).  "
+                         "Off by default: a plain run times its steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float64): "
+                         "pod_device, pod_gpu_mem, device_used, device_total, hbm_bad_stamps")
     ap.add_argument("--dump-timings", default="",
                     help="write every timed pod's scheduler timeline (CLOCK_MONOTONIC, like the wave's t0) here")
     ap.add_argument("--agent", default="node", choices=["node", "rank"],
@@ -683,11 +694,11 @@ def parse():
     ap.add_argument("--plugin-proc", default="process", choices=["process", "grpc"],
                     help="device-plugin path row: the plugin as its own process registered with the kubelet "
                          "stand-in, as the DaemonSet runs it (process), or served from the stand-in's process (grpc)")
-    ap.add_argument("--sweep", type=int, default=1, help="1: run the latency sweep after the timed region")
+    ap.add_argument("--sweep", type=int, default=1, help="with --full, 1: run the latency sweep after the timed region")
     # 20 waves a latency point (~0.4 s at 5 ms): with 8, single points read 20-45 % below their neighbours
     ap.add_argument("--sweep-steps", type=int, default=20)
     ap.add_argument("--open-loop", default="auto",
-                    help="open-loop throughput rows after the timed region: 'auto' (the rate ladder "
+                    help="with --full, open-loop throughput rows after the timed region: 'auto' (the rate ladder "
                          f"{OPEN_LOOP_RATES} at {OPEN_LOOP_LATENCIES_MS} ms apiserver latency), a comma list of "
                          "rates, or 0 (off)")
     ap.add_argument("--open-loop-gib", type=int, default=1, help="pod size of the open-loop rows")
@@ -713,7 +724,10 @@ def parse():
                          "profiles/r05_session5/).  The region-level run_delay_pct and psi_timed_ms are always there")
     ap.add_argument("--apiserver-threads", type=int, default=0,
                     help="event loops of the fake apiserver (0: auto; GSX_FAKEAPI_THREADS overrides)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:
+        a.sweep, a.open_loop = 0, "0"  # a plain run: the timed steps and the result line only
+    return a
 
 
 def rank_device(devs, phys: int, local_rank: int, use_gpu: bool, who: str = "rank"):
@@ -782,6 +796,28 @@ def _same_condition(ref_client) -> float | None:
     rows = {r.get("bind_mode"): r for r in ref_client or [] if isinstance(r, dict)}
     b = rows.get("binding", {}).get("pods_per_s")
     return round(b / BASELINE_BINDS_PER_S, 2) if b else None
+
+
+def dump_outputs(path: str, last: dict, agent_stats: list[dict]) -> None:
+    """What the last timed wave computed, as ``path/<name>.npy`` (float64; a few hundred bytes in all).  A wave's
+    caller gets a placement: from the extender's ledger as read when every pod of the wave ran (``/inspect``),
+    ``pod_device`` and ``pod_gpu_mem`` -- the device index each pod was bound to and the gpu-mem charged for it, in
+    pod-name order (-1 / 0: not in the ledger) -- and ``device_used`` / ``device_total`` per device; and
+    ``hbm_bad_stamps`` per GPU rank: stamps of resident pod slices that the HIP verify kernel found overwritten over the
+    run.  The inputs are the arguments alone (pod names, sizes and count); the uids the apiserver draws, and with
+    them the stamp values in HBM, differ from run to run and are not written."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    devs = [d for n in last["insp"]["nodes"] for d in n["devs"]]
+    where = {f'{p["namespace"]}/{p["name"]}': (d["id"], p["usedGPU"]) for d in devs for p in d["pods"]}
+    arrays = {"pod_device": [where.get(k, (-1, 0))[0] for k in last["keys"]],
+              "pod_gpu_mem": [where.get(k, (-1, 0))[1] for k in last["keys"]],
+              "device_used": [d["usedGPU"] for d in devs],
+              "device_total": [d["totalGPU"] for d in devs],
+              "hbm_bad_stamps": [x["bad_stamps"] for x in agent_stats]}
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def launch_ranks(n: int) -> int:
@@ -1153,7 +1189,7 @@ def main():
             time.sleep(0.0002)
         t_end = time.perf_counter()
         # per-pod scheduler timings are collected after the timed region (fetch_timings)
-        return {"keys": keys, "used": used, "total": total, "per_dev": per_dev,
+        return {"keys": keys, "used": used, "total": total, "per_dev": per_dev, "insp": insp,
                 "t_bound": t_bound - t0, "t_run": t_run - t0, "t_total": t_end - t0, "t0": t0,
                 "teardown": (t_insp - t_run, t_del - t_insp, t_gone - t_del, t_end - t_gone), "t_created": t_created - t0}
 
@@ -1308,6 +1344,8 @@ def main():
         st, body = api_batch.run([("GET", "/fake/stats", b"")], 1)[0]
         apiserver_stats = json.loads(body) if st == 200 else {"error": st}
         apiserver_stats.pop("counts", None)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, step_stats[-1], agent_stats)
 
     sweep = ref_client = plugin_row = plugin_row_native = None
     if rank == 0 and a.sweep:

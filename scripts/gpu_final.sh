@@ -13,7 +13,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smok
 tail -1 $OUT/smoke.log
 for i in 1 2 3; do
   sw=0; [ $i -eq 3 ] && sw=1
-  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --sweep $sw --json-out $OUT/bench$i.json > $OUT/bench$i.log 2>&1 || exit $?
+  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full --sweep $sw --json-out $OUT/bench$i.json > $OUT/bench$i.log 2>&1 || exit $?
   python -c "
 import json; d=json.load(open('$OUT/bench$i.json'))
 print('bench', $i, d['value'], d['wave_pods_per_s']['p50'], d['p50_bind_latency_ms'], d['p99_bind_latency_ms'], d['timed_region_ms']['max_over_ranks'])"

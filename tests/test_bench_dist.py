@@ -38,7 +38,7 @@ def _env():
 
 @pytest.mark.slow
 def test_bench_single_process_fake_devices():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--devices", "fake"],
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--devices", "fake", "--full"],
                        cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -59,6 +59,30 @@ def test_bench_single_process_fake_devices():
     assert ref["binding"]["pods_per_s"] > ref["update"]["pods_per_s"]
     assert d["vs_baseline_same_condition"] == round(ref["binding"]["pods_per_s"] / 2.5, 2)
     assert "bind_order_waits" in rows[("binding", 0)]
+
+
+@pytest.mark.slow
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full only the timed steps run; --dump-outputs writes the last wave's placement as float64 arrays."""
+    import numpy as np
+
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--devices", "fake",
+                        "--dump-outputs", str(tmp_path / "out")],
+                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    assert KEYS <= set(d) and d["steps"] == 3 and d["wave_pods_per_s"]["n"] == 3
+    assert d["value"] == pytest.approx(4 * 1e3 / d["ms_per_step"], rel=1e-3)  # 4 pods a step
+    assert d["latency_sweep"] is None and d["reference_client"] is None and d["open_loop"] is None
+    assert d["device_plugin_path_python_kubelet"] is None and d["inprocess_matcher_path"] is None
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert all(v.dtype == np.float64 for v in got.values())
+    # the fake device is 288 GB: 268 whole GiB
+    want = {"pod_device": [0] * 4, "pod_gpu_mem": [64] * 4, "device_used": [256], "device_total": [268],
+            "hbm_bad_stamps": [0]}
+    assert set(got) == set(want)
+    for k, v in want.items():
+        assert got[k].tolist() == v, (k, got[k])
 
 
 @pytest.mark.slow

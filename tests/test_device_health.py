@@ -38,7 +38,7 @@ def test_native_fake_backend_fault_injection():
     assert ev and ev[0]["name"] == "GPU_PRE_RESET" and ev[0]["index"] == 3
 
 
-def test_plugin_health_and_partition_change(tmp_path):
+def test_plugin_health_and_partition_change(sock_dir):
     backend = "fake:2x64GiB"
 
     async def go():
@@ -46,7 +46,7 @@ def test_plugin_health_and_partition_change(tmp_path):
         c = KubeClient(api.url)
         await c.create("nodes", make_node("n", 128, 2))
         devs = apply_memory_pools([Device(**d) for d in mxdev.enumerate_devices(backend)])
-        plugin = GpuSharePlugin(KubeClient(api.url), "n", devs, SHARED_GPU, socket_dir=str(tmp_path / "dp"),
+        plugin = GpuSharePlugin(KubeClient(api.url), "n", devs, SHARED_GPU, socket_dir=str(sock_dir / "dp"),
                                 health_backend=backend, health_interval=0.05)
         await plugin.start(register=False)
         cl = PluginClient(plugin.socket_path)

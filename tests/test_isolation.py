@@ -51,7 +51,7 @@ def test_manager_files_mounts_and_release(tmp_path):
     assert m.gc({"uid-3"}) == 1 and not m.pod_dir("uid-2").exists()
 
 
-def test_plugin_allocate_mounts_isolation_and_records(tmp_path):
+def test_plugin_allocate_mounts_isolation_and_records(tmp_path, sock_dir):
     """The gRPC Allocate answers the isolation mounts, and the record of the allocation is checkpointed."""
     from gpushare_scheduler_extender_amd.deviceplugin.devices import Device
     from gpushare_scheduler_extender_amd.deviceplugin.plugin import GpuSharePlugin
@@ -71,7 +71,7 @@ def test_plugin_allocate_mounts_isolation_and_records(tmp_path):
         pod = await c.create("pods", make_pod("a", 4, node="n", annotations=ann))
         iso = IsolationManager(str(tmp_path / "iso"), library=str(LIB))
         plugin = GpuSharePlugin(KubeClient(api.url), "n", [Device(index=0, total_bytes=16 << 30)], SHARED_GPU,
-                                socket_dir=str(tmp_path / "dp"), isolation=iso)
+                                socket_dir=str(sock_dir / "dp"), isolation=iso)
         await plugin.start(register=False, publish=False)
         cl = PluginClient(plugin.socket_path)
         try:

@@ -469,6 +469,10 @@ def test_early_answer_checkpoint_failure_keeps_the_journal_generation():
             pc = None
             await plugin.stop()
             os.rmdir(plugin.checkpoint + ".tmp")
+            # stop() closes the endpoint without yielding to this loop, which also runs the apiserver: a commit retry
+            # its serving thread sent just before is still unread.  It is answered while the fault applies, not after
+            # (where it landed, the restarted plugin found one commit to land, not two)
+            await asyncio.sleep(0.05)
             api_srv.server.faults.error_rate = 0.0
             os.environ["GSX_PLUGIN_EARLY_ANSWER"] = "0"  # restarted with the knob off: still lands the commit
             try:

@@ -139,12 +139,12 @@ def test_without_reconciliation_a_swap_lets_a_pod_land_on_a_physically_full_gpu(
     assert "Failed" in phases.values(), (phases, per_gpu)  # the node's runtime could not fit them physically
 
 
-def test_pod_resources_api_roundtrip(tmp_path):
+def test_pod_resources_api_roundtrip(sock_dir):
     """The hand-built v1 PodResourcesLister descriptor: our kubelet-side server and the plugin's client agree."""
     from gpushare_scheduler_extender_amd.deviceplugin.podresources import PodResourcesClient, PodResourcesServer
 
     async def go():
-        sock = str(tmp_path / "pr" / "kubelet.sock")
+        sock = str(sock_dir / "pr" / "kubelet.sock")
         data = [("default", "a", [("main", "aliyun.com/gpu-mem", ["g0-_-1", "g0-_-0"])]),
                 ("kube-system", "b", [("c1", "other/res", ["x"]), ("c2", "aliyun.com/gpu-mem", ["g1-_-0"])])]
         srv = PodResourcesServer(sock, lambda: data)
