@@ -47,7 +47,7 @@ def main(argv=None) -> int:
                     help="HBM per GPU withheld from sharing (driver / runtime overhead)")
     ap.add_argument("--health-interval", type=float, default=float(env.get("GSX_HEALTH_INTERVAL", "10")))
     ap.add_argument("--debug-port", type=int, default=int(env.get("GSX_DEBUG_PORT", "0")),
-                    help="serve /healthz, /metrics and /debug/state on this port (0: off)")
+                    help="serve /healthz, /metrics, /debug/state and POST /debug/memtest on this port (0: off)")
     ap.add_argument("--debug-host", default=env.get("GSX_DEBUG_HOST", "127.0.0.1"))
     ap.add_argument("--debug-port-file", default="", help="write the debug port here once it listens (port 0)")
     ap.add_argument("--no-register", action="store_true",
@@ -68,6 +68,15 @@ def main(argv=None) -> int:
                     help="run the PodResources reconciliation without a scheduler extender: swaps are detected and "
                          "the physical guard holds, but no allocation record can be repaired (tests / diagnosis)")
     ap.add_argument("--reconcile-interval", type=float, default=float(env.get("GSX_RECONCILE_INTERVAL", "2")))
+    ap.add_argument("--preflight", default=env.get("GSX_PREFLIGHT", "off"), choices=["off", "quick", "full"],
+                    help="HBM memory test (gsx-memtest, one child process per GPU) of every GPU without tenants before "
+                         "the plugin serves: a GPU with memory errors is advertised Unhealthy until a later run is "
+                         "clean (POST /debug/memtest?device=N on the debug port runs one on demand)")
+    ap.add_argument("--preflight-gib", type=float, default=float(env.get("GSX_PREFLIGHT_GIB", "0")),
+                    help="GiB per GPU the pre-flight tests (0: all free memory minus the tool's 1 GiB reserve)")
+    ap.add_argument("--preflight-timeout", type=float, default=float(env.get("GSX_PREFLIGHT_TIMEOUT", "120")),
+                    help="seconds a pre-flight child may take; it ends itself at 80 %% of it (a truncated run is no "
+                         "failure), is killed at 100 %%, and a test that could not run leaves the GPU Healthy")
     ap.add_argument("--log-level", default=env.get("LOG_LEVEL", "info"))
     ap.add_argument("--log-dir", default=env.get("GSX_LOG_DIR", ""))
     a = ap.parse_args(argv)
@@ -93,7 +102,9 @@ def main(argv=None) -> int:
                                 mount_mode=a.mount_mode, health_backend="amdsmi" if backend == "amdsmi" else None,
                                 health_interval=a.health_interval, reserve_bytes=int(a.reserve_gib * (1 << 30)),
                                 podresources_socket=a.podresources_socket or None,
-                                reconcile_interval=a.reconcile_interval, isolation=iso, extender=a.extender or None)
+                                reconcile_interval=a.reconcile_interval, isolation=iso, extender=a.extender or None,
+                                preflight=a.preflight, preflight_gib=a.preflight_gib,
+                                preflight_timeout=a.preflight_timeout)
         # the debug endpoint first: its setup (importing aiohttp) blocks the loop for a few hundred ms, and once the
         # plugin serves, kubelet's Allocates must find the reconciliation (this loop) running
         if a.debug_port or a.debug_port_file:

@@ -26,6 +26,25 @@ class DevInfo(ctypes.Structure):
                 ("clock_khz", ctypes.c_int32), ("wave_size", ctypes.c_int32), ("lds_per_block", ctypes.c_uint64)]
 
 
+class MemtestErr(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_uint64), ("expected", ctypes.c_uint32), ("actual", ctypes.c_uint32)]
+
+
+class MemtestPass(ctypes.Structure):
+    _fields_ = [("pattern", ctypes.c_int), ("seed", ctypes.c_uint32), ("invert", ctypes.c_int),
+                ("rewrite", ctypes.c_int), ("write", ctypes.c_int)]
+
+
+class MemtestReport(ctypes.Structure):
+    """``gsx_memtest_report``: checks accumulate into it; a new one is all zero."""
+    _fields_ = [("bad_dwords", ctypes.c_uint64), ("flipped_or", ctypes.c_uint32), ("n_errs", ctypes.c_uint32),
+                ("errs", MemtestErr * 32)]
+
+    def errors(self) -> list[tuple[int, int, int]]:
+        """The recorded ``(offset, expected, actual)`` of up to 32 bad dwords."""
+        return [(e.offset, e.expected, e.actual) for e in self.errs[:self.n_errs]]
+
+
 def lib():
     global _LIB
     if _LIB is not None:
@@ -62,6 +81,12 @@ def lib():
             "gsx_hbm_fill": ([vp, vp, u64, ctypes.c_uint32], i32),
             "gsx_gemm_bf16_nt": ([vp, vp, vp, vp, i32, i32, i32], i32),
             "gsx_event_time_gemm": ([vp, vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
+            "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
+                                  i32),
+            "gsx_memtest_pass": ([i32, ctypes.c_uint32, ctypes.POINTER(MemtestPass)], i32),
+            "gsx_memtest_run": ([vp, vp, u64, u64, i32, ctypes.POINTER(MemtestReport),
+                                 ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)], i32),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -208,6 +233,45 @@ def hbm_verify(stream: Stream, addr: int, nbytes: int, stride: int, tag: int) ->
 
 def hbm_fill(stream: Stream, addr: int, nbytes: int, pattern: int = 0):
     _ck(lib().gsx_hbm_fill(stream.handle, ctypes.c_void_p(addr), nbytes, pattern & 0xFFFFFFFF), "hbm_fill")
+
+
+def memtest_write(stream: Stream, addr: int, nbytes: int, origin: int, pattern: int, seed: int = 0,
+                  invert: bool = False):
+    """Store the pattern's words ``origin // 16 ...`` into ``[addr, addr + nbytes)``; not synchronised."""
+    _ck(lib().gsx_memtest_write(stream.handle, ctypes.c_void_p(addr), nbytes, origin, pattern, seed & 0xFFFFFFFF,
+                                int(invert)), "memtest_write")
+
+
+def memtest_check(stream: Stream, addr: int, nbytes: int, origin: int, pattern: int, seed: int = 0,
+                  invert: bool = False, rewrite: bool = False, report: MemtestReport | None = None) -> MemtestReport:
+    """Compare every dword with the regenerated pattern, accumulating into ``report`` (a fresh one by default);
+    ``rewrite`` stores the complement of the expected word in the same pass.  Synchronises the stream."""
+    rep = MemtestReport() if report is None else report
+    _ck(lib().gsx_memtest_check(stream.handle, ctypes.c_void_p(addr), nbytes, origin, pattern, seed & 0xFFFFFFFF,
+                                int(invert), int(rewrite), ctypes.byref(rep)), "memtest_check")
+    return rep
+
+
+def memtest_run(stream: Stream, addr: int, nbytes: int, origin: int = 0, level: str = "quick",
+                report: MemtestReport | None = None) -> tuple[MemtestReport, int, float]:
+    """Run a level's pass sequence (``ops.memtest.LEVELS``): ``(report, passes, seconds)``."""
+    from .memtest import LEVEL_IDS  # noqa: PLC0415
+
+    rep = MemtestReport() if report is None else report
+    passes, seconds = ctypes.c_uint32(0), ctypes.c_double(0.0)
+    _ck(lib().gsx_memtest_run(stream.handle, ctypes.c_void_p(addr), nbytes, origin, LEVEL_IDS[level],
+                              ctypes.byref(rep), ctypes.byref(passes), ctypes.byref(seconds)), "memtest_run")
+    return rep, passes.value, seconds.value
+
+
+def memtest_pass_table(level: str) -> list[tuple[str, int, int, int, int]]:
+    """The native pass sequence of a level, in the form of ``ops.memtest.LEVELS``."""
+    from .memtest import LEVEL_IDS  # noqa: PLC0415
+
+    out, p = [], MemtestPass()
+    while lib().gsx_memtest_pass(LEVEL_IDS[level], len(out), ctypes.byref(p)) == 0:
+        out.append(("write" if p.write else "check", p.pattern, p.seed, p.invert, p.rewrite))
+    return out
 
 
 def gemm_bf16_nt(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int):

@@ -11,6 +11,8 @@
 //                          the binpack allocator really fit and never overlap;
 //  * HBM scrub           — full-bandwidth 16 B/lane fill used to wipe a slice
 //                          when a pod leaves (and as the HBM roofline probe);
+//  * HBM memory test     — pattern write / check / moving-inversions passes at HBM
+//                          bandwidth: the device plugin's pre-flight (memtest.hip);
 //  * bf16 MFMA GEMM      — the pod workload used to measure isolation
 //                          (throughput under per-pod CU partitions);
 //  * CU-masked streams   — hipExtStreamCreateWithCUMask.
@@ -93,6 +95,47 @@ int gsx_gemm_bf16_nt(void* stream, const void* A, const void* B, void* C, int M,
 // elapsed milliseconds of running `fn` on stream via hip events (for benches)
 int gsx_event_time_gemm(void* stream, const void* A, const void* B, void* C, int M, int N, int K, int iters,
                         float* ms);
+
+// HBM pre-flight memory test (memtest.hip).  The expected content of 16-byte word W = origin/16 + word index is
+// generated from (pattern, seed, invert, W) and never stored; `origin` is the byte offset of `base` in the whole
+// tested range, so a range tested chunk by chunk keeps globally unique content.
+//   ADDR    dwords {lo32(W), hi32(W), ~lo32(W), ~hi32(W)}
+//   SOLID   every dword = seed
+//   WALK    dword j = 1u << ((4*W + j + seed) & 31)
+//   RANDOM  two 64-bit outputs of a counter-based mixer (splitmix64's output function) of 2*W + half and seed
+// invert != 0 complements all four dwords.  bytes and origin are multiples of 16; base is 16-B aligned.
+enum { GSX_MEMTEST_ADDR = 0, GSX_MEMTEST_SOLID = 1, GSX_MEMTEST_WALK = 2, GSX_MEMTEST_RANDOM = 3 };
+enum { GSX_MEMTEST_QUICK = 0, GSX_MEMTEST_FULL = 1 };
+typedef struct {
+  uint64_t offset;  // origin + byte offset of the dword
+  uint32_t expected, actual;
+} gsx_memtest_err;
+#define GSX_MEMTEST_MAX_ERRS 32
+typedef struct {
+  uint64_t bad_dwords;  // exact count
+  uint32_t flipped_or;  // OR of expected ^ actual over all bad dwords
+  uint32_t n_errs;      // min(bad_dwords, MAX_ERRS)
+  gsx_memtest_err errs[GSX_MEMTEST_MAX_ERRS];
+} gsx_memtest_report;
+// One launch on `stream`, not synchronised.
+int gsx_memtest_write(void* stream, void* base, uint64_t bytes, uint64_t origin, int pattern, uint32_t seed,
+                      int invert);
+// Compares every dword and ACCUMULATES into *report (the caller zeroes it); one stream sync.  rewrite != 0 also
+// stores the complement of the expected word in the same pass (moving inversions: a bad word is overwritten
+// with correct data).  The per-launch counters live in pinned host memory, as gsx_hbm_admit's do.
+int gsx_memtest_check(void* stream, void* base, uint64_t bytes, uint64_t origin, int pattern, uint32_t seed,
+                      int invert, int rewrite, gsx_memtest_report* report);
+// The fixed pass sequence of a level, each a triple {write, check + rewrite, check inverted}: QUICK runs ADDR and
+// RANDOM (8 x bytes of traffic); FULL adds SOLID with seeds 0, ~0, 0x55555555, 0xAAAAAAAA and WALK with seeds 0..31.
+int gsx_memtest_run(void* stream, void* base, uint64_t bytes, uint64_t origin, int level, gsx_memtest_report* report,
+                    uint32_t* passes_out, double* seconds_out);
+// Pass `idx` of a level's sequence (what gsx_memtest_run and gsx-memtest execute): 0, or 1 past the last pass.
+typedef struct {
+  int pattern;
+  uint32_t seed;
+  int invert, rewrite, write;  // write != 0: a write pass; otherwise a check, with or without rewrite
+} gsx_memtest_pass_t;
+int gsx_memtest_pass(int level, uint32_t idx, gsx_memtest_pass_t* out);
 
 #ifdef __cplusplus
 }

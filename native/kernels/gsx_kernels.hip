@@ -184,6 +184,9 @@ int grid_for(uint64_t n, int per_block, int max_blocks) {
 
 }  // namespace
 
+// for the library's other translation units (memtest.hip): the text gsx_last_error() returns on this thread
+extern "C" __attribute__((visibility("hidden"))) void gsx_internal_set_error(const char* what) { g_err = what; }
+
 extern "C" {
 
 const char* gsx_last_error(void) { return g_err.c_str(); }
