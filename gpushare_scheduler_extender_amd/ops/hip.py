@@ -1,4 +1,4 @@
-"""ctypes binding of ``libgsx_kernels.so`` (native/kernels/gsx_kernels.hip).
+"""ctypes binding of ``libgsx_kernels.so`` (native/kernels, C ABI in gsx_kernels.h).
 
 No silent fallback: on a host with a GPU every call goes to the HIP code,
 and a missing library raises with the command that builds it.  Callers that
@@ -45,6 +45,10 @@ class MemtestReport(ctypes.Structure):
         return [(e.offset, e.expected, e.actual) for e in self.errs[:self.n_errs]]
 
 
+class Slice(ctypes.Structure):
+    _fields_ = [("addr", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("tag", ctypes.c_uint64)]
+
+
 def lib():
     global _LIB
     if _LIB is not None:
@@ -78,8 +82,11 @@ def lib():
             "gsx_cuprobe": ([vp, i32, i32, u32p], i32),
             "gsx_hbm_stamp": ([vp, vp, u64, u64, u64], i32),
             "gsx_hbm_verify": ([vp, vp, u64, u64, u64, ctypes.POINTER(u64)], i32),
+            "gsx_hbm_admit_n": ([vp, ctypes.POINTER(Slice), i32, i32, i32, u64, ctypes.POINTER(u64)], i32),
             "gsx_hbm_fill": ([vp, vp, u64, ctypes.c_uint32], i32),
             "gsx_gemm_bf16_nt": ([vp, vp, vp, vp, i32, i32, i32], i32),
+            "gsx_gemm_bf16_nt_launch_cfg": ([vp, vp, vp, vp, i32, i32, i32, i32], i32),
+            "gsx_gemm_cfg_tile": ([i32, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
             "gsx_event_time_gemm": ([vp, vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
             "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
@@ -286,36 +293,12 @@ def time_gemm(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, it
     return ms.value
 
 
-class Slice(ctypes.Structure):
-    _fields_ = [("addr", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("tag", ctypes.c_uint64)]
-
-
-def hbm_admit(stream: Stream, slices: list[tuple[int, int, int]], stamp_idx: int, stride: int) -> int:
-    """Stamp slice ``stamp_idx`` (or none with -1) and verify all ``(addr, bytes, tag)`` slices in one launch."""
-    L = lib()
-    if not getattr(L, "_admit_sig", False):
-        L.gsx_hbm_admit.argtypes = [ctypes.c_void_p, ctypes.POINTER(Slice), ctypes.c_int, ctypes.c_int,
-                                    ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
-        L.gsx_hbm_admit.restype = ctypes.c_int
-        L._admit_sig = True
-    arr = (Slice * max(1, len(slices)))(*[Slice(a, b, t & 0xFFFFFFFFFFFFFFFF) for a, b, t in slices])
-    bad = ctypes.c_uint64(0)
-    _ck(L.gsx_hbm_admit(stream.handle, arr, len(slices), stamp_idx, stride, ctypes.byref(bad)), "hbm_admit")
-    return bad.value
-
-
 def hbm_admit_n(stream: Stream, slices: list[tuple[int, int, int]], n_stamp: int, stride: int,
                 verify: bool = True) -> int:
     """Stamp the first ``n_stamp`` ``(addr, bytes, tag)`` extents, then verify all of them; one stream sync."""
-    L = lib()
-    if not getattr(L, "_admit_n_sig", False):
-        L.gsx_hbm_admit_n.argtypes = [ctypes.c_void_p, ctypes.POINTER(Slice), ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
-        L.gsx_hbm_admit_n.restype = ctypes.c_int
-        L._admit_n_sig = True
     arr = (Slice * max(1, len(slices)))(*[Slice(a, b, t & 0xFFFFFFFFFFFFFFFF) for a, b, t in slices])
     bad = ctypes.c_uint64(0)
-    _ck(L.gsx_hbm_admit_n(stream.handle, arr, len(slices), n_stamp, int(verify), stride, ctypes.byref(bad)),
+    _ck(lib().gsx_hbm_admit_n(stream.handle, arr, len(slices), n_stamp, int(verify), stride, ctypes.byref(bad)),
         "hbm_admit_n")
     return bad.value
 
@@ -328,12 +311,6 @@ GEMM_CFGS = {0: "128x128/4w", 1: "256x128/8w", 2: "128x256/8w", 3: "256x256/8w",
 def gemm_bf16_nt_cfg(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, cfg: int):
     """Launch one tile configuration of the templated GEMM (native/kernels/gemm.hip)."""
     L = lib()
-    if not getattr(L, "_cfg_sig", False):
-        L.gsx_gemm_bf16_nt_launch_cfg.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4
-        L.gsx_gemm_bf16_nt_launch_cfg.restype = ctypes.c_int
-        L.gsx_gemm_cfg_tile.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-        L.gsx_gemm_cfg_tile.restype = ctypes.c_int
-        L._cfg_sig = True
     bm, bn = ctypes.c_int(0), ctypes.c_int(0)
     if L.gsx_gemm_cfg_tile(cfg, ctypes.byref(bm), ctypes.byref(bn)) != 0:
         raise HipError(f"unknown GEMM config {cfg}")

@@ -8,7 +8,8 @@
 //                          checked against what the hardware actually used;
 //  * HBM stamp / verify  — a pod's gpu-mem slice is stamped with its tag and
 //                          verified later: proves co-resident pods placed by
-//                          the binpack allocator really fit and never overlap;
+//                          the binpack allocator really fit and never overlap
+//                          (hbm_stamp.hip);
 //  * HBM scrub           — full-bandwidth 16 B/lane fill used to wipe a slice
 //                          when a pod leaves (and as the HBM roofline probe);
 //  * HBM memory test     — pattern write / check / moving-inversions passes at HBM
@@ -64,23 +65,20 @@ int gsx_memcpy_h2d(void* dst, const void* src, uint64_t bytes);
 // (may be a CU-masked stream) and synchronises it.
 int gsx_cuprobe(void* stream, int blocks, int spin, uint32_t* out_host);
 
-// HBM stamp/verify: 16-byte stamps {tag, offset} every `stride` bytes of
-// [base, base+bytes).  verify returns the number of bad stamps in *bad.
+// HBM stamp/verify (hbm_stamp.hip): 16-byte stamps {tag, offset} every `stride` bytes of
+// [base, base+bytes).  stamp launches and returns without synchronising; verify returns the
+// number of bad stamps in *bad after one stream sync.
 int gsx_hbm_stamp(void* stream, void* base, uint64_t bytes, uint64_t stride, uint64_t tag);
 int gsx_hbm_verify(void* stream, const void* base, uint64_t bytes, uint64_t stride, uint64_t tag, uint64_t* bad);
-// Batched pod admission: optionally stamp slice `stamp_idx` (-1: none), then
-// verify every slice in ONE launch; *bad = total bad stamps.  The bad-stamp
-// counter lives in pinned host memory, so there is no memset / copy kernel
-// and exactly one stream sync per call.
+// Batched pod admission.  A pod is made of one or several extents (its slice is not contiguous when the arena
+// is fragmented): stamp slices[0, n_stamp), then (verify != 0) verify all n slices, each in one launch per 32
+// extents; *bad = total bad stamps.  The bad-stamp counter lives in pinned host memory, so there is no memset /
+// copy kernel and exactly one stream sync per call.
 typedef struct {
   uint64_t addr;
   uint64_t bytes;
   uint64_t tag;
 } gsx_slice;
-int gsx_hbm_admit(void* stream, const gsx_slice* slices, int n, int stamp_idx, uint64_t stride, uint64_t* bad);
-// Admission of a pod made of several extents (its slice is not contiguous when the arena is
-// fragmented): stamp slices[0, n_stamp) in one launch, then (verify != 0) verify all n slices;
-// one stream sync.
 int gsx_hbm_admit_n(void* stream, const gsx_slice* slices, int n, int n_stamp, int verify, uint64_t stride,
                     uint64_t* bad);
 
@@ -122,7 +120,7 @@ int gsx_memtest_write(void* stream, void* base, uint64_t bytes, uint64_t origin,
                       int invert);
 // Compares every dword and ACCUMULATES into *report (the caller zeroes it); one stream sync.  rewrite != 0 also
 // stores the complement of the expected word in the same pass (moving inversions: a bad word is overwritten
-// with correct data).  The per-launch counters live in pinned host memory, as gsx_hbm_admit's do.
+// with correct data).  The per-launch counters live in pinned host memory, as gsx_hbm_admit_n's do.
 int gsx_memtest_check(void* stream, void* base, uint64_t bytes, uint64_t origin, int pattern, uint32_t seed,
                       int invert, int rewrite, gsx_memtest_report* report);
 // The fixed pass sequence of a level, each a triple {write, check + rewrite, check inverted}: QUICK runs ADDR and

@@ -8,13 +8,13 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
-#include <cstdio>
 #include <cstring>
 #include <mutex>
 
+#include "gsx_internal.h"
 #include "gsx_kernels.h"
 
-extern "C" void gsx_internal_set_error(const char* what);  // gsx_kernels.hip: the text of gsx_last_error()
+using namespace gsx;
 
 namespace {
 
@@ -199,44 +199,25 @@ __global__ __launch_bounds__(256) void memtest_kernel(uint4* __restrict__ p, uin
 }
 
 std::mutex g_mu;
-LaunchReport g_rep[64] = {};  // pinned, device-visible; one per device, for the largest grid (8 blocks per CU)
-int g_cus[64] = {0};
-std::mutex g_dev_mu[64];
-
-int fail(hipError_t e, const char* what) {
-  char buf[256];
-  std::snprintf(buf, sizeof(buf), "%s: %s (%d)", what, hipGetErrorString(e), static_cast<int>(e));
-  gsx_internal_set_error(buf);
-  return static_cast<int>(e);
-}
-
-int fail_arg(const char* what) {
-  gsx_internal_set_error(what);
-  return static_cast<int>(hipErrorInvalidValue);
-}
-
-#define MT_CHECK(call)                            \
-  do {                                            \
-    hipError_t _e = (call);                       \
-    if (_e != hipSuccess) return fail(_e, #call); \
-  } while (0)
+LaunchReport g_rep[kMaxDevices] = {};  // pinned, device-visible; one per device, for the largest grid (8 blocks / CU)
+int g_cus[kMaxDevices] = {0};
+std::mutex g_dev_mu[kMaxDevices];  // its own, not the stamp counter's: a memory test never waits for an admission
 
 // the current device, its CU count and its pinned launch report
 int device_state(int* dev, int* cus, LaunchReport* rep) {
-  MT_CHECK(hipGetDevice(dev));
-  if (*dev < 0 || *dev >= 64) return fail_arg("gsx_memtest: device index");
+  if (int rc = current_device("gsx_memtest", dev)) return rc;
   std::lock_guard<std::mutex> g(g_mu);
   if (!g_cus[*dev]) {
     int n = 0;
-    MT_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, *dev));
+    GSX_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, *dev));
     g_cus[*dev] = n > 0 ? n : 1;
   }
   if (rep && !g_rep[*dev].recs) {
     const size_t waves = static_cast<size_t>(g_cus[*dev]) * 8 * 4;
-    MT_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g_rep[*dev].heads), waves * sizeof(WaveHead),
-                           hipHostMallocCoherent));
-    MT_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g_rep[*dev].recs), waves * kMaxErrs * sizeof(gsx_memtest_err),
-                           hipHostMallocCoherent));
+    GSX_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g_rep[*dev].heads), waves * sizeof(WaveHead),
+                            hipHostMallocCoherent));
+    GSX_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g_rep[*dev].recs), waves * kMaxErrs * sizeof(gsx_memtest_err),
+                            hipHostMallocCoherent));
   }
   *cus = g_cus[*dev];
   if (rep) *rep = g_rep[*dev];
@@ -274,7 +255,7 @@ int launch(hipStream_t st, int grid, int pattern, uint4* p, uint64_t n16, uint64
     default:
       return fail_arg("gsx_memtest: unknown pattern");
   }
-  MT_CHECK(hipGetLastError());
+  GSX_CHECK(hipGetLastError());
   return 0;
 }
 
@@ -295,8 +276,8 @@ int gsx_memtest_write(void* stream, void* base, uint64_t bytes, uint64_t origin,
   if (!bytes) return 0;
   int dev = 0, cus = 0;
   if (int rc = device_state(&dev, &cus, nullptr)) return rc;
-  return launch<kWrite>(reinterpret_cast<hipStream_t>(stream), grid_for(bytes / 16, cus), pattern,
-                        static_cast<uint4*>(base), bytes / 16, origin / 16, seed, invert ? 0xFFFFFFFFu : 0u, LaunchReport{});
+  return launch<kWrite>(S(stream), grid_for(bytes / 16, cus), pattern, static_cast<uint4*>(base), bytes / 16,
+                        origin / 16, seed, invert ? 0xFFFFFFFFu : 0u, LaunchReport{});
 }
 
 int gsx_memtest_check(void* stream, void* base, uint64_t bytes, uint64_t origin, int pattern, uint32_t seed,
@@ -307,7 +288,7 @@ int gsx_memtest_check(void* stream, void* base, uint64_t bytes, uint64_t origin,
   int dev = 0, cus = 0;
   LaunchReport rep{};
   if (int rc = device_state(&dev, &cus, &rep)) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = S(stream);
   // reset -> launch -> read back under the device's mutex: concurrent callers never mix their reports
   std::lock_guard<std::mutex> dl(g_dev_mu[dev]);
   const int grid = grid_for(bytes / 16, cus);
@@ -320,7 +301,7 @@ int gsx_memtest_check(void* stream, void* base, uint64_t bytes, uint64_t origin,
                    : launch<kCheck>(st, grid, pattern, static_cast<uint4*>(base), bytes / 16, origin / 16, seed, inv,
                                     rep);
   if (rc) return rc;
-  MT_CHECK(hipStreamSynchronize(st));
+  GSX_CHECK(hipStreamSynchronize(st));
   __atomic_thread_fence(__ATOMIC_SEQ_CST);
   for (size_t w = 0; w < waves; ++w) {
     const WaveHead h = rep.heads[w];

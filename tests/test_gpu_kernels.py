@@ -54,16 +54,16 @@ def test_hbm_admit_batched_stamp_and_verify(hip):
     mib16, st = 16 << 20, 1 << 16
     a = (buf.addr(0), mib16, 11)
     b = (buf.addr(mib16), mib16, 22)
-    assert hip.hbm_admit(s, [a], 0, st) == 0
-    assert hip.hbm_admit(s, [a, b], 1, st) == 0
+    assert hip.hbm_admit_n(s, [a], 1, st) == 0
+    assert hip.hbm_admit_n(s, [b, a], 1, st) == 0
     # a pod wrongly placed over the second half of a and the first half of b
     c = (buf.addr(mib16 // 2), mib16, 33)
-    assert hip.hbm_admit(s, [a, b, c], 2, st) == 2 * (mib16 // 2) // st
-    assert hip.hbm_admit(s, [c], -1, st) == 0
+    assert hip.hbm_admit_n(s, [c, a, b], 1, st) == 2 * (mib16 // 2) // st
+    assert hip.hbm_admit_n(s, [c], 0, st) == 0
     # more slices than one launch's table (32): chunked launches
     many = [(buf.addr(i * (1 << 20)), 1 << 20, 100 + i) for i in range(40)]
     for i in range(40):
-        assert hip.hbm_admit(s, many[: i + 1], i, st) == 0
+        assert hip.hbm_admit_n(s, [many[i]] + many[:i], 1, st) == 0
     buf.free()
     s.destroy()
 
@@ -298,7 +298,7 @@ def test_hbm_verify_counts_are_per_call_under_concurrency(hip):
         hip.hbm_stamp(s, b.addr(0), 32 * mib, st, 77)
         s.sync()
     n = (32 * mib) // st
-    errs = []
+    errs, done = [], []
 
     def run(i):
         want = 0 if i == 0 else n  # thread 1 verifies against the wrong tag: every stamp is bad
@@ -308,10 +308,11 @@ def test_hbm_verify_counts_are_per_call_under_concurrency(hip):
             if got != want:
                 errs.append((i, got, want))
                 return
-            got = hip.hbm_admit(streams[i], [(bufs[i].addr(0), 32 * mib, tag)], -1, st)
+            got = hip.hbm_admit_n(streams[i], [(bufs[i].addr(0), 32 * mib, tag)], 0, st)
             if got != want:
                 errs.append((i, "admit", got, want))
                 return
+        done.append(i)  # a call that raised ends its thread before this line
     ts = [threading.Thread(target=run, args=(i,)) for i in range(2)]
     for t in ts:
         t.start()
@@ -321,3 +322,153 @@ def test_hbm_verify_counts_are_per_call_under_concurrency(hip):
         b.free()
         s.destroy()
     assert not errs, errs[:3]
+    assert sorted(done) == [0, 1], done
+
+
+# ---- characterisation of the stamp / verify paths against a NumPy twin --------------------------------------
+# Stamp i of an extent is the 16 bytes {tag, i * stride} (two little-endian u64) at byte i * stride of the extent;
+# a stamp is bad when either word differs.  The twin works on a host byte array that mirrors the device buffer.
+
+def _twin_stamp(arr, off, nbytes, stride, tag):
+    import numpy as np
+
+    for i in range(nbytes // stride):
+        arr[off + i * stride: off + i * stride + 16] = np.array([tag, i * stride], dtype="<u8").view(np.uint8)
+
+
+def _twin_bad(arr, off, nbytes, stride, tag):
+    import numpy as np
+
+    bad = 0
+    for i in range(nbytes // stride):
+        got = arr[off + i * stride: off + i * stride + 16].view("<u8")
+        bad += int(got[0] != tag or got[1] != i * stride)
+    return bad
+
+
+def _readback(buf):
+    import numpy as np
+
+    return np.frombuffer(buf.to_host(), dtype=np.uint8)
+
+
+def test_hbm_stamp_content_byte_for_byte(hip):
+    """Both stamping entry points write exactly the twin's bytes: an extent that is only 16-B aligned, a stride
+    that is no power of two, a trailing partial stride, and nothing outside the stamps is touched."""
+    import numpy as np
+
+    size, off, stride, tag = 1 << 20, 48, 4112, 0x1122334455667788
+    nbytes = 5 * stride + 40
+    want = np.full(size, 0xA5, dtype=np.uint8)
+    _twin_stamp(want, off, nbytes, stride, tag)
+    assert int((want != 0xA5).sum()) > 0
+    s = hip.Stream(0)
+    for how in ("stamp", "admit_n"):
+        buf = hip.DeviceBuffer(0, size)
+        buf.from_host(bytes([0xA5]) * size)
+        if how == "stamp":
+            hip.hbm_stamp(s, buf.addr(off), nbytes, stride, tag)
+            s.sync()
+        else:
+            assert hip.hbm_admit_n(s, [(buf.addr(off), nbytes, tag)], 1, stride, verify=False) == 0
+        got = _readback(buf)
+        buf.free()
+        assert np.array_equal(got, want), (how, np.flatnonzero(got != want)[:8])
+    s.destroy()
+
+
+@pytest.mark.parametrize("cap,how", [(8192, "single"), (1024, "table")])
+def test_hbm_stamps_beyond_one_pass_of_the_grid(hip, cap, how):
+    """``cap * 256 + 257`` stamps at stride 16: every lane of the capped grid takes a second trip of the grid-stride
+    loop and one block a ragged third (single-range cap 8192 blocks, table cap 1024 blocks per row)."""
+    import numpy as np
+
+    n, stride, tag = cap * 256 + 257, 16, 0xC0FFEE
+    nbytes = n * stride
+    s = hip.Stream(0)
+    buf = hip.DeviceBuffer(0, nbytes)
+    buf.from_host(bytes(nbytes))
+    ext = (buf.addr(0), nbytes, tag)
+    if how == "single":
+        hip.hbm_stamp(s, *ext[:2], stride, tag)
+        assert hip.hbm_verify(s, *ext[:2], stride, tag) == 0
+    else:
+        assert hip.hbm_admit_n(s, [ext], 1, stride) == 0
+    want = np.empty((n, 2), dtype="<u8")
+    want[:, 0] = tag
+    want[:, 1] = np.arange(n, dtype=np.uint64) * stride
+    got = _readback(buf).view("<u8").reshape(n, 2)
+    assert np.array_equal(got, want), np.flatnonzero((got != want).any(axis=1))[:8]
+    # five bad stamps written from the host, around the ends of the grid's first pass: wrong tag or wrong offset
+    for k, i in enumerate((0, cap * 256 - 1, cap * 256, n - 1, n // 2 + 3)):
+        words = [tag + 1, i * stride] if k % 2 == 0 else [tag, i * stride + 16]
+        buf.from_host(np.array(words, dtype="<u8").tobytes(), i * stride)
+    assert hip.hbm_verify(s, *ext[:2], stride, tag) == 5
+    assert hip.hbm_admit_n(s, [ext], 0, stride) == 5
+    buf.free()
+    s.destroy()
+
+
+def test_hbm_admit_n_ragged_table_across_the_chunk(hip):
+    """40 disjoint extents of differing sizes (zero stamps, one stamp, several with more than one block's 256),
+    33 of them stamped: two chunks of the 32-row table for the stamp and for the verify.  Then an extent placed
+    over two of them: the count is the one the twin gets by replaying the same writes on a host byte array."""
+    import numpy as np
+
+    stride, slot = 64, 1 << 16
+    counts = [0, 1, 257, 300, 700, 1000] + [(k * 37) % 90 + 2 for k in range(6, 40)]
+    lens = [stride - 16 if c == 0 else c * stride + (k % 3) * 8 for k, c in enumerate(counts)]
+    assert all(n <= slot for n in lens)
+    size = 40 * slot
+    s = hip.Stream(0)
+    buf = hip.DeviceBuffer(0, size)
+    ext = [(buf.addr(k * slot), lens[k], 900 + k) for k in range(40)]
+    # the seven extents that this admission does not stamp are resident already: their stamps come from the host
+    host = np.full(size, 0x3C, dtype=np.uint8)
+    for k in range(33, 40):
+        _twin_stamp(host, k * slot, lens[k], stride, 900 + k)
+    buf.from_host(host.tobytes())
+    assert hip.hbm_admit_n(s, ext, 33, stride) == 0
+    for k in range(33):
+        _twin_stamp(host, k * slot, lens[k], stride, 900 + k)
+    got = _readback(buf)
+    assert np.array_equal(got, host), np.flatnonzero(got != host)[:8]
+    # over the tail of extent 4 (from its stamp 100) and the first 50 stamps of extent 5
+    x_off, x_len = 4 * slot + 100 * stride, (slot - 100 * stride) + 50 * stride + 8
+    assert hip.hbm_admit_n(s, [(buf.addr(x_off), x_len, 77)], 1, stride, verify=False) == 0
+    _twin_stamp(host, x_off, x_len, stride, 77)
+    want = sum(_twin_bad(host, k * slot, lens[k], stride, 900 + k) for k in range(40))
+    assert want == 600 + 50
+    assert hip.hbm_admit_n(s, ext, 0, stride) == want
+    got = _readback(buf)
+    assert np.array_equal(got, host), np.flatnonzero(got != host)[:8]
+    buf.free()
+    s.destroy()
+
+
+def test_hbm_rejected_arguments_name_their_entry_point(hip):
+    """Every rejected call raises with the entry point's name in the text and leaves nothing held: valid calls on
+    the same device succeed right afterwards."""
+    st = 1 << 12
+    s = hip.Stream(0)
+    buf = hip.DeviceBuffer(0, 1 << 20)
+    a, nb = buf.addr(0), 1 << 20
+    cases = []
+    for stride, base in ((8, a), (24, a), (st, a + 8)):
+        cases += [("gsx_hbm_stamp", lambda stride=stride, base=base: hip.hbm_stamp(s, base, nb // 2, stride, 5)),
+                  ("gsx_hbm_verify", lambda stride=stride, base=base: hip.hbm_verify(s, base, nb // 2, stride, 5)),
+                  ("gsx_hbm_admit_n", lambda stride=stride, base=base:
+                   hip.hbm_admit_n(s, [(a, 4096, 5), (base, nb // 2, 5)], 1, stride))]
+    cases += [("gsx_hbm_stamp", lambda: hip.hbm_stamp(s, 0, nb, st, 5)),
+              ("gsx_hbm_verify", lambda: hip.hbm_verify(s, 0, nb, st, 5)),
+              ("gsx_hbm_admit_n", lambda: hip.hbm_admit_n(s, [(a, nb, 5), (0, nb, 6)], 1, st)),
+              ("gsx_hbm_admit_n", lambda: hip.hbm_admit_n(s, [(a, nb, 5)], 2, st))]
+    for name, call in cases:
+        with pytest.raises(hip.HipError) as e:
+            call()
+        assert name + ":" in str(e.value), (name, str(e.value))
+    assert hip.hbm_admit_n(s, [(a, nb, 5)], 1, st) == 0
+    assert hip.hbm_verify(s, a, nb, st, 5) == 0
+    assert hip.hbm_verify(s, a, nb, st, 6) == nb // st
+    buf.free()
+    s.destroy()
