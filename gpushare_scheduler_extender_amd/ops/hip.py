@@ -87,6 +87,7 @@ def lib():
             "gsx_gemm_bf16_nt": ([vp, vp, vp, vp, i32, i32, i32], i32),
             "gsx_gemm_bf16_nt_launch_cfg": ([vp, vp, vp, vp, i32, i32, i32, i32], i32),
             "gsx_gemm_cfg_tile": ([i32, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
+            "gsx_gemm_cfg_name": ([i32], ctypes.c_char_p),
             "gsx_event_time_gemm": ([vp, vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
             "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
@@ -303,20 +304,15 @@ def hbm_admit_n(stream: Stream, slices: list[tuple[int, int, int]], n_stamp: int
     return bad.value
 
 
-GEMM_CFGS = {0: "128x128/4w", 1: "256x128/8w", 2: "128x256/8w", 3: "256x256/8w", 4: "128x128/4w-nogroup",
-             5: "256x256/8w-phased-g4", 6: "256x256/8w-phased-g8", 7: "256x256/4w-agpr-g4", 8: "256x256/4w-agpr-g8",
-             9: "256x256/4w-asm-agpr-g4", 10: "256x256/8w-phased-g4-mfma32"}
+def gemm_cfgs() -> dict[int, str]:
+    """``{index: name}`` of the tile configurations, read from the library's table (native/kernels/gemm.hip)."""
+    out: dict[int, str] = {}
+    while (name := lib().gsx_gemm_cfg_name(len(out))) is not None:
+        out[len(out)] = name.decode()
+    return out
 
 
 def gemm_bf16_nt_cfg(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, cfg: int):
-    """Launch one tile configuration of the templated GEMM (native/kernels/gemm.hip)."""
-    L = lib()
-    bm, bn = ctypes.c_int(0), ctypes.c_int(0)
-    if L.gsx_gemm_cfg_tile(cfg, ctypes.byref(bm), ctypes.byref(bn)) != 0:
-        raise HipError(f"unknown GEMM config {cfg}")
-    if m % bm.value or n % bn.value or k % 64:
-        raise HipError(f"GEMM config {cfg} needs M%{bm.value}==0, N%{bn.value}==0, K%64==0")
-    rc = L.gsx_gemm_bf16_nt_launch_cfg(stream.handle, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c),
-                                       m, n, k, cfg)
-    if rc != 0:
-        raise HipError(f"gemm cfg {cfg}: hip error {rc}")
+    """Launch one tile configuration of the GEMM; an unknown config or a shape it cannot take raises HipError."""
+    _ck(lib().gsx_gemm_bf16_nt_launch_cfg(stream.handle, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c),
+                                          m, n, k, cfg), f"gemm cfg {cfg}")

@@ -1,22 +1,32 @@
 // bf16 MFMA GEMM family for the pod workload: C[M][N] = A[M][K] * B[N][K]^T (bf16 in/out, fp32 accumulate).
+// C ABI in gsx_kernels.h.
 //
-// One template, several tile shapes (BM x BN with WM x WN waves, BK = 64),
-// selected at launch.  Structure per K-tile (see gsx_kernels.hip for the
-// 128x128 original and the reasoning):
+// Three kernels share one tile map, one LDS swizzle and one epilogue; they differ in the schedule of their K loop:
+// gemm_kernel (several tile shapes, one __syncthreads per K-tile), gemm_phased_kernel (256x256, prefetch in flight
+// across barriers; the dispatched one) and gemm_w4_kernel (256x256, one wave per SIMD; ablation).  Common structure
+// (BM x BN block tile, BK = 64):
 //   * global -> LDS with global_load_lds (16 B/lane), lane-linear LDS image,
 //     XOR swizzle folded into the per-lane *global* source address;
 //   * two LDS buffers: tile k+1 in flight while the MFMAs consume tile k;
-//     one barrier per K-tile;
 //   * v_mfma_f32_16x16x32_bf16, each wave owns a (BM/WM) x (BN/WN) C tile;
 //   * s_setprio around the MFMA burst so the partner wave's loads issue;
 //   * grouped, XCD-aware tile order (GROUP_M tile-rows per group; workgroup
 //     ids remapped bijectively so one XCD's blocks share A/B panels in L2);
 //   * epilogue through LDS: 16-B coalesced row stores.
+// One host launcher and one table of the eleven configurations follow the kernels.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
+#include <cstdio>
+#include <type_traits>
+
+#include "gsx_internal.h"
+#include "gsx_kernels.h"
 
 namespace gsxgemm {
+
+using namespace gsx;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -26,7 +36,16 @@ typedef void __attribute__((address_space(3)))* lptr_t;
 
 constexpr int BK = 64;
 
-__device__ __forceinline__ uint32_t swz(int row, int chunk) {
+// The LDS swizzle, both halves.  A K-tile row is 128 B = 8 chunks of 16 B, and the LDS image of a tile is
+// lane-linear: load slot p (lane p of a round of global_load_lds) lands at byte 16 p, i.e. row p >> 3, chunk
+// position p & 7.  Invariant: chunk c of row r sits at position c ^ ((r >> 1) & 7).  glds_col() is the writer's half
+// (slot p fetches, from whichever global row its LDS row holds, the chunk that belongs at its position), swz() the
+// reader's.  The XOR is its own inverse, so both apply the same term; change one and the other must follow.
+__device__ __forceinline__ int glds_col(int p) {  // in elements, from the first element of the slot's global row
+  const int row = p >> 3, slot = p & 7;
+  return (slot ^ ((row >> 1) & 7)) * 8;
+}
+__device__ __forceinline__ uint32_t swz(int row, int chunk) {  // in bytes, from the tile's LDS base
   return static_cast<uint32_t>(row * (BK * 2) + ((chunk ^ ((row >> 1) & 7)) << 4));
 }
 
@@ -35,6 +54,63 @@ __device__ __forceinline__ uint16_t f2bf(float f) {
   if ((u & 0x7f800000u) == 0x7f800000u) return static_cast<uint16_t>((u >> 16) | ((u & 0xffff) ? 0x40 : 0));
   u += 0x7fffu + ((u >> 16) & 1u);
   return static_cast<uint16_t>(u >> 16);
+}
+
+// XCD-aware bijective remap of the workgroup id (ids are dealt round-robin to the 8 XCDs), then grouped tile order:
+// GROUP_M tile-rows per group, the last group ragged.
+template <int BM, int BN, int GROUP_M>
+__device__ __forceinline__ void tile_of(int orig, int nwg, int M, int N, int& tm, int& tn) {
+  const int xcd = orig & 7;
+  const int q = nwg >> 3, r = nwg & 7;
+  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+  const int ntm = M / BM, ntn = N / BN;
+  const int per_group = GROUP_M * ntn;
+  const int g = wg / per_group;
+  const int first_m = g * GROUP_M;
+  const int gm = (ntm - first_m) < GROUP_M ? (ntm - first_m) : GROUP_M;
+  tm = first_m + (wg % per_group) % gm;
+  tn = (wg % per_group) / gm;
+}
+
+// Epilogue through LDS, in a region private to the wave: the accumulator fragments are scattered as bf16 into a
+// row-major WTM x WTN tile `ct`, which then leaves in 16-B row stores.
+// 16x16 C map: column fr = lane & 15, row 4 fq + reg, fq = lane >> 4
+template <int WTN, int MR, int NR>
+__device__ __forceinline__ void scatter16(uint16_t* ct, const f32x4 (&acc)[MR][NR], int fr, int fq) {
+#pragma unroll
+  for (int m = 0; m < MR; ++m)
+#pragma unroll
+    for (int n = 0; n < NR; ++n)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ct[(m * 16 + fq * 4 + j) * WTN + n * 16 + fr] = f2bf(acc[m][n][j]);
+}
+// 32x32 C map: column r32 = lane & 31, row (reg & 3) + 8 (reg >> 2) + 4 h32, h32 = lane >> 5
+template <int WTN, int MR, int NR>
+__device__ __forceinline__ void scatter32(uint16_t* ct, const f32x16 (&acc)[MR][NR], int r32, int h32) {
+#pragma unroll
+  for (int m = 0; m < MR; ++m)
+#pragma unroll
+    for (int n = 0; n < NR; ++n)
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        ct[(m * 32 + (j & 3) + 8 * (j >> 2) + 4 * h32) * WTN + n * 32 + r32] = f2bf(acc[m][n][j]);
+}
+// The wave tile's origin in C is (row0, col0 + wcol).  The column comes in two parts that are added to the pointer one
+// after the other: gemm_kernel keeps its block and wave columns apart, the 256x256 kernels pass their sum and 0.
+// Summing them first is the same address but another instruction stream for gemm_kernel (0.4 % slower on MI355X).
+template <int WTM, int WTN>
+__device__ __forceinline__ void store_wave_tile(const uint16_t* ct, uint16_t* C, int N, int row0, int col0, int wcol,
+                                                int lane) {
+  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+  __builtin_amdgcn_wave_barrier();
+  constexpr int LPR = WTN / 8;   // lanes per row (16 B each)
+  constexpr int RPI = 64 / LPR;  // rows per store instruction
+#pragma unroll
+  for (int i = 0; i < WTM / RPI; ++i) {
+    const int rr = i * RPI + lane / LPR, cc = (lane % LPR) * 8;
+    const uint4 v = *reinterpret_cast<const uint4*>(ct + rr * WTN + cc);
+    *reinterpret_cast<uint4*>(C + static_cast<size_t>(row0 + rr) * N + col0 + wcol + cc) = v;
+  }
 }
 
 template <int BM, int BN, int WM, int WN, int GROUP_M>
@@ -55,33 +131,15 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const uint16_t* __re
   const int wid = tid >> 6;
   const int wr = wid / WN, wc = wid % WN;
 
-  // XCD-aware bijective remap, then grouped tile order
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int xcd = orig & 7;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  const int ntm = M / BM, ntn = N / BN;
-  const int per_group = GROUP_M * ntn;
-  const int g = wg / per_group;
-  const int first_m = g * GROUP_M;
-  const int gm = (ntm - first_m) < GROUP_M ? (ntm - first_m) : GROUP_M;
-  const int tm = first_m + (wg % per_group) % gm;
-  const int tn = (wg % per_group) / gm;
+  int tm, tn;
+  tile_of<BM, BN, GROUP_M>(blockIdx.x, gridDim.x, M, N, tm, tn);
   const int row0 = tm * BM, col0 = tn * BN;
 
-  int offA[RA], offB[RB];
+  int off[RA > RB ? RA : RB];  // round i loads the same rows and slots of an A tile and of a B tile
 #pragma unroll
-  for (int i = 0; i < RA; ++i) {
+  for (int i = 0; i < (RA > RB ? RA : RB); ++i) {
     const int p = (i * NW + wid) * 64 + lane;
-    const int rr = p >> 3, slot = p & 7;
-    offA[i] = rr * K + ((slot ^ ((rr >> 1) & 7)) * 8);
-  }
-#pragma unroll
-  for (int i = 0; i < RB; ++i) {
-    const int p = (i * NW + wid) * 64 + lane;
-    const int rr = p >> 3, slot = p & 7;
-    offB[i] = rr * K + ((slot ^ ((rr >> 1) & 7)) * 8);
+    off[i] = (p >> 3) * K + glds_col(p);
   }
   const uint16_t* Ab = A + static_cast<size_t>(row0) * K;
   const uint16_t* Bb = B + static_cast<size_t>(col0) * K;
@@ -91,11 +149,11 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const uint16_t* __re
     char* lb = la + TA;
 #pragma unroll
     for (int i = 0; i < RA; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(Ab + offA[i] + kt * BK), (lptr_t)(la + (i * NW + wid) * 1024), 16,
+      __builtin_amdgcn_global_load_lds((gptr_t)(Ab + off[i] + kt * BK), (lptr_t)(la + (i * NW + wid) * 1024), 16,
                                        0, 0);
 #pragma unroll
     for (int i = 0; i < RB; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(Bb + offB[i] + kt * BK), (lptr_t)(lb + (i * NW + wid) * 1024), 16,
+      __builtin_amdgcn_global_load_lds((gptr_t)(Bb + off[i] + kt * BK), (lptr_t)(lb + (i * NW + wid) * 1024), 16,
                                        0, 0);
   };
 
@@ -131,24 +189,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const uint16_t* __re
     }
     __syncthreads();
   }
-  // epilogue through LDS (wave-private region): bf16 tile, then 16-B row stores
   uint16_t* ct = reinterpret_cast<uint16_t*>(lds + wid * (WTM * WTN * 2));
-#pragma unroll
-  for (int m = 0; m < MR; ++m)
-#pragma unroll
-    for (int n = 0; n < NR; ++n)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ct[(m * 16 + fq * 4 + j) * WTN + n * 16 + fr] = f2bf(acc[m][n][j]);
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-  constexpr int LPR = WTN / 8;   // lanes per row (16 B each)
-  constexpr int RPI = 64 / LPR;  // rows per store instruction
-#pragma unroll
-  for (int i = 0; i < WTM / RPI; ++i) {
-    const int rr = i * RPI + lane / LPR, cc = (lane % LPR) * 8;
-    const uint4 v = *reinterpret_cast<const uint4*>(ct + rr * WTN + cc);
-    *reinterpret_cast<uint4*>(C + static_cast<size_t>(row0 + wr * WTM + rr) * N + col0 + wc * WTN + cc) = v;
-  }
+  scatter16<WTN>(ct, acc, fr, fq);
+  store_wave_tile<WTM, WTN>(ct, C, N, row0 + wr * WTM, col0, wc * WTN, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -202,18 +245,8 @@ __global__ __launch_bounds__(512) void gemm_phased_kernel(const uint16_t* __rest
   const int wid = tid >> 6;
   const int wr = wid >> 2, wc = wid & 3;
 
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int xcd = orig & 7;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  const int ntm = M / BM, ntn = N / BN;
-  const int per_group = GROUP_M * ntn;
-  const int g = wg / per_group;
-  const int first_m = g * GROUP_M;
-  const int gm = (ntm - first_m) < GROUP_M ? (ntm - first_m) : GROUP_M;
-  const int tm = first_m + (wg % per_group) % gm;
-  const int tn = (wg % per_group) / gm;
+  int tm, tn;
+  tile_of<BM, BN, GROUP_M>(blockIdx.x, gridDim.x, M, N, tm, tn);
   const uint16_t* Ab = A + static_cast<size_t>(tm * BM) * K;
   const uint16_t* Bb = B + static_cast<size_t>(tn * BN) * K;
 
@@ -222,8 +255,8 @@ __global__ __launch_bounds__(512) void gemm_phased_kernel(const uint16_t* __rest
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int p = (i * 8 + wid) * 64 + lane;
-    const int lr = p >> 3, slot = p & 7;
-    const int sw = (slot ^ ((lr >> 1) & 7)) * 8;
+    const int lr = p >> 3;
+    const int sw = glds_col(p);
     off[0][i] = ((lr >> 6) * 128 + (lr & 63)) * K + sw;
     off[1][i] = ((lr >> 6) * 128 + 64 + (lr & 63)) * K + sw;
     off[2][i] = ((lr >> 5) * 64 + (lr & 31)) * K + sw;
@@ -238,18 +271,15 @@ __global__ __launch_bounds__(512) void gemm_phased_kernel(const uint16_t* __rest
     __builtin_amdgcn_global_load_lds((gptr_t)(src + off[half][1]), (lptr_t)(dst + 8 * 1024), 16, 0, 0);
   };
 
-  f32x4 acc[8][4];
-  f32x16 acc32[4][2];  // M32: [32-row block][32-col block] of the wave's 128x64 tile
+  // the wave's 128x64 tile as [8][4] 16x16 fragments, or (M32) as [32-row block][32-col block]
+  constexpr int AM = M32 ? 4 : 8, AN = M32 ? 2 : 4;
+  std::conditional_t<M32, f32x16, f32x4> acc[AM][AN];
 #pragma unroll
-  for (int m = 0; m < 8; ++m)
+  for (int m = 0; m < AM; ++m)
 #pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < AN; ++n)
 #pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc32[m][n][j] = 0.f;
+      for (int j = 0; j < (M32 ? 16 : 4); ++j) acc[m][n][j] = 0.f;
 
   const int fr = lane & 15, fq = lane >> 4;
   const int r32 = lane & 31, h32 = lane >> 5;  // M32 operand maps: row / column lane & 31, k = 8 (lane >> 5) + j
@@ -293,8 +323,8 @@ __global__ __launch_bounds__(512) void gemm_phased_kernel(const uint16_t* __rest
       for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
         for (int b = 0; b < 2; ++b)
-          acc32[mh * 2 + b][nh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              af[b * 2 + (kk >> 1)][kk & 1], bf[nh][kk >> 1][kk & 1], acc32[mh * 2 + b][nh], 0, 0, 0);
+          acc[mh * 2 + b][nh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              af[b * 2 + (kk >> 1)][kk & 1], bf[nh][kk >> 1][kk & 1], acc[mh * 2 + b][nh], 0, 0, 0);
     } else {
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk)
@@ -355,49 +385,11 @@ __global__ __launch_bounds__(512) void gemm_phased_kernel(const uint16_t* __rest
 
   uint16_t* ct = reinterpret_cast<uint16_t*>(lds + wid * (WTM * WTN * 2));
   if constexpr (M32) {
-    // 32x32 C map: column lane & 31, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-          ct[(m * 32 + (j & 3) + 8 * (j >> 2) + 4 * h32) * WTN + n * 32 + r32] = f2bf(acc32[m][n][j]);
+    scatter32<WTN>(ct, acc, r32, h32);
   } else {
-#pragma unroll
-    for (int m = 0; m < 8; ++m)
-#pragma unroll
-      for (int n = 0; n < 4; ++n)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ct[(m * 16 + fq * 4 + j) * WTN + n * 16 + fr] = f2bf(acc[m][n][j]);
+    scatter16<WTN>(ct, acc, fr, fq);
   }
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-  constexpr int LPR = WTN / 8, RPI = 64 / LPR;
-  const int row0 = tm * BM + wr * WTM, col0 = tn * BN + wc * WTN;
-#pragma unroll
-  for (int i = 0; i < WTM / RPI; ++i) {
-    const int rr = i * RPI + lane / LPR, cc = (lane % LPR) * 8;
-    const uint4 v = *reinterpret_cast<const uint4*>(ct + rr * WTN + cc);
-    *reinterpret_cast<uint4*>(C + static_cast<size_t>(row0 + rr) * N + col0 + cc) = v;
-  }
-}
-
-template <int GM, bool M32 = false>
-hipError_t launch_phased(hipStream_t s, const void* A, const void* B, void* C, int M, int N, int K) {
-  constexpr int lds = 8 * PH_HALF;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_phased_kernel<GM, M32>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
-  if (M % 256 || N % 256 || K % BK) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((gemm_phased_kernel<GM, M32>), dim3((M / 256) * (N / 256)), dim3(512), lds, s,
-                     static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), static_cast<uint16_t*>(C), M,
-                     N, K);
-  return hipGetLastError();
+  store_wave_tile<WTM, WTN>(ct, C, N, tm * BM + wr * WTM, tn * BN + wc * WTN, 0, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -441,18 +433,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int wid = tid >> 6;
   const int wr = wid >> 1, wc = wid & 1;
 
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int xcd = orig & 7;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  const int ntm = M / BM, ntn = N / BN;
-  const int per_group = GROUP_M * ntn;
-  const int g = wg / per_group;
-  const int first_m = g * GROUP_M;
-  const int gm = (ntm - first_m) < GROUP_M ? (ntm - first_m) : GROUP_M;
-  const int tm = first_m + (wg % per_group) % gm;
-  const int tn = (wg % per_group) / gm;
+  int tm, tn;
+  tile_of<BM, BN, GROUP_M>(blockIdx.x, gridDim.x, M, N, tm, tn);
   const uint16_t* Ab = A + static_cast<size_t>(tm * BM) * K;
   const uint16_t* Bb = B + static_cast<size_t>(tn * BN) * K;
 
@@ -460,8 +442,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int p = (i * 4 + wid) * 64 + lane;
-    const int row = p >> 3, slot = p & 7;
-    off[i] = row * K + (slot ^ ((row >> 1) & 7)) * 8;
+    off[i] = (p >> 3) * K + glds_col(p);
   }
   const int nk = K / BK;
   auto stage = [&](int tile) {
@@ -541,87 +522,133 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
   ph_barrier();
 
-  // epilogue: wave-private 128x128 bf16 staging (32 KiB per wave), 16-B row stores
+  // wave-private 128x128 bf16 staging (32 KiB per wave)
   uint16_t* ct = reinterpret_cast<uint16_t*>(lds + wid * (WT * WT * 2));
-#pragma unroll
-  for (int m = 0; m < 8; ++m)
-#pragma unroll
-    for (int n = 0; n < 8; ++n)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ct[(m * 16 + fq * 4 + j) * WT + n * 16 + fr] = f2bf(acc[m][n][j]);
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-  constexpr int LPR = WT / 8, RPI = 64 / LPR;
-  const int row0 = tm * BM + wr * WT, col0 = tn * BN + wc * WT;
-#pragma unroll
-  for (int i = 0; i < WT / RPI; ++i) {
-    const int rr = i * RPI + lane / LPR, cc = (lane % LPR) * 8;
-    const uint4 v = *reinterpret_cast<const uint4*>(ct + rr * WT + cc);
-    *reinterpret_cast<uint4*>(C + static_cast<size_t>(row0 + rr) * N + col0 + cc) = v;
-  }
+  scatter16<WT>(ct, acc, fr, fq);
+  store_wave_tile<WT, WT>(ct, C, N, tm * BM + wr * WT, tn * BN + wc * WT, 0, lane);
 }
 
-template <int GM, bool ASM>
-hipError_t launch_w4(hipStream_t s, const void* A, const void* B, void* C, int M, int N, int K) {
-  constexpr int lds = 4 * 256 * BK * 2;  // 128 KiB
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w4_kernel<GM, ASM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr = true;
+// ---------------------------------------------------------------------------
+// Host side: one launcher, one table.
+// ---------------------------------------------------------------------------
+
+// Validates once for every kernel, then launches; a failure's text begins with `who`, the C entry point.
+template <auto KERNEL, int THREADS, int LDS, int BM, int BN>
+int launch(const char* who, hipStream_t s, const void* A, const void* B, void* C, int M, int N, int K) {
+  char msg[160];
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK) {
+    std::snprintf(msg, sizeof(msg), "%s: need M%%%d==0, N%%%d==0, K%%%d==0", who, BM, BN, BK);
+    return fail_arg(msg);
   }
-  if (M % 256 || N % 256 || K % BK) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((gemm_w4_kernel<GM, ASM>), dim3((M / 256) * (N / 256)), dim3(256), lds, s,
-                     static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), static_cast<uint16_t*>(C), M,
-                     N, K);
-  return hipGetLastError();
+  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) % 16) {
+    std::snprintf(msg, sizeof(msg), "%s: operands must be 16-B aligned", who);
+    return fail_arg(msg);
+  }
+  // More dynamic LDS than the default limit has to be asked for.  The flag is per device because
+  // hipFuncSetAttribute is documented per function and device, not because a failure without it was observed
+  // (that has not been measured).  Two threads that race here both set the same value.
+  static std::atomic<bool> attr[kMaxDevices];
+  int dev = 0;
+  if (int rc = current_device(who, &dev)) return rc;
+  if (!attr[dev].load(std::memory_order_acquire)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    if (e != hipSuccess) return fail(e, who);
+    attr[dev].store(true, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(KERNEL, dim3((M / BM) * (N / BN)), dim3(THREADS), LDS, s, static_cast<const uint16_t*>(A),
+                     static_cast<const uint16_t*>(B), static_cast<uint16_t*>(C), M, N, K);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(e, who);
 }
 
+struct Cfg {
+  const char* name;  // profiles/ key on the index and on this string
+  int bm, bn;
+  int (*launch)(const char* who, hipStream_t s, const void* A, const void* B, void* C, int M, int N, int K);
+};
 template <int BM, int BN, int WM, int WN, int GM>
-hipError_t launch(hipStream_t s, const void* A, const void* B, void* C, int M, int N, int K) {
-  constexpr int lds = 2 * (BM + BN) * BK * 2;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<BM, BN, WM, WN, GM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
-  const int tiles = (M / BM) * (N / BN);
-  hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, GM>), dim3(tiles), dim3(WM * WN * 64), lds, s,
-                     static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), static_cast<uint16_t*>(C), M,
-                     N, K);
-  return hipGetLastError();
+constexpr Cfg plain(const char* name) {
+  return {name, BM, BN, &launch<&gemm_kernel<BM, BN, WM, WN, GM>, WM * WN * 64, 2 * (BM + BN) * BK * 2, BM, BN>};
 }
+template <int GM, bool M32>
+constexpr Cfg phased(const char* name) {
+  return {name, 256, 256, &launch<&gemm_phased_kernel<GM, M32>, 512, 8 * PH_HALF, 256, 256>};
+}
+template <int GM, bool ASM>
+constexpr Cfg w4(const char* name) {
+  return {name, 256, 256, &launch<&gemm_w4_kernel<GM, ASM>, 256, 4 * 256 * BK * 2, 256, 256>};
+}
+
+constexpr Cfg kCfgs[] = {
+    plain<128, 128, 2, 2, 8>("128x128/4w"),
+    plain<256, 128, 4, 2, 4>("256x128/8w"),
+    plain<128, 256, 2, 4, 8>("128x256/8w"),
+    plain<256, 256, 2, 4, 4>("256x256/8w"),
+    plain<128, 128, 2, 2, 1>("128x128/4w-nogroup"),
+    phased<4, false>("256x256/8w-phased-g4"),
+    phased<8, false>("256x256/8w-phased-g8"),
+    w4<4, false>("256x256/4w-agpr-g4"),
+    w4<8, false>("256x256/4w-agpr-g8"),
+    w4<4, true>("256x256/4w-asm-agpr-g4"),
+    phased<4, true>("256x256/8w-phased-g4-mfma32"),
+};
+constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
+// the two rows gsx_gemm_bf16_nt dispatches to
+constexpr int kCfgGrouped128 = 0, kCfgPhased = 5;
+
+static const Cfg* cfg_row(int cfg) { return cfg >= 0 && cfg < kNumCfgs ? &kCfgs[cfg] : nullptr; }
 
 }  // namespace gsxgemm
 
-// Tile configurations (index -> BM x BN, waves).  Exposed for benchmarking.
-extern "C" int gsx_gemm_cfg_tile(int cfg, int* bm, int* bn) {
-  static const int t[][2] = {{128, 128}, {256, 128}, {128, 256}, {256, 256}, {128, 128},
-                             {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}};
-  if (cfg < 0 || cfg > 10) return -1;
-  *bm = t[cfg][0];
-  *bn = t[cfg][1];
+using namespace gsxgemm;
+
+extern "C" {
+
+const char* gsx_gemm_cfg_name(int cfg) { return cfg_row(cfg) ? cfg_row(cfg)->name : nullptr; }
+
+int gsx_gemm_cfg_tile(int cfg, int* bm, int* bn) {
+  const Cfg* c = cfg_row(cfg);
+  if (!c) return -1;
+  *bm = c->bm;
+  *bn = c->bn;
   return 0;
 }
 
-extern "C" int gsx_gemm_bf16_nt_launch_cfg(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
-                                           int cfg) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (cfg) {
-    case 0: return static_cast<int>(gsxgemm::launch<128, 128, 2, 2, 8>(s, A, B, C, M, N, K));
-    case 1: return static_cast<int>(gsxgemm::launch<256, 128, 4, 2, 4>(s, A, B, C, M, N, K));
-    case 2: return static_cast<int>(gsxgemm::launch<128, 256, 2, 4, 8>(s, A, B, C, M, N, K));
-    case 3: return static_cast<int>(gsxgemm::launch<256, 256, 2, 4, 4>(s, A, B, C, M, N, K));
-    case 4: return static_cast<int>(gsxgemm::launch<128, 128, 2, 2, 1>(s, A, B, C, M, N, K));
-    case 5: return static_cast<int>(gsxgemm::launch_phased<4>(s, A, B, C, M, N, K));
-    case 6: return static_cast<int>(gsxgemm::launch_phased<8>(s, A, B, C, M, N, K));
-    case 7: return static_cast<int>(gsxgemm::launch_w4<4, false>(s, A, B, C, M, N, K));
-    case 8: return static_cast<int>(gsxgemm::launch_w4<8, false>(s, A, B, C, M, N, K));
-    case 9: return static_cast<int>(gsxgemm::launch_w4<4, true>(s, A, B, C, M, N, K));
-    case 10: return static_cast<int>(gsxgemm::launch_phased<4, true>(s, A, B, C, M, N, K));
-    default: return static_cast<int>(hipErrorInvalidValue);
-  }
+int gsx_gemm_bf16_nt_launch_cfg(void* stream, const void* A, const void* B, void* C, int M, int N, int K, int cfg) {
+  const Cfg* c = cfg_row(cfg);
+  if (!c) return fail_arg("gsx_gemm_bf16_nt_launch_cfg: unknown config");
+  return c->launch("gsx_gemm_bf16_nt_launch_cfg", S(stream), A, B, C, M, N, K);
 }
+
+int gsx_gemm_bf16_nt(void* stream, const void* A, const void* B, void* C, int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % 128 || N % 128 || K % 64)
+    return fail_arg("gsx_gemm_bf16_nt: need M%128==0, N%128==0, K%64==0");
+  // phased 256x256 / 8 waves (prefetch in flight across barriers): 1.39-1.46 PFLOP/s on MI355X at
+  // 4k-16k (the __syncthreads 256x256 tile: 1.12-1.21); 128x128 grouped otherwise (profiles/r01_kernels.json)
+  const Cfg& c = kCfgs[(M % 256 == 0 && N % 256 == 0) ? kCfgPhased : kCfgGrouped128];
+  return c.launch("gsx_gemm_bf16_nt", S(stream), A, B, C, M, N, K);
+}
+
+int gsx_event_time_gemm(void* stream, const void* A, const void* B, void* C, int M, int N, int K, int iters,
+                        float* ms) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  auto timed = [&]() -> int {
+    GSX_CHECK(hipEventCreate(&e0));
+    GSX_CHECK(hipEventCreate(&e1));
+    GSX_CHECK(hipEventRecord(e0, S(stream)));
+    for (int i = 0; i < iters; ++i) {
+      if (int rc = gsx_gemm_bf16_nt(stream, A, B, C, M, N, K)) return rc;
+    }
+    GSX_CHECK(hipEventRecord(e1, S(stream)));
+    GSX_CHECK(hipEventSynchronize(e1));
+    GSX_CHECK(hipEventElapsedTime(ms, e0, e1));
+    return 0;
+  };
+  const int rc = timed();
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return rc;
+}
+
+}  // extern "C"

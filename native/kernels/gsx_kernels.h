@@ -85,12 +85,20 @@ int gsx_hbm_admit_n(void* stream, const gsx_slice* slices, int n, int n_stamp, i
 // Fill [base, base+bytes) with a 32-bit pattern (bytes % 16 == 0).
 int gsx_hbm_fill(void* stream, void* base, uint64_t bytes, uint32_t pattern);
 
-// C[M][N] (bf16) = A[M][K] (bf16, row-major) * B[N][K]^T (bf16, row-major).
-// Requires M % 128 == 0, N % 128 == 0, K % 64 == 0.  Dispatches to the best
-// tile of the templated family in gemm.hip (256x256 when M, N % 256 == 0).
+// bf16 GEMM (gemm.hip): C[M][N] (bf16) = A[M][K] (bf16, row-major) * B[N][K]^T (bf16, row-major), fp32 accumulate.
+// A, B and C are 16-B aligned.  Launches on `stream` and returns without synchronising.
+// gsx_gemm_bf16_nt requires M % 128 == 0, N % 128 == 0, K % 64 == 0 and dispatches to one of the configurations
+// below: the phased 256x256 kernel when M and N are multiples of 256, the grouped 128x128 tile otherwise.
 int gsx_gemm_bf16_nt(void* stream, const void* A, const void* B, void* C, int M, int N, int K);
+// The configurations, one table in gemm.hip: index 0 .. 10, each a kernel with a BM x BN block tile and a name
+// ("256x256/8w-phased-g4"); most are ablations kept for benchmarking.  _cfg_name returns NULL and _cfg_tile
+// nonzero outside the table.  _launch_cfg launches configuration `cfg`, which requires M % BM == 0, N % BN == 0,
+// K % 64 == 0.
+const char* gsx_gemm_cfg_name(int cfg);
+int gsx_gemm_cfg_tile(int cfg, int* bm, int* bn);
+int gsx_gemm_bf16_nt_launch_cfg(void* stream, const void* A, const void* B, void* C, int M, int N, int K, int cfg);
 
-// elapsed milliseconds of running `fn` on stream via hip events (for benches)
+// elapsed milliseconds of `iters` back-to-back gsx_gemm_bf16_nt on `stream`, by hip events (for benches)
 int gsx_event_time_gemm(void* stream, const void* A, const void* B, void* C, int M, int N, int K, int iters,
                         float* ms);
 

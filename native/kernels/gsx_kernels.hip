@@ -9,9 +9,6 @@
 #include "gsx_internal.h"
 #include "gsx_kernels.h"
 
-extern "C" int gsx_gemm_bf16_nt_launch_cfg(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
-                                           int cfg);
-
 namespace {
 thread_local std::string g_err;  // the library's one error text: every translation unit sets it through gsx::set_error
 }  // namespace
@@ -81,10 +78,6 @@ int grid_for(uint64_t n, int per_block, int max_blocks) {
   if (g > static_cast<uint64_t>(max_blocks)) g = max_blocks;
   return g < 1 ? 1 : static_cast<int>(g);
 }
-
-// ------------------------------------------------------------------ bf16 MFMA GEMM
-// The kernels live in gemm.hip (templated tile family); gsx_gemm_bf16_nt
-// picks the measured-best tile for the shape (profiles/r01_kernels.json).
 
 }  // namespace
 
@@ -199,37 +192,6 @@ int gsx_hbm_fill(void* stream, void* base, uint64_t bytes, uint32_t pattern) {
   hipLaunchKernelGGL(fill_kernel, dim3(grid_for(n16, 256 * 4, 256 * 16)), dim3(256), 0, S(stream),
                      static_cast<uint4*>(base), n16, pattern);
   GSX_CHECK(hipGetLastError());
-  return 0;
-}
-
-int gsx_gemm_bf16_nt(void* stream, const void* A, const void* B, void* C, int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0 || M % 128 || N % 128 || K % 64)
-    return fail_arg("gsx_gemm_bf16_nt: need M%128==0, N%128==0, K%64==0");
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) % 16)
-    return fail_arg("gsx_gemm_bf16_nt: operands must be 16-B aligned");
-  // phased 256x256 / 8 waves (prefetch in flight across barriers): 1.39-1.46 PFLOP/s on MI355X at
-  // 4k-16k (the __syncthreads 256x256 tile: 1.12-1.21); 128x128 grouped otherwise
-  const int cfg = (M % 256 == 0 && N % 256 == 0) ? 5 : 0;
-  int rc = gsx_gemm_bf16_nt_launch_cfg(stream, A, B, C, M, N, K, cfg);
-  if (rc != 0) return fail(static_cast<hipError_t>(rc), "gemm launch");
-  return 0;
-}
-
-int gsx_event_time_gemm(void* stream, const void* A, const void* B, void* C, int M, int N, int K, int iters,
-                        float* ms) {
-  hipEvent_t e0, e1;
-  GSX_CHECK(hipEventCreate(&e0));
-  GSX_CHECK(hipEventCreate(&e1));
-  GSX_CHECK(hipEventRecord(e0, S(stream)));
-  for (int i = 0; i < iters; ++i) {
-    int rc = gsx_gemm_bf16_nt(stream, A, B, C, M, N, K);
-    if (rc) return rc;
-  }
-  GSX_CHECK(hipEventRecord(e1, S(stream)));
-  GSX_CHECK(hipEventSynchronize(e1));
-  GSX_CHECK(hipEventElapsedTime(ms, e0, e1));
-  GSX_CHECK(hipEventDestroy(e0));
-  GSX_CHECK(hipEventDestroy(e1));
   return 0;
 }
 

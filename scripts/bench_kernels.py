@@ -38,7 +38,7 @@ def gemm(size_list, iters=20):
         row = {"m": m, "n": n, "k": k, "gsx_tflops": round(ours, 1), "torch_tflops": round(ref, 1),
                "gsx_ms": round(ms, 4), "max_abs_err": round(err, 4)}
         ts = torch.cuda.ExternalStream(s.ptr)
-        for cfg, name in hip.GEMM_CFGS.items():
+        for cfg, name in hip.gemm_cfgs().items():
             try:
                 hip.gemm_bf16_nt_cfg(s, a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k, cfg)
             except hip.HipError:

@@ -285,6 +285,93 @@ def test_gemm_phased_is_deterministic(hip):
     s.destroy()
 
 
+GEMM_CFG_NAMES = ["128x128/4w", "256x128/8w", "128x256/8w", "256x256/8w", "128x128/4w-nogroup",
+                  "256x256/8w-phased-g4", "256x256/8w-phased-g8", "256x256/4w-agpr-g4", "256x256/4w-agpr-g8",
+                  "256x256/4w-asm-agpr-g4", "256x256/8w-phased-g4-mfma32"]
+
+
+@pytest.fixture(scope="module")
+def gemm_exact_case():
+    """Host-built operands whose product has no rounding before the final bf16 conversion: every input is k/16 with
+    |k| <= 15 (a bf16), every product a multiple of 2^-8 and every partial sum below 71, so fp32 accumulation is
+    exact in any order and the kernel has to equal the fp64 product rounded once."""
+    m, n, k = 768, 1280, 320
+    i, j = torch.arange(m).unsqueeze(1), torch.arange(k).unsqueeze(0)
+    a = (((7 * i + 13 * j) % 31 - 15).double() / 16)
+    i = torch.arange(n).unsqueeze(1)
+    b = (((11 * i + 5 * j) % 29 - 14).double() / 16)
+    assert torch.equal(a.bfloat16().double(), a) and torch.equal(b.bfloat16().double(), b)
+    want = (a @ b.t()).float().bfloat16()
+    return a.bfloat16(), b.bfloat16(), want
+
+
+@pytest.mark.parametrize("cfg", [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10])
+def test_gemm_tile_configs_exact_on_ragged_grid(hip, gemm_exact_case, cfg):
+    """768 x 1280 x 320: a ragged last tile-row group for every GROUP_M, grids of 15 / 30 / 60 blocks (no multiple
+    of the 8 XCDs), 5 K-tiles; row / column periods 31 and 29 put different data under every tile."""
+    a_h, b_h, want = gemm_exact_case
+    (m, k), n = a_h.shape, b_h.shape[0]
+    a, b = a_h.cuda(), b_h.cuda()
+    c = torch.full((m, n), float("nan"), device="cuda", dtype=torch.bfloat16)
+    s = hip.Stream(0)
+    torch.cuda.synchronize()
+    hip.gemm_bf16_nt_cfg(s, a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k, cfg)
+    s.sync()
+    torch.testing.assert_close(c.cpu(), want, atol=0, rtol=0)
+    s.destroy()
+
+
+def test_gemm_cfg_table(hip):
+    import ctypes
+
+    L = hip.lib()
+    assert [L.gsx_gemm_cfg_name(c) for c in range(11)] == [x.encode() for x in GEMM_CFG_NAMES]
+    assert L.gsx_gemm_cfg_name(-1) is None and L.gsx_gemm_cfg_name(11) is None
+    for c, name in enumerate(GEMM_CFG_NAMES):
+        bm, bn = ctypes.c_int(0), ctypes.c_int(0)
+        assert L.gsx_gemm_cfg_tile(c, ctypes.byref(bm), ctypes.byref(bn)) == 0
+        assert f"{bm.value}x{bn.value}" == name.split("/")[0]
+    assert L.gsx_gemm_cfg_tile(11, ctypes.byref(bm), ctypes.byref(bn)) != 0
+    assert hip.gemm_cfgs() == dict(enumerate(GEMM_CFG_NAMES))
+
+
+def test_gemm_launch_cfg_rejects_in_c(hip):
+    """The exported launcher itself refuses what a configuration cannot take.  Every call gets real buffers for
+    512 x 512 x 128 (A and B with a spare block on either side), so a check that went missing would show as a
+    wrong answer and not as an access outside the buffers."""
+    import ctypes
+
+    m, n, k = 512, 512, 128
+    torch.manual_seed(3)
+    ab = torch.randint(-3, 4, (2, 3, m, k), device="cuda").to(torch.bfloat16)
+    a, b = ab[0, 1], ab[1, 1]
+    c = torch.full((m, n), float("nan"), device="cuda", dtype=torch.bfloat16)
+    pa, pb, pc = a.data_ptr(), b.data_ptr(), c.data_ptr()
+    s = hip.Stream(0)
+    torch.cuda.synchronize()
+    cases = [(0, pa, pb, pc, 200, n, k), (5, pa, pb, pc, m, 384, k), (11, pa, pb, pc, m, n, k)]
+    for cfg in range(11):
+        cases += [(cfg, pa, pb, pc, m, n, 0), (cfg, pa, pb, pc, m, n, 96)]
+        # misaligned operands, at a shape that stays inside the buffers
+        cases += [(cfg, pa + 8, pb, pc, 256, 256, 64), (cfg, pa, pb + 8, pc, 256, 256, 64),
+                  (cfg, pa, pb, pc + 8, 256, 256, 64)]
+    L = hip.lib()
+    for cfg, xa, xb, xc, xm, xn, xk in cases:
+        rc = L.gsx_gemm_bf16_nt_launch_cfg(s.handle, ctypes.c_void_p(xa), ctypes.c_void_p(xb), ctypes.c_void_p(xc),
+                                           xm, xn, xk, cfg)
+        assert rc != 0, (cfg, xm, xn, xk)
+        assert L.gsx_last_error().decode().startswith("gsx_gemm_bf16_nt_launch_cfg:"), L.gsx_last_error()
+        with pytest.raises(hip.HipError):
+            hip.gemm_bf16_nt_cfg(s, xa, xb, xc, xm, xn, xk, cfg)
+    s.sync()
+    assert bool(torch.isnan(c.float()).all())  # no rejected call launched anything
+    hip.gemm_bf16_nt_cfg(s, pa, pb, pc, m, n, k, 5)
+    s.sync()
+    want = (a.double() @ b.double().t()).float().bfloat16()  # small integers: exact up to the one final rounding
+    torch.testing.assert_close(c, want, atol=0, rtol=0)
+    s.destroy()
+
+
 def test_hbm_verify_counts_are_per_call_under_concurrency(hip):
     """two host threads verifying on one device must each get their own bad-stamp count (the
     per-device counter's reset -> launch -> readback is serialised).  ctypes drops the GIL, so the calls
