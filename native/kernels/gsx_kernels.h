@@ -10,7 +10,7 @@
 //                          verified later: proves co-resident pods placed by
 //                          the binpack allocator really fit and never overlap
 //                          (hbm_stamp.hip);
-//  * HBM scrub           — full-bandwidth 16 B/lane fill used to wipe a slice
+//  * HBM scrub           — the memory test's SOLID write pass, used to wipe a slice
 //                          when a pod leaves (and as the HBM roofline probe);
 //  * HBM memory test     — pattern write / check / moving-inversions passes at HBM
 //                          bandwidth: the device plugin's pre-flight (memtest.hip);
@@ -82,7 +82,7 @@ typedef struct {
 int gsx_hbm_admit_n(void* stream, const gsx_slice* slices, int n, int n_stamp, int verify, uint64_t stride,
                     uint64_t* bad);
 
-// Fill [base, base+bytes) with a 32-bit pattern (bytes % 16 == 0).
+// Fill [base, base+bytes) with a 32-bit pattern (bytes % 16 == 0): gsx_memtest_write's SOLID pass (memtest.hip).
 int gsx_hbm_fill(void* stream, void* base, uint64_t bytes, uint32_t pattern);
 
 // bf16 GEMM (gemm.hip): C[M][N] (bf16) = A[M][K] (bf16, row-major) * B[N][K]^T (bf16, row-major), fp32 accumulate.

@@ -57,28 +57,6 @@ __global__ __launch_bounds__(64) void cuprobe_kernel(uint32_t* out, int spin) {
   }
 }
 
-// ------------------------------------------------------------------ HBM fill
-
-__global__ __launch_bounds__(256) void fill_kernel(uint4* p, uint64_t n16, uint32_t pat) {
-  uint4 v = make_uint4(pat, pat, pat, pat);
-  uint64_t i = blockIdx.x * 256ull + threadIdx.x;
-  const uint64_t step = gridDim.x * 256ull;
-  // 4 independent 16-B stores in flight per lane
-  for (; i + 3 * step < n16; i += 4 * step) {
-    p[i] = v;
-    p[i + step] = v;
-    p[i + 2 * step] = v;
-    p[i + 3 * step] = v;
-  }
-  for (; i < n16; i += step) p[i] = v;
-}
-
-int grid_for(uint64_t n, int per_block, int max_blocks) {
-  uint64_t g = (n + per_block - 1) / per_block;
-  if (g > static_cast<uint64_t>(max_blocks)) g = max_blocks;
-  return g < 1 ? 1 : static_cast<int>(g);
-}
-
 }  // namespace
 
 extern "C" {
@@ -182,16 +160,6 @@ int gsx_cuprobe(void* stream, int blocks, int spin, uint32_t* out_host) {
   GSX_CHECK(hipMemcpyAsync(out_host, d, sizeof(uint32_t) * 2 * blocks, hipMemcpyDeviceToHost, S(stream)));
   GSX_CHECK(hipFreeAsync(d, S(stream)));
   GSX_CHECK(hipStreamSynchronize(S(stream)));
-  return 0;
-}
-
-int gsx_hbm_fill(void* stream, void* base, uint64_t bytes, uint32_t pattern) {
-  if (!base || bytes % 16 || reinterpret_cast<uintptr_t>(base) % 16) return fail_arg("gsx_hbm_fill: need 16-B multiple");
-  uint64_t n16 = bytes / 16;
-  if (!n16) return 0;
-  hipLaunchKernelGGL(fill_kernel, dim3(grid_for(n16, 256 * 4, 256 * 16)), dim3(256), 0, S(stream),
-                     static_cast<uint4*>(base), n16, pattern);
-  GSX_CHECK(hipGetLastError());
   return 0;
 }
 

@@ -1,12 +1,11 @@
 // HBM stamps for MI355X (gfx950): a pod's slice is stamped with {tag, offset} every `stride` bytes when it is
 // admitted, and every resident slice is verified by counting its bad stamps.  C ABI in gsx_kernels.h.
 //
-// Two device helpers (stamp an extent, count an extent's bad stamps), three kernels over a table of extents
+// Two device helpers (stamp an extent, count an extent's bad stamps), two kernels over a table of extents
 // (grid.y = extent), one host launcher; a single range is a table of one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <mutex>
 
 #include "gsx_internal.h"
@@ -74,20 +73,9 @@ __global__ __launch_bounds__(256) void verify_slices_kernel(SliceTable t, uint64
   count_bad_stamps(t.s[blockIdx.y], stride, bad);
 }
 
-// One launch per admission: grid.y rows [0, n_stamp) stamp the new extents, the other rows verify the resident
-// ones.  Only used when the host has checked that no two extents of the table overlap, so the two kinds of block
-// touch disjoint memory and need no ordering between them; with an overlap the two-launch path runs instead, and the
-// verify launch counts the overwritten stamps.  The stamp rows do not read back what they wrote (the two-launch
-// path verifies fresh stamps in its second launch): in this mode a fresh slice is first verified by the next
-// admission on the device, so the two modes' bad counts differ by the current admission's own new stamps.
-__global__ __launch_bounds__(256) void admit_slices_kernel(SliceTable t, int n_stamp, uint64_t stride,
-                                                           unsigned long long* bad) {
-  if (static_cast<int>(blockIdx.y) < n_stamp) {  // uniform: a whole block stamps or verifies
-    stamp_extent(t.s[blockIdx.y], stride);
-  } else {
-    count_bad_stamps(t.s[blockIdx.y], stride, bad);
-  }
-}
+// Stamp and verify stay two launches.  One fused launch (stamp rows and verify rows in one grid) was measured: it
+// was not faster in the wall-clock of an admission, and it cannot verify the stamps it has just written, because the
+// rows of one launch are unordered (profiles/r02_fused_admit/).
 
 // One bad-stamp counter per device, in pinned host memory the kernels add to directly: no memset, no copy, and one
 // stream sync per count.  Its reset -> kernel launch -> readback sequence is held under the device's mutex, so
@@ -115,11 +103,9 @@ constexpr int kTableBlocks = 1024, kRangeBlocks = 8192;
 // The one launcher: stamps slices[0, n_stamp), then counts the bad stamps of slices[0, n_verify) into *bad.
 // Extents go out in tables of kMaxSlices, each launch's grid.x sized from the largest extent of its table.
 // n_verify == 0 launches the stamps only, and synchronises only where `sync` asks; otherwise reset -> launches ->
-// one sync -> read of the device's counter run under the device's mutex.  `one_launch` (the caller has checked
-// that one table holds all extents and that they are pairwise disjoint) puts the stamp rows and the verify rows
-// into one launch of admit_slices_kernel.
+// one sync -> read of the device's counter run under the device's mutex.
 int launch(const char* who, hipStream_t st, const gsx_slice* slices, int n_stamp, int n_verify, uint64_t stride,
-           int max_blocks, bool one_launch, bool sync, uint64_t* bad) {
+           int max_blocks, bool sync, uint64_t* bad) {
   auto tables = [&](int count, auto&& kernel) {
     for (int from = 0; from < count; from += kMaxSlices) {
       SliceTable t;
@@ -135,12 +121,10 @@ int launch(const char* who, hipStream_t st, const gsx_slice* slices, int n_stamp
     }
     return 0;
   };
-  if (!one_launch) {
-    if (int rc = tables(n_stamp, [&](dim3 grid, const SliceTable& t) {
-          hipLaunchKernelGGL(stamp_slices_kernel, grid, dim3(256), 0, st, t, stride);
-        }))
-      return rc;
-  }
+  if (int rc = tables(n_stamp, [&](dim3 grid, const SliceTable& t) {
+        hipLaunchKernelGGL(stamp_slices_kernel, grid, dim3(256), 0, st, t, stride);
+      }))
+    return rc;
   if (!n_verify) {
     if (sync) GSX_CHECK(hipStreamSynchronize(st));
     return 0;
@@ -151,27 +135,12 @@ int launch(const char* who, hipStream_t st, const gsx_slice* slices, int n_stamp
   std::lock_guard<std::mutex> dl(g_dev_mu[dev]);
   __atomic_store_n(hc, 0ull, __ATOMIC_SEQ_CST);
   if (int rc = tables(n_verify, [&](dim3 grid, const SliceTable& t) {
-        if (one_launch) {
-          hipLaunchKernelGGL(admit_slices_kernel, grid, dim3(256), 0, st, t, n_stamp, stride, hc);
-        } else {
-          hipLaunchKernelGGL(verify_slices_kernel, grid, dim3(256), 0, st, t, stride, hc);
-        }
+        hipLaunchKernelGGL(verify_slices_kernel, grid, dim3(256), 0, st, t, stride, hc);
       }))
     return rc;
   GSX_CHECK(hipStreamSynchronize(st));
   *bad = __atomic_load_n(hc, __ATOMIC_SEQ_CST);
   return 0;
-}
-
-bool pairwise_disjoint(const gsx_slice* slices, int n) {
-  for (int i = 0; i < n; ++i) {
-    for (int j = i + 1; j < n; ++j) {
-      const uint64_t a0 = slices[i].addr, a1 = a0 + slices[i].bytes;
-      const uint64_t b0 = slices[j].addr, b1 = b0 + slices[j].bytes;
-      if (a0 < b1 && b0 < a1) return false;
-    }
-  }
-  return true;
 }
 
 }  // namespace
@@ -183,7 +152,7 @@ int gsx_hbm_stamp(void* stream, void* base, uint64_t bytes, uint64_t stride, uin
   if (reinterpret_cast<uintptr_t>(base) % 16) return fail_arg("gsx_hbm_stamp: base not 16-B aligned");
   if (bytes < stride) return 0;
   const gsx_slice sl = {reinterpret_cast<uintptr_t>(base), bytes, tag};
-  return launch("gsx_hbm_stamp", S(stream), &sl, 1, 0, stride, kRangeBlocks, false, false, nullptr);
+  return launch("gsx_hbm_stamp", S(stream), &sl, 1, 0, stride, kRangeBlocks, false, nullptr);
 }
 
 int gsx_hbm_verify(void* stream, const void* base, uint64_t bytes, uint64_t stride, uint64_t tag, uint64_t* bad) {
@@ -192,7 +161,7 @@ int gsx_hbm_verify(void* stream, const void* base, uint64_t bytes, uint64_t stri
   *bad = 0;
   if (bytes < stride) return 0;
   const gsx_slice sl = {reinterpret_cast<uintptr_t>(base), bytes, tag};
-  return launch("gsx_hbm_verify", S(stream), &sl, 0, 1, stride, kRangeBlocks, false, true, bad);
+  return launch("gsx_hbm_verify", S(stream), &sl, 0, 1, stride, kRangeBlocks, true, bad);
 }
 
 int gsx_hbm_admit_n(void* stream, const gsx_slice* slices, int n, int n_stamp, int verify, uint64_t stride,
@@ -203,20 +172,7 @@ int gsx_hbm_admit_n(void* stream, const gsx_slice* slices, int n, int n_stamp, i
   for (int i = 0; i < n; ++i) {
     if (!slices[i].addr || slices[i].addr % 16) return fail_arg("gsx_hbm_admit_n: slice base not 16-B aligned");
   }
-  // one table, extents pairwise disjoint: stamp and verify can share one launch
-  // (every pair: two new extents that overlap each other must be caught by the verify launch as well)
-  // opt-in (GSX_ADMIT_ONE_LAUNCH=1): it cuts GPU time per admission (6.5 vs 10.2 us) but not the wall-clock of an
-  // admission, and its kernel-time tail is longer; interleaved A/Bs of the driver's bench showed no gain
-  // (profiles/r02_fused_admit/), so two launches stay the default.  Its contract is weaker: the fresh stamps are
-  // written, not read back (the rows of one launch are unordered), so a bad count covers the resident slices only,
-  // where the default path also verifies every new extent it just stamped
-  static const bool opted_in = [] {
-    const char* e = std::getenv("GSX_ADMIT_ONE_LAUNCH");
-    return e && e[0] == '1';
-  }();
-  const bool one_launch = opted_in && verify && n > 0 && n <= kMaxSlices && pairwise_disjoint(slices, n);
-  return launch("gsx_hbm_admit_n", S(stream), slices, n_stamp, verify ? n : 0, stride, kTableBlocks, one_launch, true,
-                bad);
+  return launch("gsx_hbm_admit_n", S(stream), slices, n_stamp, verify ? n : 0, stride, kTableBlocks, true, bad);
 }
 
 }  // extern "C"

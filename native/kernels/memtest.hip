@@ -1,5 +1,6 @@
 // HBM pre-flight memory test for MI355X (gfx950): pattern write, check and moving-inversions passes at HBM
-// bandwidth.  C ABI at the end of gsx_kernels.h; NumPy twin of the generator in ops/memtest.py.
+// bandwidth, and the scrub (gsx_hbm_fill), which is the SOLID write pass.  C ABI at the end of gsx_kernels.h; NumPy
+// twin of the generator in ops/memtest.py.
 //
 // Every pass is one grid-stride launch: 16 B per lane (global_load / global_store_dwordx4), four independent
 // accesses in flight per lane, grid sized from the CU count, 64-bit index math, no LDS, no scratch, no atomics.
@@ -96,13 +97,52 @@ __device__ __forceinline__ uint32_t put_word(gsx_memtest_err* recs, uint32_t slo
   return slot;
 }
 
-// The rare path, entered by a whole wave (every lane active: both loops of the kernel keep a wave together) when any
-// of its lanes saw a mismatch in this iteration and the wave's slots are not used up: the lanes' bad dwords take the
-// wave's next slots in lane order.  `nrec` is the wave's record count so far, the same in every lane; returns the new
-// one.  A wave in a range that is bad throughout comes here once, for 32 stores.
-__device__ __forceinline__ uint32_t record_errors(gsx_memtest_err* recs, uint32_t nrec, uint32_t c, uint64_t off0,
-                                                  uint64_t off1, uint64_t off2, uint64_t off3, uint4 e0, uint4 a0,
-                                                  uint4 e1, uint4 a1, uint4 e2, uint4 a2, uint4 e3, uint4 a3) {
+// what a wave has found so far in its sweep
+struct Tally {
+  uint32_t mine = 0;  // this lane's bad dwords
+  uint32_t flip = 0;  // OR of expected ^ actual over them
+  uint32_t nrec = 0;  // records the wave has written, the same in every lane
+};
+
+// One step of the sweep, called by a whole wave (every lane active: both loops of the kernel keep a wave together):
+// the N words i, i + step, ... of a lane that is `live`; a lane that is not stays in with a count of zero.
+// e[] and a[] are indexed by unrolled constants only, so they stay in registers.
+template <int PAT, int MODE, int N>
+__device__ __forceinline__ void sweep_step(uint4* __restrict__ p, uint64_t i, uint64_t step, bool live, uint64_t W0,
+                                           uint32_t seed, uint64_t key, uint32_t inv, gsx_memtest_err* recs,
+                                           Tally& t) {
+  if (MODE == kWrite) {
+    if (live) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) p[i + k * step] = gen_word<PAT>(W0 + i + k * step, seed, key, inv);
+    }
+    return;
+  }
+  uint4 e[N], a[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) e[k] = a[k] = make_uint4(0, 0, 0, 0);
+  if (live) {
+    // N independent 16-B loads in flight per lane, all issued before any expected word is generated
+#pragma unroll
+    for (int k = 0; k < N; ++k) a[k] = ld16(p + i + k * step);
+#pragma unroll
+    for (int k = 0; k < N; ++k) e[k] = gen_word<PAT>(W0 + i + k * step, seed, key, inv);
+    if (MODE == kCheckRewrite) {  // the complement goes out whether or not the word was bad
+#pragma unroll
+      for (int k = 0; k < N; ++k) p[i + k * step] = make_uint4(~e[k].x, ~e[k].y, ~e[k].z, ~e[k].w);
+    }
+  }
+  uint32_t c = 0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    c += bad_dwords(e[k], a[k]);
+    t.flip |= flipped_bits(e[k], a[k]);
+  }
+  t.mine += c;
+  if (t.nrec >= kMaxErrs || __ballot(c != 0) == 0) return;
+  // The rare path: a lane of the wave saw a mismatch in this step and the wave's slots are not used up.  The lanes'
+  // bad dwords take the wave's next slots in lane order.  A wave in a range that is bad throughout comes here once,
+  // for 32 stores.
   const int lane = threadIdx.x & 63;
   uint32_t incl = c;  // inclusive prefix sum of the lanes' counts
   for (int o = 1; o < 64; o <<= 1) {
@@ -110,14 +150,12 @@ __device__ __forceinline__ uint32_t record_errors(gsx_memtest_err* recs, uint32_
     if (lane >= o) incl += up;
   }
   const uint32_t total = __shfl(incl, 63, 64);
-  uint32_t slot = nrec + incl - c;
+  uint32_t slot = t.nrec + incl - c;
   if (c != 0 && slot < kMaxErrs) {
-    slot = put_word(recs, slot, off0, e0, a0);
-    slot = put_word(recs, slot, off1, e1, a1);
-    slot = put_word(recs, slot, off2, e2, a2);
-    slot = put_word(recs, slot, off3, e3, a3);
+#pragma unroll
+    for (int k = 0; k < N; ++k) slot = put_word(recs, slot, 16 * (W0 + i + k * step), e[k], a[k]);
   }
-  return nrec + total < kMaxErrs ? nrec + total : kMaxErrs;
+  t.nrec = t.nrec + total < kMaxErrs ? t.nrec + total : kMaxErrs;
 }
 
 // p[0, n16): the words W0 .. W0 + n16 - 1.  MODE kWrite stores the pattern; kCheck compares; kCheckRewrite
@@ -128,71 +166,33 @@ __global__ __launch_bounds__(256) void memtest_kernel(uint4* __restrict__ p, uin
   const uint64_t key = (static_cast<uint64_t>(seed) + 1ull) * 0x9E3779B97F4A7C15ull;  // never 0: mix64(0) is 0
   uint64_t i = blockIdx.x * 256ull + threadIdx.x;
   const uint64_t step = gridDim.x * 256ull;
-  uint32_t mine = 0, flip = 0, nrec = 0;
+  Tally t;
   const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);
   gsx_memtest_err* recs = MODE == kWrite ? nullptr : rep.recs + static_cast<uint64_t>(wave) * kMaxErrs;
   // a wave's 64 lanes hold consecutive words: the unrolled loop runs while the wave's last lane has four words left,
   // so the whole wave leaves it together
   for (uint64_t last = i + (63u - (threadIdx.x & 63u)); last + 3 * step < n16; last += 4 * step, i += 4 * step) {
-    const uint64_t i1 = i + step, i2 = i + 2 * step, i3 = i + 3 * step;
-    if (MODE == kWrite) {
-      p[i] = gen_word<PAT>(W0 + i, seed, key, inv);
-      p[i1] = gen_word<PAT>(W0 + i1, seed, key, inv);
-      p[i2] = gen_word<PAT>(W0 + i2, seed, key, inv);
-      p[i3] = gen_word<PAT>(W0 + i3, seed, key, inv);
-    } else {
-      // four independent 16-B loads in flight per lane
-      const uint4 a0 = ld16(p + i), a1 = ld16(p + i1), a2 = ld16(p + i2), a3 = ld16(p + i3);
-      const uint4 e0 = gen_word<PAT>(W0 + i, seed, key, inv), e1 = gen_word<PAT>(W0 + i1, seed, key, inv);
-      const uint4 e2 = gen_word<PAT>(W0 + i2, seed, key, inv), e3 = gen_word<PAT>(W0 + i3, seed, key, inv);
-      if (MODE == kCheckRewrite) {
-        p[i] = make_uint4(~e0.x, ~e0.y, ~e0.z, ~e0.w);
-        p[i1] = make_uint4(~e1.x, ~e1.y, ~e1.z, ~e1.w);
-        p[i2] = make_uint4(~e2.x, ~e2.y, ~e2.z, ~e2.w);
-        p[i3] = make_uint4(~e3.x, ~e3.y, ~e3.z, ~e3.w);
-      }
-      const uint32_t c = bad_dwords(e0, a0) + bad_dwords(e1, a1) + bad_dwords(e2, a2) + bad_dwords(e3, a3);
-      mine += c;
-      flip |= flipped_bits(e0, a0) | flipped_bits(e1, a1) | flipped_bits(e2, a2) | flipped_bits(e3, a3);
-      if (nrec < kMaxErrs && __ballot(c != 0) != 0) {
-        nrec = record_errors(recs, nrec, c, 16 * (W0 + i), 16 * (W0 + i1), 16 * (W0 + i2), 16 * (W0 + i3), e0, a0,
-                             e1, a1, e2, a2, e3, a3);
-      }
-    }
+    sweep_step<PAT, MODE, 4>(p, i, step, true, W0, seed, key, inv, recs, t);
   }
   // tail: the words left (four per lane in a wave that straddles the end of the unrolled range).  Lanes run out
   // at different trip counts, so those that are done stay in with a count of zero until the whole wave is
   for (;;) {
     const bool live = i < n16;
     if (__ballot(live) == 0) break;
-    if (MODE == kWrite) {
-      if (live) p[i] = gen_word<PAT>(W0 + i, seed, key, inv);
-    } else {
-      uint4 e = make_uint4(0, 0, 0, 0), a = e;
-      if (live) {
-        a = ld16(p + i);
-        e = gen_word<PAT>(W0 + i, seed, key, inv);
-        if (MODE == kCheckRewrite) p[i] = make_uint4(~e.x, ~e.y, ~e.z, ~e.w);
-      }
-      const uint32_t c = bad_dwords(e, a);
-      mine += c;
-      flip |= flipped_bits(e, a);
-      if (nrec < kMaxErrs && __ballot(c != 0) != 0) {
-        nrec = record_errors(recs, nrec, c, 16 * (W0 + i), 0, 0, 0, e, a, e, e, e, e, e, e);
-      }
-    }
+    sweep_step<PAT, MODE, 1>(p, i, step, live, W0, seed, key, inv, recs, t);
     i += step;
   }
   if (MODE != kWrite) {
     // wave64 reduction over the whole grid-stride loop: one counter update per wave and launch, and none from a
     // wave that saw no mismatch (a lane's own count fits 32 bits: it reads a 1/2^19th of the range on MI355X)
-    unsigned long long bad = mine;
+    unsigned long long bad = t.mine;
+    uint32_t flip = t.flip;
     for (int o = 32; o > 0; o >>= 1) {
       bad += __shfl_xor(bad, o, 64);
       flip |= __shfl_xor(flip, o, 64);
     }
     if ((threadIdx.x & 63) == 0 && bad) {
-      u32x4 h = {static_cast<uint32_t>(bad), static_cast<uint32_t>(bad >> 32), flip, nrec};
+      u32x4 h = {static_cast<uint32_t>(bad), static_cast<uint32_t>(bad >> 32), flip, t.nrec};
       *reinterpret_cast<u32x4*>(&rep.heads[wave]) = h;
     }
   }
@@ -232,29 +232,20 @@ int grid_for(uint64_t n16, int cus) {
   return static_cast<int>(g > cap ? cap : (g < 1 ? 1 : g));
 }
 
-template <int MODE>
-int launch(hipStream_t st, int grid, int pattern, uint4* p, uint64_t n16, uint64_t W0, uint32_t seed, uint32_t inv,
-           LaunchReport rep) {
-  switch (pattern) {
-    case GSX_MEMTEST_ADDR:
-      hipLaunchKernelGGL((memtest_kernel<GSX_MEMTEST_ADDR, MODE>), dim3(grid), dim3(256), 0, st, p, n16, W0, seed,
-                         inv, rep);
-      break;
-    case GSX_MEMTEST_SOLID:
-      hipLaunchKernelGGL((memtest_kernel<GSX_MEMTEST_SOLID, MODE>), dim3(grid), dim3(256), 0, st, p, n16, W0, seed,
-                         inv, rep);
-      break;
-    case GSX_MEMTEST_WALK:
-      hipLaunchKernelGGL((memtest_kernel<GSX_MEMTEST_WALK, MODE>), dim3(grid), dim3(256), 0, st, p, n16, W0, seed,
-                         inv, rep);
-      break;
-    case GSX_MEMTEST_RANDOM:
-      hipLaunchKernelGGL((memtest_kernel<GSX_MEMTEST_RANDOM, MODE>), dim3(grid), dim3(256), 0, st, p, n16, W0, seed,
-                         inv, rep);
-      break;
-    default:
-      return fail_arg("gsx_memtest: unknown pattern");
-  }
+// the kernels, kKernels[pattern][mode]: one row per GSX_MEMTEST_* pattern, its columns kWrite, kCheck, kCheckRewrite
+using Kernel = void (*)(uint4*, uint64_t, uint64_t, uint32_t, uint32_t, LaunchReport);
+template <int PAT>
+constexpr Kernel kRow[] = {memtest_kernel<PAT, kWrite>, memtest_kernel<PAT, kCheck>, memtest_kernel<PAT, kCheckRewrite>};
+constexpr const Kernel* kKernels[] = {kRow<GSX_MEMTEST_ADDR>, kRow<GSX_MEMTEST_SOLID>, kRow<GSX_MEMTEST_WALK>,
+                                      kRow<GSX_MEMTEST_RANDOM>};
+constexpr int kPatterns = sizeof(kKernels) / sizeof(kKernels[0]);
+static_assert(GSX_MEMTEST_ADDR == 0 && GSX_MEMTEST_SOLID == 1 && GSX_MEMTEST_WALK == 2 && GSX_MEMTEST_RANDOM == 3,
+              "kKernels is indexed by the pattern's value");
+
+int launch(int mode, hipStream_t st, int grid, int pattern, uint4* p, uint64_t n16, uint64_t W0, uint32_t seed,
+           uint32_t inv, LaunchReport rep) {
+  if (pattern < 0 || pattern >= kPatterns) return fail_arg("gsx_memtest: unknown pattern");
+  hipLaunchKernelGGL(kKernels[pattern][mode], dim3(grid), dim3(256), 0, st, p, n16, W0, seed, inv, rep);
   GSX_CHECK(hipGetLastError());
   return 0;
 }
@@ -276,8 +267,18 @@ int gsx_memtest_write(void* stream, void* base, uint64_t bytes, uint64_t origin,
   if (!bytes) return 0;
   int dev = 0, cus = 0;
   if (int rc = device_state(&dev, &cus, nullptr)) return rc;
-  return launch<kWrite>(S(stream), grid_for(bytes / 16, cus), pattern, static_cast<uint4*>(base), bytes / 16,
-                        origin / 16, seed, invert ? 0xFFFFFFFFu : 0u, LaunchReport{});
+  return launch(kWrite, S(stream), grid_for(bytes / 16, cus), pattern, static_cast<uint4*>(base), bytes / 16,
+                origin / 16, seed, invert ? 0xFFFFFFFFu : 0u, LaunchReport{});
+}
+
+// the scrub: the SOLID write pass with the pattern as its seed; no report, so neither pinned memory nor a mutex
+int gsx_hbm_fill(void* stream, void* base, uint64_t bytes, uint32_t pattern) {
+  if (!base || bytes % 16 || reinterpret_cast<uintptr_t>(base) % 16) return fail_arg("gsx_hbm_fill: need 16-B multiple");
+  if (!bytes) return 0;
+  int dev = 0, cus = 0;
+  if (int rc = device_state(&dev, &cus, nullptr)) return rc;
+  return launch(kWrite, S(stream), grid_for(bytes / 16, cus), GSX_MEMTEST_SOLID, static_cast<uint4*>(base), bytes / 16,
+                0, pattern, 0, LaunchReport{});
 }
 
 int gsx_memtest_check(void* stream, void* base, uint64_t bytes, uint64_t origin, int pattern, uint32_t seed,
@@ -296,11 +297,9 @@ int gsx_memtest_check(void* stream, void* base, uint64_t bytes, uint64_t origin,
   std::memset(rep.heads, 0, waves * sizeof(WaveHead));
   __atomic_thread_fence(__ATOMIC_SEQ_CST);
   const uint32_t inv = invert ? 0xFFFFFFFFu : 0u;
-  int rc = rewrite ? launch<kCheckRewrite>(st, grid, pattern, static_cast<uint4*>(base), bytes / 16, origin / 16,
-                                           seed, inv, rep)
-                   : launch<kCheck>(st, grid, pattern, static_cast<uint4*>(base), bytes / 16, origin / 16, seed, inv,
-                                    rep);
-  if (rc) return rc;
+  if (int rc = launch(rewrite ? kCheckRewrite : kCheck, st, grid, pattern, static_cast<uint4*>(base), bytes / 16,
+                      origin / 16, seed, inv, rep))
+    return rc;
   GSX_CHECK(hipStreamSynchronize(st));
   __atomic_thread_fence(__ATOMIC_SEQ_CST);
   for (size_t w = 0; w < waves; ++w) {

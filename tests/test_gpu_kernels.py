@@ -90,16 +90,23 @@ def test_hbm_admit_n_multi_extent_pods(hip):
     s.destroy()
 
 
-def test_hbm_admit_n_opt_in_single_launch():
-    """``GSX_ADMIT_ONE_LAUNCH=1`` is read once per process, so the check runs in a child
-    (``scripts/experiments/one_launch_check.py``): disjoint extents in one launch, an overlap in two, same counts."""
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, GSX_ADMIT_ONE_LAUNCH="1", PYTHONPATH=repo)
-    r = subprocess.run([sys.executable, os.path.join(repo, "scripts", "experiments", "one_launch_check.py")],
-                       capture_output=True, text=True, timeout=120, env=env, cwd=repo)
-    assert r.returncode == 0 and "one-launch ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+def test_hbm_admit_n_counts_damage_and_overlap(hip):
+    """A verify-only table counts a resident slice's overwritten stamps, and an admission placed over two resident
+    extents adds the stamps it overwrote to that count."""
+    s = hip.Stream(0)
+    buf = hip.DeviceBuffer(0, 64 << 20)
+    mib8, st = 8 << 20, 1 << 16
+    a, b = (buf.addr(0), mib8, 11), (buf.addr(2 * mib8), mib8, 22)
+    assert hip.hbm_admit_n(s, [a, b], 2, st) == 0  # two new, nothing resident
+    c = [(buf.addr(mib8), mib8, 33), (buf.addr(3 * mib8), 2 * mib8, 33)]
+    assert hip.hbm_admit_n(s, c + [a, b], 2, st) == 0  # two more, the first two resident
+    hip.hbm_fill(s, buf.addr(0), 1 << 20, 0)  # damage a
+    s.sync()
+    assert hip.hbm_admit_n(s, c + [a, b], 0, st) == (1 << 20) // st  # verify-only table
+    d = [(buf.addr(mib8 + mib8 // 2), mib8, 44)]  # overlaps c[0] and b
+    assert hip.hbm_admit_n(s, d + c + [a, b], 1, st) == 2 * (mib8 // 2) // st + (1 << 20) // st
+    buf.free()
+    s.destroy()
 
 
 def test_hbm_fill_pattern_and_bandwidth(hip):

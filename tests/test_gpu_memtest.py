@@ -80,6 +80,25 @@ def write_and_compare(hip, s, buf, pattern, seed, invert, nbytes, origin):
         raise AssertionError(f"{ctx}: dword {k} is {body[k]:#x}, twin says {want[k]:#x}")
 
 
+def test_hbm_fill_stays_in_its_range(hip, stream):
+    """Fill is the SOLID write pass: its tail, a range that is only 16-B aligned, and its bounds.  The guards are laid
+    by a host copy, since ``write_and_compare`` lays its own with the fill under test here."""
+    lo = GUARD + 16
+    for nbytes in [*SIZES, CAPPED]:
+        total = lo + nbytes + GUARD
+        buf = hip.DeviceBuffer(0, total)
+        try:
+            buf.from_host(np.full(total // 4, GUARD_PAT, dtype=np.uint32).tobytes())
+            hip.hbm_fill(stream, buf.addr(lo), nbytes, 0x1234ABCD)
+            stream.sync()
+            got = words(buf, total)
+        finally:
+            buf.free()
+        assert (got[:lo // 4] == GUARD_PAT).all(), ("guard before", nbytes)
+        assert (got[(lo + nbytes) // 4:] == GUARD_PAT).all(), ("guard after", nbytes)
+        assert (got[lo // 4:(lo + nbytes) // 4] == 0x1234ABCD).all(), ("range", nbytes)
+
+
 @pytest.mark.parametrize("pattern", sorted(mt.PATTERNS.values()))
 def test_write_equals_the_numpy_twin(hip, stream, small, pattern):
     for seed in (0, 0x9E3779B9):
@@ -272,7 +291,7 @@ def test_bandwidth(hip, stream, big):
         print(f"memtest bandwidth {name}: {' '.join(f'{x:.2f}' for x in r)} TB/s "
               f"(median {sorted(r)[1]:.2f}, spread {max(r) - min(r):.2f})")
     for name in ("write", "check", "check+rewrite"):
-        assert sorted(rows[name])[1] > 2.0, (name, rows[name])  # the fill kernel's floor; a broken kernel is far below
+        assert sorted(rows[name])[1] > 2.0, (name, rows[name])  # the floor fill is held to; a broken kernel is far below
 
 
 def test_a_completely_bad_range_costs_what_a_clean_one_costs(hip, stream, big):
