@@ -47,7 +47,8 @@ def main(argv=None) -> int:
                     help="HBM per GPU withheld from sharing (driver / runtime overhead)")
     ap.add_argument("--health-interval", type=float, default=float(env.get("GSX_HEALTH_INTERVAL", "10")))
     ap.add_argument("--debug-port", type=int, default=int(env.get("GSX_DEBUG_PORT", "0")),
-                    help="serve /healthz, /metrics, /debug/state and POST /debug/memtest on this port (0: off)")
+                    help="serve /healthz, /metrics, /debug/state and POST /debug/memtest, /debug/cutest on this port "
+                         "(0: off)")
     ap.add_argument("--debug-host", default=env.get("GSX_DEBUG_HOST", "127.0.0.1"))
     ap.add_argument("--debug-port-file", default="", help="write the debug port here once it listens (port 0)")
     ap.add_argument("--no-register", action="store_true",
@@ -74,6 +75,12 @@ def main(argv=None) -> int:
                          "clean (POST /debug/memtest?device=N on the debug port runs one on demand)")
     ap.add_argument("--preflight-gib", type=float, default=float(env.get("GSX_PREFLIGHT_GIB", "0")),
                     help="GiB per GPU the pre-flight tests (0: all free memory minus the tool's 1 GiB reserve)")
+    ap.add_argument("--preflight-compute", default=env.get("GSX_PREFLIGHT_COMPUTE", "off"),
+                    choices=["off", "quick", "full"],
+                    help="compute test (gsx-cutest, one child process per device) of every device without tenants "
+                         "before the plugin serves, independent of --preflight: a device with CUs whose MFMA, VALU or "
+                         "LDS answer wrong is advertised Unhealthy until a later run is clean (POST "
+                         "/debug/cutest?device=N runs one on demand)")
     ap.add_argument("--preflight-timeout", type=float, default=float(env.get("GSX_PREFLIGHT_TIMEOUT", "120")),
                     help="seconds a pre-flight child may take; it ends itself at 80 %% of it (a truncated run is no "
                          "failure), is killed at 100 %%, and a test that could not run leaves the GPU Healthy")
@@ -104,7 +111,7 @@ def main(argv=None) -> int:
                                 podresources_socket=a.podresources_socket or None,
                                 reconcile_interval=a.reconcile_interval, isolation=iso, extender=a.extender or None,
                                 preflight=a.preflight, preflight_gib=a.preflight_gib,
-                                preflight_timeout=a.preflight_timeout)
+                                preflight_timeout=a.preflight_timeout, preflight_compute=a.preflight_compute)
         # the debug endpoint first: its setup (importing aiohttp) blocks the loop for a few hundred ms, and once the
         # plugin serves, kubelet's Allocates must find the reconciliation (this loop) running
         if a.debug_port or a.debug_port_file:

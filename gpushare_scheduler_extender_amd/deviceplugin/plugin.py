@@ -31,7 +31,8 @@ re-built for MI355X:
   ``ASSIGNED`` annotations when the plugin starts, before it serves;
 * re-registers when kubelet restarts (its socket is re-created);
 * optional debug port: ``/healthz``, ``/metrics``, ``/debug/state``, ``POST /debug/memtest``;
-* optional HBM pre-flight (``preflight.py``): ``gsx-memtest`` on every idle GPU before the plugin serves.
+* optional HBM pre-flight (``preflight.py``): ``gsx-memtest`` on every idle GPU before the plugin serves;
+* optional compute pre-flight (``preflight.py``): ``gsx-cutest`` on every idle device, ``POST /debug/cutest``.
 """
 from __future__ import annotations
 
@@ -53,7 +54,7 @@ from .allocator import AllocateError, ContainerAllocation, assigned_patch, build
 from .devices import UNITS, Device
 from .isolation import IsolationManager
 from .podresources import PodResourcesClient
-from .preflight import InUse, Preflight
+from .preflight import ComputePreflight, InUse, Preflight
 from .state import AllocationState, AllocRecord, PodRec
 
 log = logging.getLogger("gsx.deviceplugin")
@@ -189,7 +190,8 @@ class GpuSharePlugin:
                  podresources_socket: str | None = None, reconcile_interval: float = 2.0,
                  isolation: IsolationManager | None = None, checkpoint: str | None = None,
                  extender: str | None = None, preflight: str = "off", preflight_gib: float = 0.0,
-                 preflight_timeout: float = 120.0, memtest_cmd: list[str] | None = None):
+                 preflight_timeout: float = 120.0, memtest_cmd: list[str] | None = None,
+                 preflight_compute: str = "off", cutest_cmd: list[str] | None = None):
         self.client = client
         # the scheduler extender: the one writer of *_IDX (reconciliation moves go through it, move_record)
         self.extender_url = extender or os.environ.get("GSX_EXTENDER_URL") or None
@@ -207,6 +209,9 @@ class GpuSharePlugin:
         self.isolation = isolation
         # the HBM pre-flight (off by default): gsx-memtest on every idle GPU before the plugin serves (preflight.py)
         self.preflight = Preflight(self, preflight, preflight_gib, preflight_timeout, memtest_cmd)
+        # the compute pre-flight (off by default, independent of the HBM one): gsx-cutest on every idle device
+        self.preflight_compute = ComputePreflight(self, preflight_compute, preflight_timeout, cutest_cmd,
+                                                  self.preflight)
         self._set_devices(devices)
         self.checkpoint = checkpoint if checkpoint is not None else os.path.join(socket_dir, "gsx-allocations.json")
         self.journal_path = (self.checkpoint or os.path.join(socket_dir, "gsx-allocations.json")) + ".journal"
@@ -365,8 +370,9 @@ class GpuSharePlugin:
     def set_health(self, index: int, healthy: bool, why: str = ""):
         d = self.devices.get(index)
         # a GPU whose HBM failed the pre-flight stays Unhealthy whatever amdsmi or a reset says (health is "amdsmi
-        # healthy and not pre-flight failed"); only a later clean memory test clears the mark
-        healthy = healthy and not self.preflight.is_failed(index)
+        # healthy and not pre-flight failed"); only a later clean memory test clears the mark.  The compute
+        # pre-flight's mark holds in the same way, and each of the two needs a clean run of its own
+        healthy = healthy and not self.preflight.is_failed(index) and not self.preflight_compute.is_failed(index)
         if d is None or d.healthy == healthy:
             return
         d.healthy = healthy
@@ -1343,7 +1349,8 @@ class GpuSharePlugin:
                 "devices": [{"index": d.index, "bdf": d.bdf, "healthy": d.healthy, "units": self.units[d.index],
                              "cu": d.cu_count, "partition": d.partition, "memory_partition": d.memory_partition,
                              "health": self.health_info.get(d.index),
-                             "memtest": self.preflight.report(d.index)} for d in self.devices.values()],
+                             "memtest": self.preflight.report(d.index),
+                             "cutest": self.preflight_compute.report(d.index)} for d in self.devices.values()],
                 "informer": {"synced": self.pods.synced.is_set(), "relists": self.pods.relists,
                              "rewatches": self.pods.rewatches, "events": self.pods.events},
                 "stats": dict(self.stats), "timing": dict(self.timing), **self.state.snapshot(),
@@ -1376,6 +1383,7 @@ class GpuSharePlugin:
                     else int(h.get(key, 0))
                 lines.append(f'gpushare_plugin_device_{name}{{device="{i}"}} {v}')
         lines += self.preflight.metrics()
+        lines += self.preflight_compute.metrics()
         lines.append("# TYPE gpushare_plugin_cu_free gauge")
         lines += [f'gpushare_plugin_cu_free{{device="{i}"}} {cp.free_count()}' for i, cp in self.state.cus.items()]
         lines.append("# TYPE gpushare_plugin_allocate_candidates gauge")
@@ -1396,7 +1404,8 @@ class GpuSharePlugin:
 
     async def serve_debug(self, host: str, port: int) -> int:
         """``/healthz``, ``/metrics`` (Prometheus text) and ``/debug/state`` (JSON) for problem determination;
-        ``POST /debug/memtest?device=N[&level=quick|full][&force=1]`` runs the HBM memory test on one GPU now."""
+        ``POST /debug/memtest?device=N[&level=quick|full][&force=1]`` runs the HBM memory test on one GPU now, and
+        ``POST /debug/cutest`` with the same query the compute test."""
         import json  # noqa: PLC0415
 
         from aiohttp import web  # noqa: PLC0415
@@ -1411,21 +1420,28 @@ class GpuSharePlugin:
         async def state(_):
             return web.Response(text=json.dumps(self.debug_state(), indent=1), content_type="application/json")
 
-        async def memtest(request):
+        async def on_demand(request, pre, busy):
             q = request.query
             try:
-                rep = await self.preflight.run_device(int(q.get("device", "")), q.get("level") or None,
-                                                      q.get("force") == "1")
+                rep = await pre.run_device(int(q.get("device", "")), q.get("level") or None, q.get("force") == "1")
             except InUse:
-                return web.Response(status=409, text="GPU in use; force=1 tests what is free now\n")
+                return web.Response(status=409, text=busy)
             except KeyError:
                 return web.Response(status=404, text="no such device\n")
             except ValueError as e:
                 return web.Response(status=400, text=f"{e}\n")
             return web.Response(text=json.dumps(rep), content_type="application/json")
 
+        async def memtest(request):
+            return await on_demand(request, self.preflight, "GPU in use; force=1 tests what is free now\n")
+
+        async def cutest(request):
+            return await on_demand(request, self.preflight_compute,
+                                   "GPU in use; force=1 runs the test next to its tenants\n")
+
         app = web.Application()
         app.router.add_post("/debug/memtest", memtest)
+        app.router.add_post("/debug/cutest", cutest)
         app.router.add_get("/healthz", healthz)
         app.router.add_get("/metrics", metrics)
         app.router.add_get("/debug/state", state)
@@ -1537,10 +1553,11 @@ class GpuSharePlugin:
             self._tasks.append(asyncio.get_running_loop().create_task(self._epoch_loop(), name="gsx-epoch"))
         if not serve:
             return
-        if self.preflight.level != "off":
-            # the allocation state is rebuilt (checkpoint, informer): the GPUs without tenants are tested before
-            # kubelet can be offered their memory
-            await self.preflight.run_all()
+        # the allocation state is rebuilt (checkpoint, informer): the GPUs without tenants are tested before
+        # kubelet can be offered their memory (both pre-flights at once; a GPU's two children take turns)
+        todo = [p for p in (self.preflight, self.preflight_compute) if p.level != "off"]
+        if todo:
+            await asyncio.gather(*(p.run_all() for p in todo))
         await self.serve()
         if publish:
             try:

@@ -1,4 +1,5 @@
-"""HBM pre-flight: run ``gsx-memtest`` on the GPUs nobody uses yet and keep what fails out of ListAndWatch.
+"""Pre-flight: run ``gsx-memtest`` (HBM) and ``gsx-cutest`` (compute) on the GPUs nobody uses yet and keep what fails
+out of ListAndWatch.
 
 The plugin never opens HIP itself: every GPU is tested by a child process of its own (at most
 :data:`MAX_CHILDREN` at a time), whose JSON line and exit code are the result:
@@ -13,6 +14,11 @@ The plugin never opens HIP itself: every GPU is tested by a child process of its
 A GPU with an allocation record, or a pod of this node annotated onto it, is skipped (``"skipped": "in use"``): the
 test never takes memory from a tenant.  Compute partitions of one GPU share its HBM, so one child tests the pool
 and its result holds for every partition; the pool counts as in use when any of them is.
+
+:class:`ComputePreflight` is the same child-runner for ``gsx-cutest`` (``--preflight-compute``): exit 1 means CUs that
+computed wrong answers.  It runs per device, not per pool -- compute partitions of one GPU have CUs of their own --
+with ``--expect-cus`` set to the device's CU count, shares the memory test's cap on children, and never runs while
+the memory test of the same GPU does.  A device is healthy only if neither pre-flight holds it down.
 """
 from __future__ import annotations
 
@@ -30,6 +36,7 @@ KILL_GRACE_S = 2.0  # between SIGTERM and SIGKILL of a child past its timeout
 # what a forced on-demand run leaves free next to the tenants' memory, as the tool's own default does
 FORCE_RESERVE = 1 << 30
 TOOL = Path(__file__).resolve().parents[1] / "_native" / "gsx-memtest"
+CUTEST_TOOL = TOOL.with_name("gsx-cutest")
 
 
 class InUse(Exception):
@@ -37,6 +44,11 @@ class InUse(Exception):
 
 
 class Preflight:
+    NAME = "memtest"  # in log lines, reasons and metric names
+    BAD = "bad_dwords"  # the report key that counts what exit 1 found
+    METRICS = (("bad_dwords", "bad_dwords"), ("bytes_tested", "bytes_tested"), ("seconds", "seconds"),
+               ("last_run_timestamp", "timestamp"))
+
     def __init__(self, plugin, level: str = "off", gib: float = 0.0, timeout: float = 120.0,
                  cmd: list[str] | None = None):
         if level not in LEVELS:
@@ -51,6 +63,16 @@ class Preflight:
         self.reports: dict[str, dict] = {}  # the last outcome per pool
         self.errors_total = 0  # tests that could not run
         self._sem: asyncio.Semaphore | None = None
+        self._gpu_locks: dict[str, asyncio.Lock] = {}  # one child per physical GPU at a time, whichever tool
+
+    def _slot(self) -> asyncio.Semaphore:
+        """The cap on children, shared by every pre-flight of the plugin."""
+        if self._sem is None:
+            self._sem = asyncio.Semaphore(MAX_CHILDREN)
+        return self._sem
+
+    def _gpu_lock(self, idx: int) -> asyncio.Lock:
+        return self._gpu_locks.setdefault(Preflight._key(self, idx), asyncio.Lock())
 
     # ------------------------------------------------------------ which GPUs
     def _key(self, idx: int) -> str:
@@ -119,10 +141,10 @@ class Preflight:
         rep["exit"] = proc.returncode
         if proc.returncode not in (0, 1):
             rep["error"] = rep.get("error") or f"exit status {proc.returncode}"
-        elif "bad_dwords" not in rep:
+        elif self.BAD not in rep:
             rep["error"] = "no report on stdout"
-        elif proc.returncode == 1 and not rep["bad_dwords"]:
-            rep["error"] = "exit 1 without bad dwords"
+        elif proc.returncode == 1 and not rep[self.BAD]:
+            rep["error"] = f"exit 1 without {self.BAD.replace('_', ' ')}"
         return rep
 
     @staticmethod
@@ -154,23 +176,22 @@ class Preflight:
         self.reports[key] = rep
         if rep.get("error"):  # could not run: the GPU stays as it was
             self.errors_total += 1
-            log.warning("memtest of GPU %d could not run: %s", idx, rep["error"])
+            log.warning("%s of GPU %d could not run: %s", self.NAME, idx, rep["error"])
             return
-        if rep.get("bad_dwords"):
+        if rep.get(self.BAD):
             rep["reason"] = self.reason(rep)
             self.failed.add(key)
         else:
             self.failed.discard(key)
         for i in self._pool(idx):
-            if rep.get("bad_dwords"):
+            if rep.get(self.BAD):
                 self.plugin.set_health(i, False, f"({rep['reason']})")
             elif (self.plugin.health_info.get(i) or {}).get("healthy", True):
-                self.plugin.set_health(i, True, "(memtest clean)")  # unless amdsmi holds it down
+                # unless amdsmi, or the other pre-flight, holds it down
+                self.plugin.set_health(i, True, f"({self.NAME} clean)")
 
     async def _one(self, idx: int, level: str, force: bool) -> dict:
-        if self._sem is None:
-            self._sem = asyncio.Semaphore(MAX_CHILDREN)
-        async with self._sem:
+        async with self._gpu_lock(idx), self._slot():
             rep = await self._child(idx, level, force)
         if idx in self.plugin.devices:  # not re-shaped meanwhile
             self._apply(idx, rep)
@@ -190,7 +211,7 @@ class Preflight:
         if todo:
             t0 = time.monotonic()
             await asyncio.gather(*(self._one(i, self.level, False) for i in todo))
-            log.info("pre-flight memtest (%s) of GPUs %s took %.1fs; failed: %s", self.level, todo,
+            log.info("pre-flight %s (%s) of GPUs %s took %.1fs; failed: %s", self.NAME, self.level, todo,
                      time.monotonic() - t0, sorted(self.failed) or "none")
         return {i: self.report(i) for i in sorted(self.plugin.devices) if self.report(i) is not None}
 
@@ -210,15 +231,56 @@ class Preflight:
     # ------------------------------------------------------------ exposed state
     def metrics(self) -> list[str]:
         lines = []
-        for name, key in (("bad_dwords", "bad_dwords"), ("bytes_tested", "bytes_tested"), ("seconds", "seconds"),
-                          ("last_run_timestamp", "timestamp")):
-            lines.append(f"# TYPE gpushare_plugin_memtest_{name} gauge")
+        for name, key in self.METRICS:
+            lines.append(f"# TYPE gpushare_plugin_{self.NAME}_{name} gauge")
             for i in sorted(self.plugin.devices):
                 rep = self.report(i)
                 if rep is None or "skipped" in rep or (rep.get("error") and key != "timestamp"):
                     continue
-                lines.append(f'gpushare_plugin_memtest_{name}{{device="{i}"}} {rep.get(key, 0)}')
-        lines += ["# TYPE gpushare_plugin_memtest_errors_total counter",
-                  f"gpushare_plugin_memtest_errors_total {self.errors_total}"]
+                lines.append(f'gpushare_plugin_{self.NAME}_{name}{{device="{i}"}} {rep.get(key, 0)}')
+        lines += [f"# TYPE gpushare_plugin_{self.NAME}_errors_total counter",
+                  f"gpushare_plugin_{self.NAME}_errors_total {self.errors_total}"]
         return lines
+
+
+class ComputePreflight(Preflight):
+    """``gsx-cutest`` through the same child-runner: per device, and never next to ``memory``'s child on one GPU."""
+    NAME = "cutest"
+    BAD = "bad_cu_count"
+    METRICS = (("bad_cus", "bad_cu_count"), ("bad_waves", "bad_waves"), ("cus_seen", "cus_seen"),
+               ("seconds", "seconds"), ("last_run_timestamp", "timestamp"))
+
+    def __init__(self, plugin, level: str = "off", timeout: float = 120.0, cmd: list[str] | None = None,
+                 memory: Preflight | None = None):
+        super().__init__(plugin, level, 0.0, timeout, cmd or [str(CUTEST_TOOL)])
+        self.memory = memory
+
+    def _slot(self) -> asyncio.Semaphore:
+        return self.memory._slot() if self.memory is not None else super()._slot()
+
+    def _gpu_lock(self, idx: int) -> asyncio.Lock:
+        return self.memory._gpu_lock(idx) if self.memory is not None else super()._gpu_lock(idx)
+
+    def _key(self, idx: int) -> str:
+        """By device: a partition's CUs are its own (the BDF tells physical GPUs apart, the index partitions)."""
+        d = self.plugin.devices.get(idx)
+        return f"#{idx}" if d is None else f"{d.bdf}#{idx}"
+
+    def _pool(self, idx: int) -> list[int]:
+        return [idx]
+
+    def _argv(self, idx: int, level: str, force: bool) -> list[str]:
+        d = self.plugin.devices[idx]
+        argv = [*self.cmd, "--bdf", d.bdf] if d.bdf else [*self.cmd, "--device", str(idx)]
+        argv += ["--level", level]
+        if d.cu_count > 0:
+            argv += ["--expect-cus", str(d.cu_count)]
+        return [*argv, "--max-seconds", f"{0.8 * self.timeout:.3f}"]
+
+    @staticmethod
+    def reason(rep: dict) -> str:
+        first = (rep.get("bad_cus") or [{}])[0]
+        where = " ".join(f"{k} {first.get(k, 0)}" for k in ("xcc", "se", "sh", "cu"))
+        return (f"cutest: {rep.get('bad_cu_count', 0)} bad CUs (first {where}, "
+                f"units {','.join(first.get('units') or []) or '?'})")
 

@@ -45,6 +45,52 @@ class MemtestReport(ctypes.Structure):
         return [(e.offset, e.expected, e.actual) for e in self.errs[:self.n_errs]]
 
 
+class CutestRecord(ctypes.Structure):
+    """``gsx_cutest_record``: what one wave of the compute test wrote."""
+    _fields_ = [("hw_id", ctypes.c_uint32), ("xcc_id", ctypes.c_uint32), ("fail_mask", ctypes.c_uint32),
+                ("seed", ctypes.c_uint32), ("sig", ctypes.c_uint64 * 9)]
+
+    def where(self) -> tuple[int, int, int, int]:
+        """The physical CU ``(xcc, se, sh, cu)`` the wave ran on."""
+        d = decode_hw_id(self.hw_id, self.xcc_id)
+        return d["xcc"], d["se"], d["sh"], d["cu"]
+
+    @property
+    def simd(self) -> int:
+        return (self.hw_id >> 4) & 0x3
+
+
+class CutestInject(ctypes.Structure):
+    _fields_ = [("xcc", ctypes.c_int32), ("se", ctypes.c_int32), ("sh", ctypes.c_int32), ("cu", ctypes.c_int32),
+                ("simd", ctypes.c_int32), ("unit", ctypes.c_int32), ("xor_mask", ctypes.c_uint32)]
+
+
+class CutestCu(ctypes.Structure):
+    _fields_ = [("waves", ctypes.c_uint32), ("bad_waves", ctypes.c_uint32), ("fail_mask", ctypes.c_uint16),
+                ("simds", ctypes.c_uint8), ("bad_simds", ctypes.c_uint8)]
+
+
+class CutestBad(ctypes.Structure):
+    _fields_ = [("xcc", ctypes.c_uint8), ("se", ctypes.c_uint8), ("sh", ctypes.c_uint8), ("cu", ctypes.c_uint8),
+                ("simds", ctypes.c_uint8), ("unit", ctypes.c_uint8), ("units", ctypes.c_uint16),
+                ("seed", ctypes.c_uint32), ("expected", ctypes.c_uint64), ("got", ctypes.c_uint64)]
+
+
+class CutestReport(ctypes.Structure):
+    """``gsx_cutest_report``: launches accumulate into it; a new one is all zero."""
+    _fields_ = [("waves", ctypes.c_uint64), ("bad_waves", ctypes.c_uint64), ("cus_seen", ctypes.c_uint32),
+                ("simds_seen", ctypes.c_uint32), ("cus_covered", ctypes.c_uint32), ("bad_cus", ctypes.c_uint32),
+                ("n_bad", ctypes.c_uint32), ("launches", ctypes.c_uint32), ("cus_expected", ctypes.c_uint32),
+                ("covered", ctypes.c_uint32), ("bad", CutestBad * 16), ("cu", CutestCu * 4096)]
+
+    def cus(self) -> dict[tuple[int, int, int, int], CutestCu]:
+        """``{(xcc, se, sh, cu): entry}`` of the physical CUs that ran a wave."""
+        return {(s >> 8, (s >> 5) & 7, (s >> 4) & 1, s & 15): c for s, c in enumerate(self.cu) if c.waves}
+
+    def bad_entries(self) -> list[CutestBad]:
+        return list(self.bad[:self.n_bad])
+
+
 class Slice(ctypes.Structure):
     _fields_ = [("addr", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("tag", ctypes.c_uint64)]
 
@@ -95,6 +141,17 @@ def lib():
             "gsx_memtest_pass": ([i32, ctypes.c_uint32, ctypes.POINTER(MemtestPass)], i32),
             "gsx_memtest_run": ([vp, vp, u64, u64, i32, ctypes.POINTER(MemtestReport),
                                  ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)], i32),
+            "gsx_cutest_unit_name": ([i32], ctypes.c_char_p),
+            "gsx_cutest_unit_shape": ([i32] + [ctypes.POINTER(i32)] * 5, i32),
+            "gsx_cutest_seeds": ([i32], ctypes.c_uint32),
+            "gsx_cutest_expected": ([i32, ctypes.c_uint32, ctypes.POINTER(u64)], i32),
+            "gsx_cutest_launch": ([vp, ctypes.c_uint32, i32, ctypes.POINTER(CutestInject),
+                                   ctypes.POINTER(CutestRecord), ctypes.c_uint32], i32),
+            "gsx_cutest_aggregate": ([ctypes.POINTER(CutestRecord), ctypes.c_uint32, ctypes.POINTER(CutestReport)],
+                                     i32),
+            "gsx_cutest_run": ([vp, i32, ctypes.c_uint32, ctypes.POINTER(CutestReport),
+                                ctypes.POINTER(ctypes.c_double)], i32),
+            "gsx_cutest_stream_cus": ([vp, ctypes.POINTER(ctypes.c_uint32)], i32),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -280,6 +337,58 @@ def memtest_pass_table(level: str) -> list[tuple[str, int, int, int, int]]:
     while lib().gsx_memtest_pass(LEVEL_IDS[level], len(out), ctypes.byref(p)) == 0:
         out.append(("write" if p.write else "check", p.pattern, p.seed, p.invert, p.rewrite))
     return out
+
+
+def cutest_expected(unit: int, seed: int) -> int:
+    """The native host twin's signature of ``unit`` for ``seed`` (``ops.cutest.expected_signature``); no device call."""
+    sig = ctypes.c_uint64(0)
+    _ck(lib().gsx_cutest_expected(unit, seed & 0xFFFFFFFF, ctypes.byref(sig)), "cutest_expected")
+    return sig.value
+
+
+def cutest_unit_table() -> list[tuple]:
+    """The native unit table: ``(name, m, n, k, rounds, span)`` per matrix unit, ``(name,)`` for the others."""
+    out = []
+    while (name := lib().gsx_cutest_unit_name(len(out))) is not None:
+        v = [ctypes.c_int(0) for _ in range(5)]
+        shaped = lib().gsx_cutest_unit_shape(len(out), *map(ctypes.byref, v)) == 0
+        out.append((name.decode(), *(x.value for x in v)) if shaped else (name.decode(),))
+    return out
+
+
+def cutest_seeds(level: str) -> int:
+    from .cutest import LEVEL_IDS  # noqa: PLC0415
+
+    return lib().gsx_cutest_seeds(LEVEL_IDS[level])
+
+
+def cutest_launch(stream: Stream, seed: int, blocks: int, inject: tuple | None = None):
+    """One launch of the compute test: the ``4 * blocks`` waves' records (a ctypes array of :class:`CutestRecord`).
+    ``inject`` is ``(xcc, se, sh, cu, simd or -1, unit, xor_mask)``.  Synchronises the stream."""
+    recs = (CutestRecord * (4 * blocks))()
+    inj = ctypes.byref(CutestInject(*inject)) if inject else None
+    _ck(lib().gsx_cutest_launch(stream.handle, seed & 0xFFFFFFFF, blocks, inj, recs, len(recs)), "cutest_launch")
+    return recs
+
+
+def cutest_aggregate(records, report: CutestReport | None = None) -> CutestReport:
+    """Accumulate records (a ctypes array or a list of :class:`CutestRecord`) into ``report``; pure host code."""
+    rep = CutestReport() if report is None else report
+    arr = records if isinstance(records, ctypes.Array) else (CutestRecord * max(1, len(records)))(*records)
+    _ck(lib().gsx_cutest_aggregate(arr, len(records), ctypes.byref(rep)), "cutest_aggregate")
+    return rep
+
+
+def cutest_run(stream: Stream, level: str = "quick", expect_cus: int = 0,
+               report: CutestReport | None = None) -> tuple[CutestReport, float]:
+    """A level's launches, and more while coverage is short (``ops.cutest.SEEDS``): ``(report, seconds)``."""
+    from .cutest import LEVEL_IDS  # noqa: PLC0415
+
+    rep = CutestReport() if report is None else report
+    seconds = ctypes.c_double(0.0)
+    _ck(lib().gsx_cutest_run(stream.handle, LEVEL_IDS[level], expect_cus, ctypes.byref(rep), ctypes.byref(seconds)),
+        "cutest_run")
+    return rep, seconds.value
 
 
 def gemm_bf16_nt(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int):

@@ -14,6 +14,9 @@
 //                          when a pod leaves (and as the HBM roofline probe);
 //  * HBM memory test     — pattern write / check / moving-inversions passes at HBM
 //                          bandwidth: the device plugin's pre-flight (memtest.hip);
+//  * compute test        — a known-answer test of every CU's MFMA, VALU and LDS that
+//                          names the physical CUs and SIMDs that answered wrong: the
+//                          plugin's compute pre-flight (cutest.hip);
 //  * bf16 MFMA GEMM      — the pod workload used to measure isolation
 //                          (throughput under per-pod CU partitions);
 //  * CU-masked streams   — hipExtStreamCreateWithCUMask.
@@ -142,6 +145,92 @@ typedef struct {
   int invert, rewrite, write;  // write != 0: a write pass; otherwise a check, with or without rewrite
 } gsx_memtest_pass_t;
 int gsx_memtest_pass(int level, uint32_t idx, gsx_memtest_pass_t* out);
+
+// Compute pre-flight (cutest.hip): a known-answer test of every CU's matrix cores, vector ALU and LDS.  One launch
+// runs workgroups of 4 waves that each take a CU's whole LDS (one workgroup per CU at a time); every wave reads
+// its HW_ID / XCC_ID, runs the units below from `seed` and writes one record.  A unit ends in one 64-bit
+// signature, the same for every healthy wave of a launch; NumPy twin in ops/cutest.py.
+//   MFMA_*    R chained matrix instructions on integer operands that are a function of (seed, unit, round, matrix
+//             coordinates); every result is an exact integer whatever the summation order
+//   VALU_F32  MFMA_F32's product by v_fma_f32: the same signature
+//   VALU_INT  a per-lane chain of 32-bit multiplies (low and high), 64-bit multiply-adds, rotates, xor, popcount
+//             and compare-selects
+//   LDS       two passes (the RANDOM words of the memory test, then their complement) over the workgroup's whole
+//             LDS: every wave fills a quarter and checks the quarter another wave wrote, half of it with b128
+//             and half with b32 reads
+enum {
+  GSX_CUTEST_MFMA_BF16_16 = 0,
+  GSX_CUTEST_MFMA_BF16_32 = 1,
+  GSX_CUTEST_MFMA_F16 = 2,
+  GSX_CUTEST_MFMA_FP8 = 3,
+  GSX_CUTEST_MFMA_I8 = 4,
+  GSX_CUTEST_MFMA_F32 = 5,
+  GSX_CUTEST_VALU_F32 = 6,
+  GSX_CUTEST_VALU_INT = 7,
+  GSX_CUTEST_LDS = 8,
+  GSX_CUTEST_UNITS = 9
+};
+enum { GSX_CUTEST_QUICK = 0, GSX_CUTEST_FULL = 1 };
+#define GSX_CUTEST_MAX_BAD 16      // bad-CU entries a report lists; its counts stay exact beyond
+#define GSX_CUTEST_CU_SLOTS 4096   // a physical CU's slot: xcc << 8 | se << 5 | sh << 4 | cu
+#define GSX_CUTEST_MAX_BLOCKS 8192
+const char* gsx_cutest_unit_name(int unit);  // NULL outside the table
+// The matrix units' table: a chain of `rounds` M x N x K products of integers in [-span/2, span/2 - 1].  Nonzero
+// for a unit that is no matrix unit.
+int gsx_cutest_unit_shape(int unit, int* m, int* n, int* k, int* rounds, int* span);
+// Launches of a level (seeds 0 .. n - 1): QUICK 8, FULL 256; 0 for an unknown level.
+uint32_t gsx_cutest_seeds(int level);
+typedef struct {
+  uint32_t hw_id, xcc_id;  // HW_REG_HW_ID and HW_REG_XCC_ID of the wave, as the CU probe records them
+  uint32_t fail_mask;      // bit u: sig[u] is not the expected signature
+  uint32_t seed;
+  uint64_t sig[GSX_CUTEST_UNITS];
+} gsx_cutest_record;
+// For tests: a wave whose HW_ID fields match (simd < 0: any SIMD of the CU) XORs xor_mask into the raw 32 bits of
+// result element (0, 0) of `unit` before the fold (VALU_INT: lane 0's 32-bit state; LDS: dword 0 of the quarter
+// it read).  xor_mask == 0: off.  One value changes; nothing else does.
+typedef struct {
+  int32_t xcc, se, sh, cu, simd, unit;
+  uint32_t xor_mask;
+} gsx_cutest_inject;
+typedef struct {
+  uint32_t waves, bad_waves;
+  uint16_t fail_mask;        // OR over the CU's waves
+  uint8_t simds, bad_simds;  // 4-bit sets: the SIMDs that ran a wave / a bad wave
+} gsx_cutest_cu;
+typedef struct {
+  uint8_t xcc, se, sh, cu;
+  uint8_t simds;  // the SIMDs with a bad wave
+  uint8_t unit;   // the first bad unit of the CU's first bad wave, with its seed and signatures
+  uint16_t units;
+  uint32_t seed;
+  uint64_t expected, got;
+} gsx_cutest_bad;
+typedef struct {
+  uint64_t waves, bad_waves;
+  uint32_t cus_seen, simds_seen;  // CUs / (CU, SIMD) pairs that ran a wave
+  uint32_t cus_covered;           // CUs all four of whose SIMDs ran a wave
+  uint32_t bad_cus, n_bad;        // exact count; min(bad_cus, MAX_BAD) entries in bad[]
+  uint32_t launches, cus_expected, covered;  // set by gsx_cutest_run
+  gsx_cutest_bad bad[GSX_CUTEST_MAX_BAD];
+  gsx_cutest_cu cu[GSX_CUTEST_CU_SLOTS];
+} gsx_cutest_report;
+// The host-side twin, in plain integer arithmetic: no device call.
+int gsx_cutest_expected(int unit, uint32_t seed, uint64_t* sig);
+// One launch of `blocks` workgroups and one stream sync; records_out[0, 4 * blocks) are the waves' records
+// (n >= 4 * blocks).  inject may be NULL.
+int gsx_cutest_launch(void* stream, uint32_t seed, int blocks, const gsx_cutest_inject* inject,
+                      gsx_cutest_record* records_out, uint32_t n);
+// Pure host code: ACCUMULATES n records into *report (the caller zeroes a new one).
+int gsx_cutest_aggregate(const gsx_cutest_record* records, uint32_t n, gsx_cutest_report* report);
+// A level's launches (4 workgroups per expected CU), accumulated into *report (the caller zeroes it).  While
+// fewer than expect_cus CUs are covered, up to GSX_CUTEST_EXTRA_LAUNCHES more follow; coverage that stays short
+// clears report->covered and is no error.  expect_cus == 0: the popcount of the stream's CU mask, or the device's
+// CU count when the stream has none.
+#define GSX_CUTEST_EXTRA_LAUNCHES 8
+int gsx_cutest_run(void* stream, int level, uint32_t expect_cus, gsx_cutest_report* report, double* seconds_out);
+// What expect_cus == 0 stands for on `stream`.
+int gsx_cutest_stream_cus(void* stream, uint32_t* cus);
 
 #ifdef __cplusplus
 }
