@@ -544,6 +544,14 @@ int launch(const char* who, hipStream_t s, const void* A, const void* B, void* C
     std::snprintf(msg, sizeof(msg), "%s: operands must be 16-B aligned", who);
     return fail_arg(msg);
   }
+  // The kernels keep a lane's source offset inside an operand tile in an int: row * K + column, with
+  // row < max(BM, BN) and column <= BK - 8 (off[] of the three kernels).  Everything else that grows with the
+  // problem is added to the pointer in 64 bits.
+  constexpr int SIDE = BM > BN ? BM : BN;
+  if (static_cast<int64_t>(SIDE - 1) * K + (BK - 8) > INT32_MAX) {
+    std::snprintf(msg, sizeof(msg), "%s: K too large: %d rows of K elements must stay below 2^31", who, SIDE);
+    return fail_arg(msg);
+  }
   // More dynamic LDS than the default limit has to be asked for.  The flag is per device because
   // hipFuncSetAttribute is documented per function and device, not because a failure without it was observed
   // (that has not been measured).  Two threads that race here both set the same value.

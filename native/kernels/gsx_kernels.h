@@ -90,6 +90,8 @@ int gsx_hbm_fill(void* stream, void* base, uint64_t bytes, uint32_t pattern);
 
 // bf16 GEMM (gemm.hip): C[M][N] (bf16) = A[M][K] (bf16, row-major) * B[N][K]^T (bf16, row-major), fp32 accumulate.
 // A, B and C are 16-B aligned.  Launches on `stream` and returns without synchronising.
+// K is limited by the 32-bit offsets inside an operand tile: (max(BM, BN) - 1) * K + 56 < 2^31, which is
+// K <= 8421504 for a tile side of 256 and K <= 16909312 for 128; a longer K is rejected.
 // gsx_gemm_bf16_nt requires M % 128 == 0, N % 128 == 0, K % 64 == 0 and dispatches to one of the configurations
 // below: the phased 256x256 kernel when M and N are multiples of 256, the grouped 128x128 tile otherwise.
 int gsx_gemm_bf16_nt(void* stream, const void* A, const void* B, void* C, int M, int N, int K);

@@ -302,14 +302,9 @@ def gemm_exact_case():
     """Host-built operands whose product has no rounding before the final bf16 conversion: every input is k/16 with
     |k| <= 15 (a bf16), every product a multiple of 2^-8 and every partial sum below 71, so fp32 accumulation is
     exact in any order and the kernel has to equal the fp64 product rounded once."""
-    m, n, k = 768, 1280, 320
-    i, j = torch.arange(m).unsqueeze(1), torch.arange(k).unsqueeze(0)
-    a = (((7 * i + 13 * j) % 31 - 15).double() / 16)
-    i = torch.arange(n).unsqueeze(1)
-    b = (((11 * i + 5 * j) % 29 - 14).double() / 16)
-    assert torch.equal(a.bfloat16().double(), a) and torch.equal(b.bfloat16().double(), b)
-    want = (a @ b.t()).float().bfloat16()
-    return a.bfloat16(), b.bfloat16(), want
+    from tests.gemm_cases import exact_case  # the generator lives with the other GEMM test operands
+
+    return exact_case(768, 1280, 320)
 
 
 @pytest.mark.parametrize("cfg", [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10])
