@@ -10,7 +10,9 @@
 // (gsx_memtest_pass).  A chunk is far larger than the 256 MiB Infinity Cache and every pass sweeps it in ascending
 // order, so a check reads what the pass before it left in HBM, not in a cache; a --bytes below the cache size
 // does not have that property.
-// --max-seconds is consulted between passes: the run ends early with "truncated": true, which is no failure.
+// --max-seconds is consulted between passes: the run ends early with "truncated": true, which is no failure.  It
+// counts from the start of the process, as the timeout of whoever started the tool does: opening the device and
+// allocating the chunks use it up too.  "seconds" and "gbps" cover the passes alone.
 // --inject (for tests) XORs one dword of the tool's own buffer, through a host copy, after the first write pass
 // of the chunk that holds it.
 //
@@ -153,6 +155,7 @@ double since(std::chrono::steady_clock::time_point t0) {
 }  // namespace
 
 int main(int argc, char** argv) {
+  const auto started = std::chrono::steady_clock::now();  // what --max-seconds counts from
   Args a;
   Result r;
   std::memset(&r.rep, 0, sizeof r.rep);
@@ -206,7 +209,7 @@ int main(int argc, char** argv) {
     gsx_memtest_pass_t ps;
     bool complete = true;
     for (uint32_t k = 0; gsx_memtest_pass(a.level, k, &ps) == 0; ++k) {
-      if (a.max_seconds > 0 && since(t0) >= a.max_seconds) {
+      if (a.max_seconds > 0 && since(started) >= a.max_seconds) {
         r.truncated = true;
         complete = false;
         break;

@@ -118,6 +118,18 @@ def test_masked_stream_tests_its_64_cus(hip, clean):
     assert rep.bad_waves == 0 and rep.bad_cus == 0
 
 
+def test_full_level_is_clean_on_the_whole_gpu(hip, clean):
+    """All 256 seeds of ``full``: a false positive at any of them would take a healthy GPU out of service."""
+    s, _blocks, _ = clean
+    cu_count = hip.device_info(0)["cu_count"]
+    run, seconds = hip.cutest_run(s, "full")
+    print("full:", run.launches, "launches,", f"{seconds:.3f}s; covered", run.cus_covered, "of", run.cus_expected)
+    assert run.bad_waves == 0 and run.bad_cus == 0 and run.n_bad == 0
+    assert run.cus_seen == run.cus_expected == cu_count
+    assert run.covered == 1 and run.cus_covered == cu_count
+    assert ct.SEEDS["full"] == 256 and 256 <= run.launches <= 256 + ct.EXTRA_LAUNCHES
+
+
 def _tool(*argv):
     r = subprocess.run([str(TOOL), *argv], capture_output=True, text=True, timeout=120)
     return r.returncode, json.loads(r.stdout.strip().splitlines()[-1])

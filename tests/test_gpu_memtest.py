@@ -23,7 +23,10 @@ GUARD_PAT = 0xC3C3C3C3
 # one word; under one block; one word past a block; tails on both sides of the unrolled loop (the grid is
 # ceil(words / 1024) blocks below 32 MiB, so every lane's four words end right around these sizes)
 SIZES = [16, 4080, 4096 + 16, (1 << 20) + 16, (3 << 20) - 16]
-# past 32 MiB the grid stops growing (8 blocks per CU) and the unrolled loop runs more than once before the tail
+# past 32 MiB the grid stops growing (8 blocks per CU): at 256 CUs this is 5 grid steps + 3 words, so every wave
+# makes exactly one iteration of the unrolled loop, one tail step with all lanes live and, in block 0's wave 0, a
+# second with three (tests/test_memtest_cases.py pins this).  Two unrolled iterations with every dword compared:
+# CAPPED2 of tests/memtest_cases.py, in tests/test_gpu_memtest_report.py
 CAPPED = (40 << 20) + 48
 ORIGINS = [0, 48, 2**36 - (1 << 20)]  # the last crosses W = 2**32 inside the 1 MiB+ buffers
 BIG = (4 << 30) + (2 << 20)
