@@ -135,6 +135,12 @@ def lib():
             "gsx_gemm_cfg_tile": ([i32, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
             "gsx_gemm_cfg_name": ([i32], ctypes.c_char_p),
             "gsx_event_time_gemm": ([vp, vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_gemm_fp8_nt": ([vp, vp, vp, vp, i32, i32, i32, vp, vp, i32], i32),
+            "gsx_gemm_fp8_nt_launch_cfg": ([vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32], i32),
+            "gsx_gemm_fp8_cfg_tile": ([i32, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
+            "gsx_gemm_fp8_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_event_time_gemm_fp8": ([vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32,
+                                         ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
             "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
                                   i32),
@@ -425,3 +431,40 @@ def gemm_bf16_nt_cfg(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: 
     """Launch one tile configuration of the GEMM; an unknown config or a shape it cannot take raises HipError."""
     _ck(lib().gsx_gemm_bf16_nt_launch_cfg(stream.handle, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c),
                                           m, n, k, cfg), f"gemm cfg {cfg}")
+
+
+# ``scale_mode`` of the fp8 GEMM (gsx_kernels.h): c = bf16((acc * scale_a[row or 0]) * scale_b[col or 0])
+SCALE_NONE, SCALE_TENSOR, SCALE_ROW = 0, 1, 2
+
+
+def gemm_fp8_nt(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, scale_a: int = 0, scale_b: int = 0,
+                scale_mode: int = SCALE_NONE):
+    """``C`` (bf16) ``= A * B^T`` on OCP e4m3 operands (``torch.float8_e4m3fn``); the scales are device addresses of
+    fp32 values, one each (``SCALE_TENSOR``) or ``m`` and ``n`` of them (``SCALE_ROW``).  Not synchronised."""
+    _ck(lib().gsx_gemm_fp8_nt(stream.handle, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m, n, k,
+                              ctypes.c_void_p(scale_a), ctypes.c_void_p(scale_b), scale_mode), "gemm_fp8_nt")
+
+
+def gemm_fp8_cfgs() -> dict[int, str]:
+    """``{index: name}`` of the fp8 tile configurations, read from the library's table (native/kernels/gemm_fp8.hip)."""
+    out: dict[int, str] = {}
+    while (name := lib().gsx_gemm_fp8_cfg_name(len(out))) is not None:
+        out[len(out)] = name.decode()
+    return out
+
+
+def gemm_fp8_nt_cfg(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, cfg: int, scale_a: int = 0,
+                    scale_b: int = 0, scale_mode: int = SCALE_NONE):
+    """Launch one configuration of the fp8 GEMM; an unknown config or a shape it cannot take raises HipError."""
+    _ck(lib().gsx_gemm_fp8_nt_launch_cfg(stream.handle, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c),
+                                         m, n, k, ctypes.c_void_p(scale_a), ctypes.c_void_p(scale_b), scale_mode,
+                                         cfg), f"gemm fp8 cfg {cfg}")
+
+
+def time_gemm_fp8(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, iters: int, scale_a: int = 0,
+                  scale_b: int = 0, scale_mode: int = SCALE_NONE) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_gemm_fp8(stream.handle, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c),
+                                      m, n, k, ctypes.c_void_p(scale_a), ctypes.c_void_p(scale_b), scale_mode, iters,
+                                      ctypes.byref(ms)), "time_gemm_fp8")
+    return ms.value

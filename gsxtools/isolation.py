@@ -51,7 +51,8 @@ def pod_envs(n_pods: int, cus_each: int, gpu_total_gib: int, pod_gib: int, with_
     return envs
 
 
-def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str) -> list[dict]:
+def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str,
+             dtype: str = "bf16") -> list[dict]:
     start_at = time.time() + 20.0  # time for every process to import torch and warm up
     procs = []
     sizes = size if isinstance(size, list) else [size] * len(envs)
@@ -68,7 +69,7 @@ def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str
         env["PYTHONPATH"] = str(ROOT) + os.pathsep + env.get("PYTHONPATH", "")
         cmd = [sys.executable, "-m", "gsxtools.workload", "--total",
                e["SHARED_GPU_MEM_DEV"], "--allocated", e["SHARED_GPU_MEM_CONTAINER"], "--kernel", kernel,
-               "--size", str(sz), "--seconds", str(seconds), "--json"]
+               "--size", str(sz), "--seconds", str(seconds), "--dtype", dtype, "--json"]
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                                       cwd=str(ROOT)))
     out = []
@@ -86,7 +87,7 @@ def summarize(name: str, res: list[dict]) -> dict:
             "aggregate_tflops": round(sum(t), 1), "fairness_min_over_max": round(min(t) / max(t), 3) if t else None}
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--pods", type=int, default=4)
     ap.add_argument("--cus", type=int, default=64)
@@ -94,40 +95,45 @@ def main(argv=None) -> int:
     ap.add_argument("--gpu-gib", type=int, default=287)
     ap.add_argument("--seconds", type=float, default=8.0)
     ap.add_argument("--kernel", default="gsx", choices=["gsx", "torch"])
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"], help="the pods' GEMM operand type")
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--small-size", type=int, default=2048)
     ap.add_argument("--scenarios",
                     default="solo,shared,partitioned,env,env-gsx,solo-small,solo64,noisy,noisy-partitioned")
     ap.add_argument("--json-out", default="")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None) -> int:
+    a = build_parser().parse_args(argv)
     results = []
     for sc in a.scenarios.split(","):
         if sc == "solo":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, False)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "none")
+            res = run_pods(envs, a.seconds, a.kernel, a.size, "none", a.dtype)
         elif sc == "shared":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, False)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "none")
+            res = run_pods(envs, a.seconds, a.kernel, a.size, "none", a.dtype)
         elif sc == "partitioned":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, True)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "stream")
+            res = run_pods(envs, a.seconds, a.kernel, a.size, "stream", a.dtype)
         elif sc == "solo64":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, True)
-            res = run_pods(envs, a.seconds, a.kernel, a.small_size, "stream")
+            res = run_pods(envs, a.seconds, a.kernel, a.small_size, "stream", a.dtype)
         elif sc == "solo-small":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, False)
-            res = run_pods(envs, a.seconds, a.kernel, a.small_size, "none")
+            res = run_pods(envs, a.seconds, a.kernel, a.small_size, "none", a.dtype)
         elif sc in ("noisy", "noisy-partitioned"):
             masked = sc == "noisy-partitioned"
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, masked)
             sizes = [a.small_size] + [a.size] * (a.pods - 1)
-            res = run_pods(envs, a.seconds, a.kernel, sizes, "stream" if masked else "none")
+            res = run_pods(envs, a.seconds, a.kernel, sizes, "stream" if masked else "none", a.dtype)
         elif sc == "env":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, True)
-            res = run_pods(envs, a.seconds, "torch" if a.kernel == "gsx" else a.kernel, a.size, "env")
+            res = run_pods(envs, a.seconds, "torch" if a.kernel == "gsx" else a.kernel, a.size, "env", a.dtype)
         elif sc == "env-gsx":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, True)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "env")
+            res = run_pods(envs, a.seconds, a.kernel, a.size, "env", a.dtype)
         else:
             raise SystemExit(f"unknown scenario {sc}")
         s = summarize(sc, res)

@@ -17,6 +17,7 @@ _spec.loader.exec_module(_mod)
 
 run = _mod.run
 main = _mod.main
+build_parser = _mod.build_parser
 parse_mask = _mod.parse_mask
 kernels_lib_path = _mod.kernels_lib_path
 

@@ -11,7 +11,7 @@ Targets (outputs land in ``gpushare_scheduler_extender_amd/_native/``):
                 module also loads on hosts without a GPU and never binds to the
                 ROCm-SMI copy bundled inside the torch wheel).
 * ``kernels`` – HIP/CDNA4 kernels for gfx950 (``libgsx_kernels.so``): CU probe,
-                HBM touch/verify, HBM memory test, compute (MFMA / VALU / LDS) test, bf16 MFMA GEMM workload,
+                HBM touch/verify, HBM memory test, compute (MFMA / VALU / LDS) test, bf16 and fp8 MFMA GEMM workload,
                 CU-masked streams.
 * ``tools``   – standalone HIP executables (``gsx-cuprobe``, ``gsx-memprobe``, ``gsx-memtest``, ``gsx-cutest``).
 * ``isolate`` – ``libgsx_isolate.so``, the HSA tools library that enforces a pod's CU partition and HBM share

@@ -19,6 +19,8 @@
 //                          plugin's compute pre-flight (cutest.hip);
 //  * bf16 MFMA GEMM      — the pod workload used to measure isolation
 //                          (throughput under per-pod CU partitions);
+//  * fp8 MFMA GEMM       — the same workload on OCP e4m3 operands and the K=128
+//                          MFMA, with per-tensor or per-row scales (gemm_fp8.hip);
 //  * CU-masked streams   — hipExtStreamCreateWithCUMask.
 //
 // All functions return 0 or a hipError_t value; gsx_last_error() has text.
@@ -106,6 +108,34 @@ int gsx_gemm_bf16_nt_launch_cfg(void* stream, const void* A, const void* B, void
 // elapsed milliseconds of `iters` back-to-back gsx_gemm_bf16_nt on `stream`, by hip events (for benches)
 int gsx_event_time_gemm(void* stream, const void* A, const void* B, void* C, int M, int N, int K, int iters,
                         float* ms);
+
+// fp8 GEMM (gemm_fp8.hip): C[M][N] (bf16) = A[M][K] * B[N][K]^T with A and B in OCP e4m3 (torch.float8_e4m3fn, not
+// the fnuz encoding), row-major, fp32 accumulate; the same schedules as the bf16 kernels on
+// v_mfma_f32_16x16x128_f8f6f4.  Before the conversion to bf16 the accumulator is scaled by two fp32 multiplies in
+// this order, c = bf16((acc * sa) * sb):
+//   GSX_GEMM_SCALE_NONE    no multiply; scale_a and scale_b are ignored
+//   GSX_GEMM_SCALE_TENSOR  sa = scale_a[0], sb = scale_b[0]
+//   GSX_GEMM_SCALE_ROW     sa = scale_a[row] (M floats), sb = scale_b[col] (N floats)
+// The scales are in device memory, non-NULL and 4-B aligned unless the mode is NONE; A, B and C are 16-B aligned.
+// Launches on `stream` and returns without synchronising; everything is validated before the first device call.
+// K is limited by the 32-bit offsets inside an operand tile: (max(BM, BN) - 1) * K + 112 < 2^31, which is
+// K <= 8421504 for a tile side of 256 and K <= 16909312 for 128 (multiples of 128); a longer K is rejected.
+// gsx_gemm_fp8_nt requires M % 128 == 0, N % 128 == 0, K % 128 == 0 and dispatches like gsx_gemm_bf16_nt: the phased
+// 256x256 kernel when M and N are multiples of 256, the grouped 128x128 tile otherwise.
+enum { GSX_GEMM_SCALE_NONE = 0, GSX_GEMM_SCALE_TENSOR = 1, GSX_GEMM_SCALE_ROW = 2 };
+int gsx_gemm_fp8_nt(void* stream, const void* A, const void* B, void* C, int M, int N, int K, const float* scale_a,
+                    const float* scale_b, int scale_mode);
+// The fp8 configurations, a table of their own in gemm_fp8.hip: 0 "128x128/4w", 1 "256x256/8w-phased-g4" (the
+// dispatched one), 2 "256x256/8w-phased-g4-mfma32" (v_mfma_f32_16x16x32_fp8_fp8, which runs at the bf16 rate: the
+// ablation of the K=128 instruction).  Same conventions as the bf16 table; _launch_cfg requires M % BM == 0,
+// N % BN == 0, K % 128 == 0.
+const char* gsx_gemm_fp8_cfg_name(int cfg);
+int gsx_gemm_fp8_cfg_tile(int cfg, int* bm, int* bn);
+int gsx_gemm_fp8_nt_launch_cfg(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
+                               const float* scale_a, const float* scale_b, int scale_mode, int cfg);
+// elapsed milliseconds of `iters` back-to-back gsx_gemm_fp8_nt on `stream`, by hip events (for benches)
+int gsx_event_time_gemm_fp8(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
+                            const float* scale_a, const float* scale_b, int scale_mode, int iters, float* ms);
 
 // HBM pre-flight memory test (memtest.hip).  The expected content of 16-byte word W = origin/16 + word index is
 // generated from (pattern, seed, invert, W) and never stored; `origin` is the byte offset of `base` in the whole

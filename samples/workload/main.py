@@ -12,7 +12,8 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   process, including torch's own;
 * the compute is the bf16 MFMA GEMM of ``libgsx_kernels.so`` (``--kernel gsx``, found next to this file, at
   ``$GSX_KERNELS_LIB``, or in the repository's build tree) or ``torch.matmul`` / hipBLASLt (``--kernel torch``);
-  ``auto`` (default) takes the MFMA kernel when the library is there and says so when it falls back.
+  ``auto`` (default) takes the MFMA kernel when the library is there and says so when it falls back;
+* ``--dtype fp8`` runs the same loop on OCP e4m3 operands: the library's fp8 GEMM, or ``torch._scaled_mm``.
 """
 from __future__ import annotations
 
@@ -52,6 +53,9 @@ class Kernels:
                            "gsx_stream_sync": [vp], "gsx_gemm_bf16_nt": [vp, vp, vp, vp, i32, i32, i32]}.items():
             f = getattr(L, name)
             f.argtypes, f.restype = args, i32
+        if hasattr(L, "gsx_gemm_fp8_nt"):  # an image built before the fp8 kernels has none; --dtype fp8 says so
+            L.gsx_gemm_fp8_nt.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32]
+            L.gsx_gemm_fp8_nt.restype = i32
         L.gsx_last_error.argtypes, L.gsx_last_error.restype = [], ctypes.c_char_p
         self.L, self.path = L, path
 
@@ -69,6 +73,13 @@ class Kernels:
         self._ck(self.L.gsx_gemm_bf16_nt(s, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m, n, k),
                  "gemm_bf16_nt")
 
+    def gemm_fp8(self, s, a: int, b: int, c: int, m: int, n: int, k: int):
+        """e4m3 operands, no scales (scale_mode 0)."""
+        if not hasattr(self.L, "gsx_gemm_fp8_nt"):
+            raise RuntimeError(f"{self.path} has no gsx_gemm_fp8_nt: rebuild it")
+        self._ck(self.L.gsx_gemm_fp8_nt(s, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m, n, k,
+                                        None, None, 0), "gemm_fp8_nt")
+
     def sync(self, s):
         self._ck(self.L.gsx_stream_sync(s), "stream_sync")
 
@@ -78,7 +89,7 @@ class Kernels:
 
 def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 8192, seconds: float = 0.0,
         iters: int = 0, report_every: float = 5.0, touch: bool = False, quiet: bool = False,
-        probe_limit: bool = False) -> dict:
+        probe_limit: bool = False, dtype: str = "bf16") -> dict:
     import torch
 
     lib_path = kernels_lib_path()
@@ -108,26 +119,39 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         hold = torch.empty(int(allocated * (1 << 30) * 0.9) // 2, dtype=torch.bfloat16, device=dev)
         hold.fill_(1)
     m = n = k = size
+    if dtype not in ("bf16", "fp8"):
+        raise SystemExit(f"--dtype {dtype}: bf16 or fp8")
     a = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
     b = torch.randn(n, k, device=dev, dtype=torch.bfloat16)
     c = torch.empty(m, n, device=dev, dtype=torch.bfloat16)
+    if dtype == "fp8":  # OCP e4m3, the MI355X's format; the output stays bf16
+        a, b = a.to(torch.float8_e4m3fn), b.to(torch.float8_e4m3fn)
+        one = torch.ones((), device=dev, dtype=torch.float32)
     own = None
     if kernel == "gsx":
         gs = hip_stream if hip_stream is not None else kl.stream(0)
         own = None if hip_stream is not None else gs
 
+        gemm = kl.gemm_fp8 if dtype == "fp8" else kl.gemm
+
         def step():
-            kl.gemm(gs, a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k)
+            gemm(gs, a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k)
 
         def sync():
             kl.sync(gs)
     else:
+        def matmul():
+            if dtype == "fp8":  # hipBLASLt's fp8 GEMM, unit per-tensor scales
+                torch._scaled_mm(a, b.t(), scale_a=one, scale_b=one, out_dtype=torch.bfloat16, out=c)
+            else:
+                torch.matmul(a, b.t(), out=c)
+
         def step():
             if stream is not None:
                 with torch.cuda.stream(stream):
-                    torch.matmul(a, b.t(), out=c)
+                    matmul()
             else:
-                torch.matmul(a, b.t(), out=c)
+                matmul()
 
         def sync():
             (stream or torch.cuda.current_stream()).synchronize()
@@ -157,7 +181,7 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
             break
     el = time.perf_counter() - t0
     out = {"tflops": done * flops / el / 1e12, "iters": done, "seconds": el, "fraction": frac,
-           "cu_mask": os.environ.get("GSX_CU_MASK", ""), "kernel": kernel, "size": size,
+           "cu_mask": os.environ.get("GSX_CU_MASK", ""), "kernel": kernel, "dtype": dtype, "size": size,
            "kernels_lib": str(kl.path) if kl is not None else "",
            "visible_devices": os.environ.get("HIP_VISIBLE_DEVICES", ""),
            "device_total_bytes": torch.cuda.get_device_properties(dev).total_memory}
@@ -176,7 +200,7 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     return out
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     p = os.environ.get("GSX_ENV_PREFIX", "SHARED_GPU_MEM")
     ap = argparse.ArgumentParser(description="GEMM loop inside the pod's GPU share (the gpushare sample workload)")
     ap.add_argument("--total", type=float, default=float(os.environ.get(f"{p}_DEV", "0") or 0),
@@ -184,15 +208,21 @@ def main(argv=None) -> int:
     ap.add_argument("--allocated", type=float, default=float(os.environ.get(f"{p}_CONTAINER", "0") or 0),
                     help="this container's share (the device plugin's *_CONTAINER env)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "gsx", "torch"])
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="operand type of the GEMM: bf16, or fp8 (OCP e4m3; the output stays bf16)")
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--seconds", type=float, default=0.0, help="0 = run forever (like the reference sample)")
     ap.add_argument("--iters", type=int, default=0)
     ap.add_argument("--touch", action="store_true")
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--probe-limit", action="store_true", help="check that the memory share is enforced")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None) -> int:
+    a = build_parser().parse_args(argv)
     res = run(a.total, a.allocated, kernel=a.kernel, size=a.size, seconds=a.seconds, iters=a.iters, touch=a.touch,
-              quiet=a.json, probe_limit=a.probe_limit)
+              quiet=a.json, probe_limit=a.probe_limit, dtype=a.dtype)
     print(json.dumps(res) if a.json else res, flush=True)
     return 0
 

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Micro-benchmarks of the HIP kernels on one MI355X: bf16 GEMM (ours vs torch/hipBLASLt), HBM fill, stamp/verify."""
+"""Micro-benchmarks of the HIP kernels on one MI355X: bf16 and fp8 GEMM (ours vs torch/hipBLASLt), HBM fill,
+stamp/verify."""
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -62,6 +64,62 @@ def gemm(size_list, iters=20):
     return out
 
 
+def gemm_fp8(size_list, iters=20, rounds=3):
+    """Every fp8 (e4m3) configuration, the bf16 default on operands of the same shape and ``torch._scaled_mm`` with
+    unit per-tensor scales, interleaved in one process: median TFLOP/s of ``rounds`` repeats, and each fp8 result's
+    max abs error against the fp32 product of the same fp8 operands."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    one = torch.ones((), device="cuda", dtype=torch.float32)
+    for m, n, k in size_list:
+        a16 = torch.rand(m, k, device="cuda", dtype=torch.bfloat16) * 2 - 1
+        b16 = torch.rand(n, k, device="cuda", dtype=torch.bfloat16) * 2 - 1
+        a, b = a16.to(torch.float8_e4m3fn), b16.to(torch.float8_e4m3fn)
+        c = torch.empty(m, n, device="cuda", dtype=torch.bfloat16)
+        ref = a.float() @ b.float().t()
+        torch.cuda.synchronize()  # operands and reference come from torch's stream; the GEMMs run on ours
+        ptrs = (a.data_ptr(), b.data_ptr(), c.data_ptr())
+        variants = {f"cfg{cfg}_{name}": (lambda cfg=cfg: hip.gemm_fp8_nt_cfg(s, *ptrs, m, n, k, cfg))
+                    for cfg, name in hip.gemm_fp8_cfgs().items()}
+        row = {"m": m, "n": n, "k": k}
+        for name, fn in variants.items():
+            c.zero_()
+            torch.cuda.synchronize()
+            fn()
+            s.sync()
+            row[f"{name}_err"] = round((c.float() - ref).abs().max().item(), 4)
+        del ref
+        variants["gsx"] = lambda: hip.gemm_fp8_nt(s, *ptrs, m, n, k)
+        variants["bf16_gsx"] = lambda: hip.gemm_bf16_nt(s, a16.data_ptr(), b16.data_ptr(), c.data_ptr(), m, n, k)
+        variants["torch"] = lambda: torch._scaled_mm(a, b.t(), scale_a=one, scale_b=one, out_dtype=torch.bfloat16,
+                                                     out=c)
+
+        def timed(fn):
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(ts)
+                for _ in range(iters):
+                    fn()
+                e1.record(ts)
+            e1.synchronize()
+            return 2 * m * n * k / (e0.elapsed_time(e1) / iters) / 1e9
+
+        runs = {name: [] for name in variants}
+        for r in range(rounds + 1):  # the first round warms up clocks and code objects
+            for name, fn in variants.items():
+                t = timed(fn)
+                if r:
+                    runs[name].append(t)
+        for name, r in runs.items():
+            row[f"{name}_tflops"] = round(statistics.median(r), 1)
+        out.append(row)
+        del a, b, a16, b16, c
+    s.destroy()
+    return out
+
+
 def hbm(nbytes=16 << 30, reps=5):
     s = hip.Stream(0)
     buf = hip.DeviceBuffer(0, nbytes)
@@ -90,7 +148,8 @@ def hbm(nbytes=16 << 30, reps=5):
 
 if __name__ == "__main__":
     sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (2048, 8192, 4096), (16384, 16384, 8192)]
-    res = {"gemm_bf16_nt": gemm(sizes), "hbm": hbm()}
+    fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
+    res = {"gemm_bf16_nt": gemm(sizes), "gemm_fp8_nt": gemm_fp8(fp8_sizes), "hbm": hbm()}
     print(json.dumps(res))
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as f:
