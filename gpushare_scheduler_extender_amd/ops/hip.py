@@ -57,7 +57,7 @@ class CutestRecord(ctypes.Structure):
 
     @property
     def simd(self) -> int:
-        return (self.hw_id >> 4) & 0x3
+        return decode_hw_id(self.hw_id, self.xcc_id)["simd"]
 
 
 class CutestInject(ctypes.Structure):
@@ -85,7 +85,7 @@ class CutestReport(ctypes.Structure):
 
     def cus(self) -> dict[tuple[int, int, int, int], CutestCu]:
         """``{(xcc, se, sh, cu): entry}`` of the physical CUs that ran a wave."""
-        return {(s >> 8, (s >> 5) & 7, (s >> 4) & 1, s & 15): c for s, c in enumerate(self.cu) if c.waves}
+        return {slot_cu(s): c for s, c in enumerate(self.cu) if c.waves}
 
     def bad_entries(self) -> list[CutestBad]:
         return list(self.bad[:self.n_bad])
@@ -280,6 +280,16 @@ def decode_hw_id(hw: int, xcc: int) -> dict:
     return {"wave": hw & 0xF, "simd": (hw >> 4) & 0x3, "pipe": (hw >> 6) & 0x3, "cu": (hw >> 8) & 0xF,
             "sh": (hw >> 12) & 0x1, "se": (hw >> 13) & 0x7, "tg": (hw >> 16) & 0xF, "vm": (hw >> 20) & 0xF,
             "queue": (hw >> 24) & 0x7, "xcc": xcc & 0xF}
+
+
+def cu_slot(xcc: int, se: int, sh: int, cu: int) -> int:
+    """A physical CU's index in ``CutestReport.cu`` (native/kernels/hwid.h)."""
+    return xcc << 8 | se << 5 | sh << 4 | cu
+
+
+def slot_cu(slot: int) -> tuple[int, int, int, int]:
+    """``(xcc, se, sh, cu)`` of a slot: the inverse of :func:`cu_slot`."""
+    return slot >> 8, (slot >> 5) & 0x7, (slot >> 4) & 0x1, slot & 0xF
 
 
 def physical_cus(records: list[tuple[int, int]]) -> set[tuple[int, int, int, int]]:

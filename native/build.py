@@ -174,17 +174,35 @@ def _hipcc() -> str:
     return str(h) if h.exists() else (shutil.which("hipcc") or "hipcc")
 
 
+KERNELS = NATIVE / "kernels"
+_hip_forced: set[Path] = set()  # what a --force has compiled in this process already
+
+
+def _kernel_sources() -> tuple[list[Path], list[Path], list[Path]]:
+    """The library's sources, the tools' mains and the headers of ``native/kernels``."""
+    srcs = sorted(KERNELS.glob("*.hip"))
+    return ([s for s in srcs if not s.stem.startswith("tool_")], [s for s in srcs if s.stem.startswith("tool_")],
+            sorted(KERNELS.glob("*.h")))
+
+
+def _hip_objs(srcs: list[Path], force: bool, verbose: bool) -> list[Path]:
+    """Objects of ``native/kernels`` sources, the library's and the tools' alike: one set of flags, and a source is
+    compiled once in a build, ``--force`` of several targets included."""
+    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-I" + str(KERNELS),
+             "-munsafe-fp-atomics"]
+    headers = _kernel_sources()[2]
+    again = [s for s in srcs if force and s not in _hip_forced]
+    _compile_objs(again, _hipcc(), flags, "kern", True, verbose, headers)
+    _hip_forced.update(again)
+    return _compile_objs(srcs, _hipcc(), flags, "kern", False, verbose, headers)
+
+
 def build_kernels(force: bool = False, verbose: bool = False) -> Path:
-    src = NATIVE / "kernels"
-    srcs = sorted(src.glob("*.hip"))
-    srcs = [s for s in srcs if not s.stem.startswith("tool_")]
-    headers = sorted(src.glob("*.h"))
+    srcs, _tools, headers = _kernel_sources()
     out = OUT / "libgsx_kernels.so"
     if _current(out, srcs, headers, force):
         return out
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-I" + str(src),
-             "-munsafe-fp-atomics"]
-    objs = _compile_objs(srcs, _hipcc(), flags, "kern", force, verbose, headers)
+    objs = _hip_objs(srcs, force, verbose)
     if force or _newer(out, objs):
         OUT.mkdir(parents=True, exist_ok=True)
         _run([_hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(out), *map(str, objs)], verbose)
@@ -192,19 +210,20 @@ def build_kernels(force: bool = False, verbose: bool = False) -> Path:
 
 
 def build_tools(force: bool = False, verbose: bool = False) -> list[Path]:
-    src = NATIVE / "kernels"
-    outs = []
-    for s in sorted(src.glob("tool_*.hip")):
-        out = OUT / ("gsx-" + s.stem[len("tool_"):])
-        deps = [s, *sorted(src.glob("*.h")), *sorted(src.glob("*.hip"))]
-        if force or _newer(out, deps):
-            OUT.mkdir(parents=True, exist_ok=True)
-            others = [str(x) for x in sorted(src.glob("*.hip")) if not x.stem.startswith("tool_")]
-            _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-I" + str(src), str(s), *others,
-                  "-L" + str(ROCM / "lib"), "-lhsa-runtime64", "-o", str(out)], verbose)
-        outs.append(out)
+    srcs, mains, headers = _kernel_sources()
+    outs = [OUT / ("gsx-" + m.stem[len("tool_"):]) for m in mains]
+    # A tool is its main's object linked with the library's objects.  Which tools are current is settled first
+    # (_current): where all are, no object is asked for.
+    stale = [(m, out) for m, out in zip(mains, outs) if not _current(out, [m, *srcs], headers, force)]
+    if stale:
+        OUT.mkdir(parents=True, exist_ok=True)
+        objs = _hip_objs([*srcs, *(m for m, _ in stale)], force, verbose)
+        lib_objs, main_objs = objs[:len(srcs)], objs[len(srcs):]
+        for main_obj, (_, out) in zip(main_objs, stale):
+            _run([_hipcc(), f"--offload-arch={ARCH}", str(main_obj), *map(str, lib_objs), "-L" + str(ROCM / "lib"),
+                  "-lhsa-runtime64", "-o", str(out)], verbose)
     # the scratch probe's kernels, one code object per private-array size (gsx-memprobe --scratch KIB)
-    probe = src / "probes" / "scratch.hip"
+    probe = KERNELS / "probes" / "scratch.hip"
     for kib, ints in ((1, 256), (4, 1024), (16, 4096), (64, 16384)):
         out = OUT / f"gsx-scratch-{kib}.hsaco"
         if force or _newer(out, [probe]):

@@ -24,6 +24,8 @@
 
 #include "gsx_internal.h"
 #include "gsx_kernels.h"
+#include "hwid.h"
+#include "mix64.h"
 
 using namespace gsx;
 
@@ -38,7 +40,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
 constexpr int kUnitCount = GSX_CUTEST_UNITS;
 constexpr int kMatrixUnits = 7;
 constexpr uint32_t kIntSteps = 256;                  // VALU_INT: steps of a lane's chain
@@ -70,14 +71,7 @@ constexpr uint32_t kSeeds[] = {8, 256};  // by level: QUICK, FULL
 
 // ------------------------------------------------------------------ what the kernel and the host twin share
 
-// splitmix64's output function, as the memory test's generator (ops/memtest.py:_mix64)
-GSX_HD uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-GSX_HD uint64_t seed_key(uint32_t seed) { return (static_cast<uint64_t>(seed) + 1ull) * kGolden; }  // never 0
+// mix64 and seed_key: mix64.h, as the memory test's generator
 
 // A[i][k] (which 0) or B[k][j] (which 1, with j in the place of i) of unit u in round r
 GSX_HD int elem(uint64_t key, uint32_t u, uint32_t r, uint32_t which, uint32_t i, uint32_t k, uint32_t span) {
@@ -106,9 +100,9 @@ GSX_HD void int_chain(uint64_t key, uint32_t lane, uint32_t* xo, uint64_t* yo) {
 }
 GSX_HD uint64_t int_fold(uint32_t x, uint64_t y, uint32_t lane) { return fold(y, lane + 1) + fold(x, lane + 65); }
 
-// LDS: dword d of the memory test's RANDOM words (word d / 4, half (d / 2) & 1 of gen_word in memtest.hip)
+// LDS: dword d of the memory test's RANDOM words (word d / 4, half (d / 2) & 1, as gen_word in memtest.hip)
 GSX_HD uint32_t lds_dword(uint64_t key, uint32_t d, uint32_t inv) {
-  const uint64_t z = mix64(2ull * (d >> 2) + ((d >> 1) & 1u) + key);
+  const uint64_t z = random_half(d >> 2, (d >> 1) & 1u, key);
   return static_cast<uint32_t>(d & 1u ? z >> 32 : z) ^ inv;
 }
 
@@ -319,11 +313,10 @@ __global__ __launch_bounds__(256) void cutest_kernel(gsx_cutest_record* __restri
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint64_t key = seed_key(seed);
-  // the fields as ops/hip.py:decode_hw_id reads them
-  const bool hit = inj.xor_mask != 0 && static_cast<int>(xcc & 0xF) == inj.xcc &&
-                   static_cast<int>((hw >> 13) & 0x7) == inj.se && static_cast<int>((hw >> 12) & 0x1) == inj.sh &&
-                   static_cast<int>((hw >> 8) & 0xF) == inj.cu &&
-                   (inj.simd < 0 || static_cast<int>((hw >> 4) & 0x3) == inj.simd);
+  const HwId at{hw, xcc};
+  const bool hit = inj.xor_mask != 0 && static_cast<int>(at.xcc()) == inj.xcc &&
+                   static_cast<int>(at.se()) == inj.se && static_cast<int>(at.sh()) == inj.sh &&
+                   static_cast<int>(at.cu()) == inj.cu && (inj.simd < 0 || static_cast<int>(at.simd()) == inj.simd);
   const int iu = hit ? inj.unit : -1;
   const uint32_t m = inj.xor_mask;
   uint64_t sig[kUnitCount];
@@ -489,9 +482,9 @@ int gsx_cutest_aggregate(const gsx_cutest_record* records, uint32_t n, gsx_cutes
   if (!rep || (n && !records)) return fail_arg("gsx_cutest_aggregate: no records or no report");
   for (uint32_t w = 0; w < n; ++w) {
     const gsx_cutest_record& r = records[w];
-    const uint32_t xcc = r.xcc_id & 0xF, se = (r.hw_id >> 13) & 0x7, sh = (r.hw_id >> 12) & 0x1,
-                   cu = (r.hw_id >> 8) & 0xF, simd = 1u << ((r.hw_id >> 4) & 0x3);
-    gsx_cutest_cu& c = rep->cu[xcc << 8 | se << 5 | sh << 4 | cu];
+    const HwId at{r.hw_id, r.xcc_id};
+    const uint32_t xcc = at.xcc(), se = at.se(), sh = at.sh(), cu = at.cu(), simd = 1u << at.simd();
+    gsx_cutest_cu& c = rep->cu[cu_slot(at)];
     if (!c.waves) ++rep->cus_seen;
     if (!(c.simds & simd)) {
       ++rep->simds_seen;
@@ -542,10 +535,21 @@ int gsx_cutest_stream_cus(void* stream, uint32_t* cus) {
 }
 
 int gsx_cutest_run(void* stream, int level, uint32_t expect_cus, gsx_cutest_report* rep, double* seconds_out) {
+  bool truncated = false;
+  return cutest_run(stream, level, expect_cus, CutestOpts{}, rep, seconds_out, &truncated);
+}
+
+}  // extern "C"
+
+namespace gsx __attribute__((visibility("hidden"))) {
+
+int cutest_run(void* stream, int level, uint32_t expect_cus, const CutestOpts& opts, gsx_cutest_report* rep,
+               double* seconds, bool* truncated) {
   const uint32_t seeds = gsx_cutest_seeds(level);
   if (!seeds) return fail_arg("gsx_cutest_run: unknown level");
   if (!rep) return fail_arg("gsx_cutest_run: no report");
   const auto t0 = std::chrono::steady_clock::now();
+  const auto since = [t0] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
   if (!expect_cus)
     if (int rc = gsx_cutest_stream_cus(stream, &expect_cus)) return rc;
   const uint64_t want = 4ull * expect_cus;
@@ -555,14 +559,18 @@ int gsx_cutest_run(void* stream, int level, uint32_t expect_cus, gsx_cutest_repo
   // the level's seeds, then further ones while a CU still has a SIMD no wave ran on
   for (uint32_t k = 0; !rc && (k < seeds || (rep->cus_covered < expect_cus && k < seeds + GSX_CUTEST_EXTRA_LAUNCHES));
        ++k) {
-    rc = gsx_cutest_launch(stream, k, blocks, nullptr, recs.data(), static_cast<uint32_t>(recs.size()));
+    if (opts.max_seconds > 0 && since() >= opts.max_seconds) {
+      *truncated = true;
+      break;
+    }
+    rc = gsx_cutest_launch(stream, k, blocks, opts.inject, recs.data(), static_cast<uint32_t>(recs.size()));
     if (!rc) rc = gsx_cutest_aggregate(recs.data(), static_cast<uint32_t>(recs.size()), rep);
     if (!rc) ++rep->launches;
   }
   rep->cus_expected = expect_cus;
   rep->covered = rep->cus_covered >= expect_cus;
-  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (seconds) *seconds = since();
   return rc;
 }
 
-}  // extern "C"
+}  // namespace gsx

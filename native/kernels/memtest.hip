@@ -14,6 +14,7 @@
 
 #include "gsx_internal.h"
 #include "gsx_kernels.h"
+#include "mix64.h"
 
 using namespace gsx;
 
@@ -39,13 +40,6 @@ struct LaunchReport {
 static_assert(sizeof(gsx_memtest_err) == 16 && sizeof(WaveHead) == 16, "a record or a header is one 16-B store");
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// splitmix64's output function on a counter: z = ctr + key, then two multiply-xorshift rounds (bijective)
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 template <int PAT>
 __device__ __forceinline__ uint4 gen_word(uint64_t W, uint32_t seed, uint64_t key, uint32_t inv) {
   uint4 v;
@@ -58,7 +52,7 @@ __device__ __forceinline__ uint4 gen_word(uint64_t W, uint32_t seed, uint64_t ke
     const uint32_t b = 4u * lo + seed;  // only its low five bits matter
     v = make_uint4(1u << (b & 31u), 1u << ((b + 1u) & 31u), 1u << ((b + 2u) & 31u), 1u << ((b + 3u) & 31u));
   } else {
-    const uint64_t a = mix64(2ull * W + key), c = mix64(2ull * W + 1ull + key);
+    const uint64_t a = random_half(W, 0, key), c = random_half(W, 1, key);
     v = make_uint4(static_cast<uint32_t>(a), static_cast<uint32_t>(a >> 32), static_cast<uint32_t>(c),
                    static_cast<uint32_t>(c >> 32));
   }
@@ -163,7 +157,7 @@ __device__ __forceinline__ void sweep_step(uint4* __restrict__ p, uint64_t i, ui
 template <int PAT, int MODE>
 __global__ __launch_bounds__(256) void memtest_kernel(uint4* __restrict__ p, uint64_t n16, uint64_t W0, uint32_t seed,
                                                       uint32_t inv, LaunchReport rep) {
-  const uint64_t key = (static_cast<uint64_t>(seed) + 1ull) * 0x9E3779B97F4A7C15ull;  // never 0: mix64(0) is 0
+  const uint64_t key = seed_key(seed);
   uint64_t i = blockIdx.x * 256ull + threadIdx.x;
   const uint64_t step = gridDim.x * 256ull;
   Tally t;
@@ -338,20 +332,55 @@ int gsx_memtest_pass(int level, uint32_t idx, gsx_memtest_pass_t* out) {
 
 int gsx_memtest_run(void* stream, void* base, uint64_t bytes, uint64_t origin, int level, gsx_memtest_report* report,
                     uint32_t* passes_out, double* seconds_out) {
-  if (level != GSX_MEMTEST_QUICK && level != GSX_MEMTEST_FULL) return fail_arg("gsx_memtest_run: unknown level");
-  if (!report) return fail_arg("gsx_memtest_run: no report");
   uint32_t passes = 0;
+  uint64_t moved = 0;
+  bool truncated = false;
   const auto t0 = std::chrono::steady_clock::now();
-  int rc = 0;
-  gsx_memtest_pass_t ps;
-  while (!rc && gsx_memtest_pass(level, passes, &ps) == 0) {
-    rc = ps.write ? gsx_memtest_write(stream, base, bytes, origin, ps.pattern, ps.seed, ps.invert)
-                  : gsx_memtest_check(stream, base, bytes, origin, ps.pattern, ps.seed, ps.invert, ps.rewrite, report);
-    if (!rc) ++passes;
-  }
+  const int rc = memtest_run(stream, base, bytes, origin, level, MemtestOpts{}, report, &passes, &moved, &truncated);
   if (passes_out) *passes_out = passes;
   if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
 
 }  // extern "C"
+
+namespace gsx __attribute__((visibility("hidden"))) {
+
+int memtest_run(void* stream, void* base, uint64_t bytes, uint64_t origin, int level, const MemtestOpts& opts,
+                gsx_memtest_report* report, uint32_t* passes, uint64_t* bytes_moved, bool* truncated) {
+  if (level != GSX_MEMTEST_QUICK && level != GSX_MEMTEST_FULL) return fail_arg("gsx_memtest_run: unknown level");
+  if (!report) return fail_arg("gsx_memtest_run: no report");
+  if (opts.flip_mask && (opts.flip_offset % 4 || opts.flip_offset >= bytes))
+    return fail_arg("gsx_memtest_run: the dword to flip is outside the range");
+  uint32_t flip = opts.flip_mask;
+  gsx_memtest_pass_t ps;
+  for (uint32_t k = 0; gsx_memtest_pass(level, k, &ps) == 0; ++k) {
+    if (opts.deadline && std::chrono::steady_clock::now() >= *opts.deadline) {
+      *truncated = true;
+      break;
+    }
+    int rc;
+    if (ps.write) {
+      rc = gsx_memtest_write(stream, base, bytes, origin, ps.pattern, ps.seed, ps.invert);
+      if (!rc && flip) {
+        // one dword of the caller's own buffer, flipped through the host: a data mismatch for the check to find
+        uint32_t w = 0;
+        char* at = static_cast<char*>(base) + opts.flip_offset;
+        if (hipStreamSynchronize(S(stream)) != hipSuccess || hipMemcpy(&w, at, 4, hipMemcpyDeviceToHost) != hipSuccess)
+          return fail_arg("--inject: reading the dword failed");
+        w ^= flip;
+        flip = 0;
+        if (hipMemcpy(at, &w, 4, hipMemcpyHostToDevice) != hipSuccess)
+          return fail_arg("--inject: writing the dword failed");
+      }
+    } else {
+      rc = gsx_memtest_check(stream, base, bytes, origin, ps.pattern, ps.seed, ps.invert, ps.rewrite, report);
+    }
+    if (rc) return rc;
+    ++*passes;
+    *bytes_moved += bytes * (ps.rewrite ? 2 : 1);
+  }
+  return 0;
+}
+
+}  // namespace gsx

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "gsx_kernels.h"
+#include "hwid.h"
 
 static std::vector<uint32_t> parse_mask(const char* s, int cus) {
   std::vector<uint32_t> w(static_cast<size_t>((cus + 31) / 32), 0u);
@@ -72,13 +73,12 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "probe: %s\n", gsx_last_error());
     return 1;
   }
-  std::set<std::tuple<int, int, int, int>> cus;
-  std::vector<std::set<std::tuple<int, int, int>>> per_xcc(16);
+  std::set<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>> cus;
+  std::vector<std::set<std::tuple<uint32_t, uint32_t, uint32_t>>> per_xcc(16);
   for (int b = 0; b < blocks; ++b) {
-    uint32_t hw = rec[static_cast<size_t>(2 * b)], xcc = rec[static_cast<size_t>(2 * b + 1)] & 0xF;
-    int cu = (hw >> 8) & 0xF, sh = (hw >> 12) & 1, se = (hw >> 13) & 7;
-    cus.insert(std::make_tuple(static_cast<int>(xcc), se, sh, cu));
-    per_xcc[xcc].insert(std::make_tuple(se, sh, cu));
+    const gsx::HwId at{rec[static_cast<size_t>(2 * b)], rec[static_cast<size_t>(2 * b + 1)]};
+    cus.insert(std::make_tuple(at.xcc(), at.se(), at.sh(), at.cu()));
+    per_xcc[at.xcc()].insert(std::make_tuple(at.se(), at.sh(), at.cu()));
   }
   std::printf("{\"device\":%d,\"arch\":\"%s\",\"cu_count\":%d,\"mask\":\"%s\",\"hsa_cu_mask\":\"%s\",\"distinct_cus\":%zu,"
               "\"per_xcd\":[",
@@ -90,7 +90,7 @@ int main(int argc, char** argv) {
     std::printf(",\"cus\":[");
     bool first = true;
     for (const auto& t : cus) {
-      std::printf("%s[%d,%d,%d,%d]", first ? "" : ",", std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t));
+      std::printf("%s[%u,%u,%u,%u]", first ? "" : ",", std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t));
       first = false;
     }
     std::printf("]");

@@ -7,7 +7,7 @@
 // device, or on a stream restricted to --cu-mask (32-bit words, as hipExtStreamCreateWithCUMask takes them), and
 // attributes every wave's answers to the physical CU and SIMD it ran on.  While fewer CUs than expected have had all
 // four SIMDs run a wave, up to GSX_CUTEST_EXTRA_LAUNCHES more launches follow.  Expected CUs: --expect-cus, else the
-// popcount of --cu-mask, else the device's CU count.
+// popcount of --cu-mask, else the device's CU count.  The loop is gsx::cutest_run, the one gsx_cutest_run has.
 // --max-seconds is consulted between launches: the run ends early with "truncated": true, which is no failure.
 // --inject (for tests) makes the waves on one physical CU (or one SIMD of it) flip bits of one result value of one
 // unit (a name of the table in gsx_kernels.h, or its number).
@@ -16,28 +16,22 @@
 // rejected before any HIP call; no such device), or --expect-cus was given and coverage stayed short.
 #include <hip/hip_runtime.h>
 
-#include <cerrno>
-#include <chrono>
 #include <cinttypes>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
+#include "gsx_internal.h"
 #include "gsx_kernels.h"
+#include "tool_common.h"
 
 namespace {
 
-struct Args {
-  int device = 0;
-  std::string bdf;
-  int level = GSX_CUTEST_QUICK;
-  std::string level_name = "quick";
+using tool::parse_u64;
+using tool::split;
+static_assert(GSX_CUTEST_QUICK == 0 && GSX_CUTEST_FULL == 1, "tool::Common::level is the compute test's level");
+
+struct Args : tool::Common {
   std::vector<uint32_t> mask;
   uint32_t expect = 0;
   bool have_expect = false;
-  double max_seconds = 0;
   bool inject = false;
   gsx_cutest_inject inj{};
 };
@@ -49,28 +43,6 @@ struct Result {
   bool truncated = false;
   gsx_cutest_report rep;
 };
-
-bool parse_u64(const char* s, uint64_t* out) {
-  if (!*s || *s == '-') return false;
-  char* end = nullptr;
-  errno = 0;
-  const unsigned long long v = std::strtoull(s, &end, 0);
-  if (errno || !end || *end) return false;
-  *out = v;
-  return true;
-}
-
-std::vector<std::string> split(const char* s, char sep) {
-  std::vector<std::string> out(1);
-  for (; *s; ++s) {
-    if (*s == sep) {
-      out.emplace_back();
-    } else {
-      out.back() += *s;
-    }
-  }
-  return out;
-}
 
 std::string unit_names(uint32_t mask) {
   std::string s;
@@ -100,15 +72,6 @@ int emit(const Args& a, const Result& r, const char* error, int rc) {
     bad += buf;
   }
   for (const gsx_cutest_cu& c : r.rep.cu) failed |= c.fail_mask;
-  std::string err = "null";
-  if (error) {
-    err = "\"";
-    for (const char* c = error; *c; ++c) {
-      if (*c == '"' || *c == '\\') err += '\\';
-      err += static_cast<unsigned char>(*c) < 0x20 ? ' ' : *c;
-    }
-    err += "\"";
-  }
   std::printf("{\"device\":%d,\"bdf\":\"%s\",\"level\":\"%s\",\"launches\":%u,\"seconds\":%.6f,\"cus_seen\":%u,"
               "\"simds_seen\":%u,\"cus_covered\":%u,\"cus_expected\":%u,\"covered\":%s,\"waves\":%" PRIu64
               ",\"bad_waves\":%" PRIu64 ",\"bad_cu_count\":%u,\"bad_cus\":[%s],\"units_failed\":[%s],"
@@ -116,32 +79,20 @@ int emit(const Args& a, const Result& r, const char* error, int rc) {
               r.device, r.bdf.c_str(), a.level_name.c_str(), r.rep.launches, r.seconds, r.rep.cus_seen,
               r.rep.simds_seen, r.rep.cus_covered, r.rep.cus_expected, r.rep.covered ? "true" : "false",
               static_cast<uint64_t>(r.rep.waves), static_cast<uint64_t>(r.rep.bad_waves), r.rep.bad_cus, bad.c_str(),
-              unit_names(failed).c_str(), r.truncated ? "true" : "false", err.c_str());
+              unit_names(failed).c_str(), r.truncated ? "true" : "false", tool::json_string(error).c_str());
   std::fflush(stdout);
   return rc;
 }
 
 // nullptr, or what is wrong with the command line
 const char* parse(int argc, char** argv, Args* a) {
-  bool have_dev = false;
-  for (int i = 1; i < argc; ++i) {
+  for (int i = 1; i < argc; i += 2) {
     const char* k = argv[i];
     const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
+    const char* why = nullptr;
     uint64_t u = 0;
-    if (!std::strcmp(k, "--device")) {
-      if (!v || !parse_u64(v, &u) || u > 1023) return "--device needs an index";
-      a->device = static_cast<int>(u);
-      have_dev = true;
-    } else if (!std::strcmp(k, "--bdf")) {
-      if (!v || !*v) return "--bdf needs DDDD:BB:DD.F";
-      unsigned d, b, dv, f;
-      char tail;
-      if (std::sscanf(v, "%x:%x:%x.%x%c", &d, &b, &dv, &f, &tail) != 4) return "--bdf needs DDDD:BB:DD.F";
-      a->bdf = v;
-    } else if (!std::strcmp(k, "--level")) {
-      if (!v || (std::strcmp(v, "quick") && std::strcmp(v, "full"))) return "--level needs quick or full";
-      a->level_name = v;
-      a->level = !std::strcmp(v, "full") ? GSX_CUTEST_FULL : GSX_CUTEST_QUICK;
+    if (tool::parse_common(k, v, a, &why)) {
+      if (why) return why;
     } else if (!std::strcmp(k, "--cu-mask")) {
       if (!v || !*v) return "--cu-mask needs 32-bit words W0,W1,...";
       uint32_t bits = 0;
@@ -156,46 +107,36 @@ const char* parse(int argc, char** argv, Args* a) {
       if (!v || !parse_u64(v, &u) || u == 0 || u > GSX_CUTEST_CU_SLOTS) return "--expect-cus needs a CU count";
       a->expect = static_cast<uint32_t>(u);
       a->have_expect = true;
-    } else if (!std::strcmp(k, "--max-seconds")) {
-      char* end = nullptr;
-      a->max_seconds = v ? std::strtod(v, &end) : -1;
-      if (!v || !*v || *end || !(a->max_seconds >= 0)) return "--max-seconds needs a number of seconds";
     } else if (!std::strcmp(k, "--inject")) {
-      static const char* why = "--inject needs XCC:SE:SH:CU[:SIMD]:UNIT:XORMASK (a unit's name or number, a non-zero "
+      static const char* bad = "--inject needs XCC:SE:SH:CU[:SIMD]:UNIT:XORMASK (a unit's name or number, a non-zero "
                                "32-bit mask)";
-      if (!v) return why;
+      if (!v) return bad;
       const std::vector<std::string> f = split(v, ':');
-      if (f.size() != 6 && f.size() != 7) return why;
+      if (f.size() != 6 && f.size() != 7) return bad;
       uint64_t n[4];
       static const uint64_t lim[4] = {15, 7, 1, 15};
       for (int j = 0; j < 4; ++j)
-        if (!parse_u64(f[j].c_str(), &n[j]) || n[j] > lim[j]) return why;
+        if (!parse_u64(f[j].c_str(), &n[j]) || n[j] > lim[j]) return bad;
       a->inj.xcc = static_cast<int>(n[0]), a->inj.se = static_cast<int>(n[1]);
       a->inj.sh = static_cast<int>(n[2]), a->inj.cu = static_cast<int>(n[3]);
       a->inj.simd = -1;
       if (f.size() == 7) {
-        if (!parse_u64(f[4].c_str(), &u) || u > 3) return why;
+        if (!parse_u64(f[4].c_str(), &u) || u > 3) return bad;
         a->inj.simd = static_cast<int>(u);
       }
       const std::string& unit = f[f.size() - 2];
       a->inj.unit = -1;
       for (int j = 0; j < GSX_CUTEST_UNITS; ++j)
         if (unit == gsx_cutest_unit_name(j) || unit == std::to_string(j)) a->inj.unit = j;
-      if (a->inj.unit < 0) return why;
-      if (!parse_u64(f.back().c_str(), &u) || u == 0 || u > 0xFFFFFFFFull) return why;
+      if (a->inj.unit < 0) return bad;
+      if (!parse_u64(f.back().c_str(), &u) || u == 0 || u > 0xFFFFFFFFull) return bad;
       a->inj.xor_mask = static_cast<uint32_t>(u);
       a->inject = true;
     } else {
       return "unknown argument (see the head of tool_cutest.hip)";
     }
-    ++i;
   }
-  if (have_dev && !a->bdf.empty()) return "--device and --bdf exclude each other";
-  return nullptr;
-}
-
-double since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return tool::check_common(*a);
 }
 
 }  // namespace
@@ -206,46 +147,18 @@ int main(int argc, char** argv) {
   std::memset(&r.rep, 0, sizeof r.rep);
   if (const char* why = parse(argc, argv, &a)) return emit(a, r, why, 2);
   // from here on the device is touched
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return emit(a, r, "no HIP device", 2);
-  int dev = a.device;
-  if (!a.bdf.empty() && hipDeviceGetByPCIBusId(&dev, a.bdf.c_str()) != hipSuccess)
-    return emit(a, r, "no device with this --bdf", 2);
-  if (dev < 0 || dev >= ndev || hipSetDevice(dev) != hipSuccess) return emit(a, r, "no such device", 2);
-  r.device = dev;
-  char bdf[32] = "";
-  if (hipDeviceGetPCIBusId(bdf, sizeof bdf, dev) == hipSuccess) r.bdf = bdf;
+  if (const char* why = tool::open_target(a, &r.device, &r.bdf)) return emit(a, r, why, 2);
   void* st = nullptr;
-  if (gsx_stream_create(dev, a.mask.empty() ? nullptr : a.mask.data(), static_cast<int>(a.mask.size()), &st))
+  if (gsx_stream_create(r.device, a.mask.empty() ? nullptr : a.mask.data(), static_cast<int>(a.mask.size()), &st))
     return emit(a, r, gsx_last_error(), 2);
-  uint32_t expect = a.expect;
-  if (!expect && gsx_cutest_stream_cus(st, &expect)) {
-    (void)gsx_stream_destroy(st);
-    return emit(a, r, gsx_last_error(), 2);
-  }
-  r.rep.cus_expected = expect;
-  const uint32_t want = 4u * expect;
-  const int blocks = static_cast<int>(want < GSX_CUTEST_MAX_BLOCKS ? want : GSX_CUTEST_MAX_BLOCKS);
-  std::vector<gsx_cutest_record> recs(4u * static_cast<size_t>(blocks));
-  const uint32_t seeds = gsx_cutest_seeds(a.level);
-  const auto t0 = std::chrono::steady_clock::now();
+  // --max-seconds counts from here, the start of the run, when the device is open and the stream made.  The device
+  // plugin passes 0.8 of the time it gives the process, as if the budget counted from the start of the process,
+  // which gsx-memtest's does and this one does not.
+  gsx::CutestOpts opts;
+  opts.inject = a.inject ? &a.inj : nullptr;
+  opts.max_seconds = a.max_seconds;
   const char* error = nullptr;
-  // gsx_cutest_run's loop, with the clock looked at between launches and the injection passed on
-  for (uint32_t k = 0; k < seeds || (r.rep.cus_covered < expect && k < seeds + GSX_CUTEST_EXTRA_LAUNCHES); ++k) {
-    if (a.max_seconds > 0 && since(t0) >= a.max_seconds) {
-      r.truncated = true;
-      break;
-    }
-    const uint32_t n = static_cast<uint32_t>(recs.size());
-    if (gsx_cutest_launch(st, k, blocks, a.inject ? &a.inj : nullptr, recs.data(), n) ||
-        gsx_cutest_aggregate(recs.data(), n, &r.rep)) {
-      error = gsx_last_error();
-      break;
-    }
-    ++r.rep.launches;
-  }
-  r.rep.covered = r.rep.cus_covered >= expect;
-  r.seconds = since(t0);
+  if (gsx::cutest_run(st, a.level, a.expect, opts, &r.rep, &r.seconds, &r.truncated)) error = gsx_last_error();
   (void)gsx_stream_destroy(st);
   if (error) return emit(a, r, error, 2);
   if (r.rep.bad_waves) return emit(a, r, nullptr, 1);

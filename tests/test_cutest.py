@@ -182,6 +182,28 @@ def test_aggregate_attributes_by_physical_cu_and_simd(hip):
     assert (rep.waves, rep.bad_waves, rep.bad_cus, rep.n_bad, rep.simds_seen) == (10, 3, 1, 1, 8)
     assert rep.bad_entries()[0].simds == 0x5 and rep.bad_entries()[0].units == 1 | 1 << 4 | 1 << 8
     assert rep.bad_entries()[0].unit == 4  # the first bad unit of the first bad wave
+    # the decode and the slot, exhaustively: every (xcc, se, sh, cu) there is a slot for, on every SIMD
+    where = [(x, se, sh, cu, simd) for x in range(16) for se in range(8) for sh in range(2) for cu in range(16)
+             for simd in range(4)]
+    arr = (hip.CutestRecord * len(where))()
+    for r, (x, se, sh, cu, simd) in zip(arr, where):
+        r.hw_id, r.xcc_id, r.seed = simd << 4 | cu << 8 | sh << 12 | se << 13 | 0xB, x, 7  # wave bits set
+        assert (*r.where(), r.simd) == (x, se, sh, cu, simd)
+    for fail in (0, 1 << 4):
+        for r in arr:
+            r.fail_mask = fail
+        rep = hip.cutest_aggregate(arr)
+        cus = rep.cus()
+        assert len(cus) == ct.CU_SLOTS == 4096 and set(cus) == {w[:4] for w in where}
+        assert all(c.simds == 0xF and c.waves == 4 for c in cus.values())
+        assert (rep.waves, rep.cus_seen, rep.simds_seen, rep.cus_covered) == (16384, 4096, 16384, 4096)
+        assert all(hip.slot_cu(hip.cu_slot(*w)) == w and rep.cu[hip.cu_slot(*w)].waves == 4 for w in cus)
+        if fail:
+            assert (rep.bad_cus, rep.n_bad, rep.bad_waves) == (4096, 16, 16384)
+            assert [(b.xcc, b.se, b.sh, b.cu) for b in rep.bad_entries()] == [w[:4] for w in where[:64:4]]
+            assert all(c.bad_simds == 0xF and c.fail_mask == fail for c in cus.values())
+        else:
+            assert (rep.bad_cus, rep.n_bad, rep.bad_waves) == (0, 0, 0)
 
 
 def test_aggregate_caps_the_entries_and_keeps_the_counts(hip):
@@ -214,14 +236,28 @@ def test_tool_rejects_bad_arguments_before_any_device_call():
     tool = ROOT / "gpushare_scheduler_extender_amd" / "_native" / "gsx-cutest"
     # no device may be opened: with every GPU hidden a device call would fail with another message
     env = {**os.environ, "HIP_VISIBLE_DEVICES": "", "ROCR_VISIBLE_DEVICES": ""}
-    for argv, word in ((["--level", "bogus"], "--level"), (["--cu-mask", "0,0"], "--cu-mask"),
-                       (["--cu-mask", "0x1ffffffff"], "--cu-mask"), (["--expect-cus", "0"], "--expect-cus"),
-                       (["--max-seconds", "-1"], "--max-seconds"), (["--inject", "0:0:0:0:LDS"], "--inject"),
-                       (["--inject", "0:0:0:0:NOSUCH:1"], "--inject"), (["--inject", "0:0:0:0:4:LDS:1"], "--inject"),
-                       (["--inject", "0:0:0:0:LDS:0"], "--inject"), (["--inject", "0:9:0:0:LDS:1"], "--inject"),
-                       (["--device", "0", "--bdf", "0000:05:00.0"], "exclude"), (["--frobnicate"], "unknown")):
+    # the whole line, as the tool printed it before its frame was shared with gsx-memtest (seconds is 0 on these paths)
+    line = ('{{"device":-1,"bdf":"","level":"{level}","launches":0,"seconds":0.000000,"cus_seen":0,"simds_seen":0,'
+            '"cus_covered":0,"cus_expected":0,"covered":false,"waves":0,"bad_waves":0,"bad_cu_count":0,"bad_cus":[],'
+            '"units_failed":[],"truncated":false,"error":"{error}"}}\n')
+    words = "--cu-mask needs 32-bit words W0,W1,..."
+    inject = "--inject needs XCC:SE:SH:CU[:SIMD]:UNIT:XORMASK (a unit's name or number, a non-zero 32-bit mask)"
+    for argv, word, error in ((["--level", "bogus"], "--level", "--level needs quick or full"),
+                              (["--cu-mask", "0,0"], "--cu-mask", "--cu-mask needs at least one CU"),
+                              (["--cu-mask", "0x1ffffffff"], "--cu-mask", words),
+                              (["--expect-cus", "0"], "--expect-cus", "--expect-cus needs a CU count"),
+                              (["--max-seconds", "-1"], "--max-seconds", "--max-seconds needs a number of seconds"),
+                              (["--inject", "0:0:0:0:LDS"], "--inject", inject),
+                              (["--inject", "0:0:0:0:NOSUCH:1"], "--inject", inject),
+                              (["--inject", "0:0:0:0:4:LDS:1"], "--inject", inject),
+                              (["--inject", "0:0:0:0:LDS:0"], "--inject", inject),
+                              (["--inject", "0:9:0:0:LDS:1"], "--inject", inject),
+                              (["--device", "0", "--bdf", "0000:05:00.0"], "exclude",
+                               "--device and --bdf exclude each other"),
+                              (["--frobnicate"], "unknown", "unknown argument (see the head of tool_cutest.hip)")):
         r = subprocess.run([str(tool), *argv], capture_output=True, text=True, timeout=60, env=env)
         assert r.returncode == 2, (argv, r.returncode, r.stdout, r.stderr)
+        assert r.stdout == line.format(level="quick", error=error), (argv, r.stdout)
         out = json.loads(r.stdout.strip().splitlines()[-1])
         assert word in out["error"] and out["device"] == -1 and out["waves"] == 0, (argv, out)
         assert set(out) >= {"device", "bdf", "level", "launches", "seconds", "cus_seen", "cus_expected", "covered",
@@ -232,6 +268,10 @@ def test_tool_rejects_bad_arguments_before_any_device_call():
                        capture_output=True, text=True, timeout=60, env=env)
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert r.returncode == 2 and out["error"] == "no HIP device" and out["device"] == -1
+    assert r.stdout == line.format(level="quick", error="no HIP device")
+    r = subprocess.run([str(tool), "--bdf", "0000:05:00.0", "--level", "full", "--expect-cus", "256",
+                        "--max-seconds", "2.5"], capture_output=True, text=True, timeout=60, env=env)
+    assert r.returncode == 2 and r.stdout == line.format(level="full", error="no HIP device")
 
 
 # ------------------------------------------------------------------ the plugin's compute pre-flight

@@ -143,6 +143,38 @@ def test_tool_clean_run(hip):
     assert out["cus_seen"] == out["cus_expected"] == hip.device_info(0)["cu_count"] and out["launches"] >= 8
 
 
+def test_tool_truncated_before_its_first_launch():
+    rc, out = _tool("--device", "0", "--max-seconds", "0.000001")
+    assert rc == 0 and out["error"] is None, out
+    assert out["truncated"] is True and out["launches"] == 0 and out["covered"] is False and out["waves"] == 0
+
+
+MASK64 = "0xffffffff,0xffffffff"
+
+
+def test_tool_on_a_masked_stream_expects_the_mask():
+    rc, out = _tool("--device", "0", "--cu-mask", MASK64)
+    assert rc == 0 and out["error"] is None and out["covered"] is True and not out["truncated"], out
+    assert out["cus_expected"] == out["cus_seen"] == out["cus_covered"] == 64 and out["bad_waves"] == 0
+    assert 8 <= out["launches"] <= 16
+
+
+def test_tool_whose_coverage_stays_short_uses_every_extra_launch(hip):
+    rc, out = _tool("--device", "0", "--cu-mask", MASK64, "--expect-cus", str(hip.device_info(0)["cu_count"]))
+    assert rc == 2 and "--expect-cus" in out["error"], out
+    assert out["covered"] is False and not out["truncated"] and out["bad_waves"] == 0
+    assert out["launches"] == ct.SEEDS["quick"] + ct.EXTRA_LAUNCHES == 16
+
+
+def test_tool_and_library_run_the_same_loop(hip, clean):
+    cu_count = hip.device_info(0)["cu_count"]
+    rc, out = _tool("--device", "0")
+    assert rc == 0 and out["error"] is None and not out["truncated"], out
+    run, _seconds = hip.cutest_run(clean[0], "quick")
+    assert out["waves"] == 16 * cu_count * out["launches"] and run.waves == 16 * cu_count * run.launches
+    assert out["cus_covered"] == run.cus_covered
+
+
 def test_tool_names_the_injected_cu(clean):
     xcc, se, sh, cu = _targets(clean)[0]
     rc, out = _tool("--device", "0", "--inject", f"{xcc}:{se}:{sh}:{cu}:LDS:0x80")

@@ -411,6 +411,19 @@ def test_tool_truncated_before_its_first_pass(hip):
     assert out["chunks"] == 0 and out["bytes_moved"] == 0 and out["bad_dwords"] == 0 and out["errors"] == []
 
 
+def test_tool_and_library_run_the_same_passes_over_one_range(hip, stream):
+    n = 32 << 20
+    rc, out = run_tool("--device", "0", "--bytes", str(n), "--level", "quick")
+    assert rc == 0 and out["error"] is None and not out["truncated"], out
+    b = hip.DeviceBuffer(0, n)
+    try:
+        rep, passes, _seconds = hip.memtest_run(stream, b.addr(0), n, 0, level="quick")
+    finally:
+        b.free()
+    assert out["passes"] == passes == 6 and out["bytes_moved"] == 8 * n
+    assert (out["chunks"], out["bytes_tested"], out["bad_dwords"], rep.bad_dwords) == (1, n, 0, 0)
+
+
 def test_tool_with_a_reserve_beyond_the_device(hip):
     _free, total = hip.mem_info(0)
     rc, out = run_tool("--device", "0", "--bytes", "all", "--reserve", str(total + (1 << 30)))

@@ -135,11 +135,26 @@ def test_tool_rejects_bad_arguments_before_any_device_call():
     tool = ROOT / "gpushare_scheduler_extender_amd" / "_native" / "gsx-memtest"
     # no device may be opened: with every GPU hidden a device call would fail with another message
     env = {**os.environ, "HIP_VISIBLE_DEVICES": "", "ROCR_VISIBLE_DEVICES": ""}
-    for argv, word in ((["--level", "bogus"], "--level"), (["--chunk", "4096"], "--chunk"),
-                       (["--bytes", "100"], "--bytes"), (["--inject", "4096"], "--inject"),
-                       (["--device", "0", "--bdf", "0000:05:00.0"], "exclude"), (["--frobnicate"], "unknown")):
+    # the whole line, as the tool printed it before its frame was shared with gsx-cutest (seconds is 0 on these paths)
+    line = ('{{"device":-1,"bdf":"","level":"{level}","bytes_tested":0,"bytes_moved":0,"passes":0,"chunks":0,'
+            '"seconds":0.000000,"gbps":0.0,"bad_dwords":0,"flipped_or":0,"errors":[],"truncated":false,'
+            '"error":"{error}"}}\n')
+    for argv, word, level, error in (
+            (["--level", "bogus"], "--level", "quick", "--level needs quick or full"),
+            (["--chunk", "4096"], "--chunk", "quick", "--chunk needs a multiple of 16 of at least 1 GiB"),
+            (["--bytes", "100"], "--bytes", "quick", "--bytes needs a positive multiple of 16, or all"),
+            (["--inject", "4096"], "--inject", "quick",
+             "--inject needs OFFSET:XORMASK (a dword offset, a non-zero 32-bit mask)"),
+            (["--device", "0", "--bdf", "0000:05:00.0"], "exclude", "quick", "--device and --bdf exclude each other"),
+            (["--frobnicate"], "unknown", "quick", "unknown argument (see the head of tool_memtest.hip)"),
+            # good arguments get as far as the device, and there is none
+            (["--bdf", "0000:05:00.0", "--bytes", "33554432", "--level", "full", "--max-seconds", "2.5"], "no HIP",
+             "full", "no HIP device"),
+            (["--device", "1", "--reserve", "0x40000000", "--chunk", "2147483648", "--inject", "4096:0x10"], "no HIP",
+             "quick", "no HIP device")):
         r = subprocess.run([str(tool), *argv], capture_output=True, text=True, timeout=60, env=env)
         assert r.returncode == 2, (argv, r.returncode, r.stdout, r.stderr)
+        assert r.stdout == line.format(level=level, error=error), (argv, r.stdout)
         out = json.loads(r.stdout.strip().splitlines()[-1])
         assert word in out["error"] and out["device"] == -1 and out["bytes_tested"] == 0, (argv, out)
         assert set(out) >= {"device", "bdf", "level", "bytes_tested", "bytes_moved", "passes", "seconds", "gbps",
