@@ -141,6 +141,13 @@ def lib():
             "gsx_gemm_fp8_cfg_name": ([i32], ctypes.c_char_p),
             "gsx_event_time_gemm_fp8": ([vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32,
                                          ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_gemm_mxfp4_nt": ([vp, vp, vp, vp, i32, i32, i32, vp, vp], i32),
+            "gsx_gemm_mxfp4_nt_launch_cfg": ([vp, vp, vp, vp, i32, i32, i32, vp, vp, i32], i32),
+            "gsx_gemm_mxfp4_cfg_tile": ([i32, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
+            "gsx_gemm_mxfp4_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_event_time_gemm_mxfp4": ([vp, vp, vp, vp, i32, i32, i32, vp, vp, i32,
+                                           ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_quant_mxfp4": ([vp, vp, vp, vp, i32, i32], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
             "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
                                   i32),
@@ -478,3 +485,44 @@ def time_gemm_fp8(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int
                                       m, n, k, ctypes.c_void_p(scale_a), ctypes.c_void_p(scale_b), scale_mode, iters,
                                       ctypes.byref(ms)), "time_gemm_fp8")
     return ms.value
+
+
+def gemm_mxfp4_nt(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, scale_a: int, scale_b: int):
+    """``C`` (bf16) ``= A * B^T`` on MXFP4 operands: ``a`` and ``b`` are e2m1, two per byte
+    (``torch.float4_e2m1fn_x2``, rows of ``k / 2`` bytes), ``scale_a`` and ``scale_b`` the device addresses of their
+    e8m0 block scales (``torch.float8_e8m0fnu``, ``[rows][k / 32]``).  Not synchronised."""
+    _ck(lib().gsx_gemm_mxfp4_nt(stream.handle, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m, n, k,
+                                ctypes.c_void_p(scale_a), ctypes.c_void_p(scale_b)), "gemm_mxfp4_nt")
+
+
+def gemm_mxfp4_cfgs() -> dict[int, str]:
+    """``{index: name}`` of the mxfp4 tile configurations, read from the library's table
+    (native/kernels/gemm_mxfp4.hip)."""
+    out: dict[int, str] = {}
+    while (name := lib().gsx_gemm_mxfp4_cfg_name(len(out))) is not None:
+        out[len(out)] = name.decode()
+    return out
+
+
+def gemm_mxfp4_nt_cfg(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, cfg: int, scale_a: int,
+                      scale_b: int):
+    """Launch one configuration of the mxfp4 GEMM; an unknown config or a shape it cannot take raises HipError."""
+    _ck(lib().gsx_gemm_mxfp4_nt_launch_cfg(stream.handle, ctypes.c_void_p(a), ctypes.c_void_p(b),
+                                           ctypes.c_void_p(c), m, n, k, ctypes.c_void_p(scale_a),
+                                           ctypes.c_void_p(scale_b), cfg), f"gemm mxfp4 cfg {cfg}")
+
+
+def time_gemm_mxfp4(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, iters: int, scale_a: int,
+                    scale_b: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_gemm_mxfp4(stream.handle, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c),
+                                        m, n, k, ctypes.c_void_p(scale_a), ctypes.c_void_p(scale_b), iters,
+                                        ctypes.byref(ms)), "time_gemm_mxfp4")
+    return ms.value
+
+
+def quant_mxfp4(stream: Stream, x: int, q: int, s: int, rows: int, k: int):
+    """Quantise bf16 ``x[rows][k]`` (``k`` a multiple of 32) to MXFP4 per OCP MX v1.0: ``q[rows][k / 2]`` e2m1 pairs
+    and ``s[rows][k / 32]`` e8m0 block scales, the operand format of ``gemm_mxfp4_nt``.  Not synchronised."""
+    _ck(lib().gsx_quant_mxfp4(stream.handle, ctypes.c_void_p(x), ctypes.c_void_p(q), ctypes.c_void_p(s), rows, k),
+        "quant_mxfp4")

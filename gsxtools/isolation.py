@@ -95,7 +95,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--gpu-gib", type=int, default=287)
     ap.add_argument("--seconds", type=float, default=8.0)
     ap.add_argument("--kernel", default="gsx", choices=["gsx", "torch"])
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"], help="the pods' GEMM operand type")
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"],
+                    help="the pods' GEMM operand type (mxfp4: with --kernel gsx only)")
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--small-size", type=int, default=2048)
     ap.add_argument("--scenarios",

@@ -11,8 +11,8 @@ Targets (outputs land in ``gpushare_scheduler_extender_amd/_native/``):
                 module also loads on hosts without a GPU and never binds to the
                 ROCm-SMI copy bundled inside the torch wheel).
 * ``kernels`` – HIP/CDNA4 kernels for gfx950 (``libgsx_kernels.so``): CU probe,
-                HBM touch/verify, HBM memory test, compute (MFMA / VALU / LDS) test, bf16 and fp8 MFMA GEMM workload,
-                CU-masked streams.
+                HBM touch/verify, HBM memory test, compute (MFMA / VALU / LDS) test, bf16, fp8 and MXFP4 MFMA GEMM
+                workload with the MXFP4 quantiser, CU-masked streams.
 * ``tools``   – standalone HIP executables (``gsx-cuprobe``, ``gsx-memprobe``, ``gsx-memtest``, ``gsx-cutest``).
 * ``isolate`` – ``libgsx_isolate.so``, the HSA tools library that enforces a pod's CU partition and HBM share
                 inside every HIP/HSA process of the pod, plus its host-only test driver (fake HSA runtime).

@@ -1,11 +1,11 @@
-// Device code and the host launcher shared by the GEMM translation units (gemm.hip: bf16, gemm_fp8.hip: fp8 e4m3).
-// Internal, like gsx_internal.h.
+// Device code and the host launcher shared by the GEMM translation units (gemm.hip: bf16, gemm_fp8.hip: fp8 e4m3,
+// gemm_mxfp4.hip: e2m1 with e8m0 block scales).  Internal, like gsx_internal.h.
 //
-// A K-tile is 128 B per row whatever the operand type: 64 bf16 or 128 fp8 values.  So the global -> LDS staging, the
-// LDS swizzle and the ds_read_b128 pattern are the same for both; an operand kind (below) says what the element is
-// and how the 16-B chunks a lane has read turn into MFMAs.  The two K-loop schedules, gemm_kernel (one __syncthreads
-// per K-tile) and gemm_phased_kernel (prefetch in flight across barriers), exist once and take the kind as a
-// parameter.
+// A K-tile is 128 B per row whatever the operand type: 64 bf16, 128 fp8 or 256 fp4 values.  So the global -> LDS
+// staging, the LDS swizzle and the ds_read_b128 pattern are the same for all; an operand kind (below) says what the
+// element is and how the 16-B chunks a lane has read turn into MFMAs.  The two K-loop schedules, gemm_kernel (one
+// __syncthreads per K-tile) and gemm_phased_kernel (prefetch in flight across barriers), exist once and take the kind
+// as a parameter.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <type_traits>
+#include <utility>
 
 #include "gsx_internal.h"
 
@@ -22,6 +23,7 @@ namespace gsxgemm {
 using namespace gsx;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef long i64x2 __attribute__((ext_vector_type(2)));
@@ -33,14 +35,17 @@ typedef void __attribute__((address_space(3)))* lptr_t;
 constexpr int ROW_BYTES = 128;  // one row of a K-tile
 constexpr int CHUNK = 16;       // what one lane stages and reads at a time
 
-// Operand kinds.  `elem` is the storage type of A and B, BK the K-tile in elements, `frag` one 16-B chunk as the
-// MFMA builtin wants it.  Lane (fr, fq) of a 16x16 fragment reads chunks fq and 4 + fq of its row; CH says how many
-// of the two one call of mma() consumes.  A and B take the same chunks, so the k positions of a product agree
+// Operand kinds.  `elem` is the storage unit of A and B and EPU the elements one unit holds (2 for packed fp4): all
+// addressing is in units, a row of K elements being K / EPU of them.  BK is the K-tile in elements, `frag` one 16-B
+// chunk as the MFMA builtin wants it; MX says that the kind takes e8m0 block scales (MxScales below).  Lane (fr, fq)
+// of a 16x16 fragment reads chunks fq and 4 + fq of its row; CH says how many of the two one call of mma() consumes.
+// A and B take the same chunks, so the k positions of a product agree
 // whatever k order the instruction gives the bytes of a lane.
 struct Bf16 {  // v_mfma_f32_16x16x32_bf16: chunk fq is k 8 fq .. 8 fq + 7 of the first k-step, 4 + fq of the second
   using elem = uint16_t;
   using frag = bf16x8;
-  static constexpr int BK = ROW_BYTES / 2, CH = 1;
+  static constexpr int EPU = 1, BK = ROW_BYTES / 2, CH = 1;
+  static constexpr bool MX = false;
   static __device__ __forceinline__ void mma(f32x4& acc, const frag* a, const frag* b) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);
   }
@@ -50,7 +55,8 @@ struct Bf16 {  // v_mfma_f32_16x16x32_bf16: chunk fq is k 8 fq .. 8 fq + 7 of th
 struct Fp8K128 {
   using elem = uint8_t;
   using frag = i32x4;
-  static constexpr int BK = ROW_BYTES, CH = 2;
+  static constexpr int EPU = 1, BK = ROW_BYTES, CH = 2;
+  static constexpr bool MX = false;
   static __device__ __forceinline__ void mma(f32x4& acc, const frag* a, const frag* b) {
     const i32x8 av = __builtin_shufflevector(a[0], a[1], 0, 1, 2, 3, 4, 5, 6, 7);
     const i32x8 bv = __builtin_shufflevector(b[0], b[1], 0, 1, 2, 3, 4, 5, 6, 7);
@@ -61,12 +67,89 @@ struct Fp8K128 {
 struct Fp8K32 {
   using elem = uint8_t;
   using frag = i64x2;
-  static constexpr int BK = ROW_BYTES, CH = 1;
+  static constexpr int EPU = 1, BK = ROW_BYTES, CH = 1;
+  static constexpr bool MX = false;
   static __device__ __forceinline__ void mma(f32x4& acc, const frag* a, const frag* b) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a[0][0], b[0][0], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a[0][1], b[0][1], acc, 0, 0, 0);
   }
 };
+// OCP e2m1, two per byte (torch.float4_e2m1fn_x2), on the same instruction with format selects 4 / 4.  One 16-B chunk
+// is 32 elements: the lane's whole operand of one MFMA and exactly one scale block, so chunk fq is block fq of the
+// tile's first 128 k and chunk 4 + fq block fq of its second 128: two MFMAs per K-tile and fragment.  `sa` and `sb`
+// are VGPRs of four e8m0 codes each (MxScales); SA and SB, immediates, say which byte this MFMA takes.  With e2m1
+// selected the instruction reads the low four of the eight operand registers; the high four are left undefined.
+// FIXED: every scale is code 127 (2^0) whatever sa and sb hold, the ablation of the scale path.
+template <bool FIXED>
+struct Mxfp4T {
+  using elem = uint8_t;
+  using frag = i32x4;
+  static constexpr int EPU = 2, BK = 2 * ROW_BYTES, CH = 1;
+  static constexpr bool MX = !FIXED;
+  template <int SA, int SB>
+  static __device__ __forceinline__ void mma(f32x4& acc, const frag* a, const frag* b, int sa, int sb) {
+    const i32x8 av = __builtin_shufflevector(a[0], a[0], 0, 1, 2, 3, -1, -1, -1, -1);
+    const i32x8 bv = __builtin_shufflevector(b[0], b[0], 0, 1, 2, 3, -1, -1, -1, -1);
+    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, acc, 4, 4, SA, sa, SB, sb);
+  }
+  static __device__ __forceinline__ void mma(f32x4& acc, const frag* a, const frag* b) {
+    mma<0, 0>(acc, a, b, 127, 127);
+  }
+};
+using Mxfp4 = Mxfp4T<false>;
+using Mxfp4Unit = Mxfp4T<true>;
+
+// The e8m0 block scales of an MX kind, staged through LDS next to the operand tiles.  S[rows][K / 32] is row-major,
+// so the eight codes of one row and one K-tile are 8 consecutive, 8-B aligned bytes, and the LDS image of an operand
+// tile's scales is [row][8 codes], 8 B per row.  mx_stage() is the writer: one global_load_lds of 4 B per lane, wave
+// w fetching rows 32 w .. 32 w + 31 (lane l: row 32 w + l / 2, codes 4 (l & 1) .. + 3), which land lane-linear, that
+// is in this very layout.  read() and pack() are the reader.  The MFMA takes the scale of lane (fr, fq) from a byte of
+// a VGPR of that lane, and which byte is an immediate: the code of (row fr of the fragment, block fq) must sit at the
+// same byte position in all 64 lanes.  So for each of its N fragments (16 rows apart) a lane reads the 8 codes of its
+// row fr (one ds_read_b64, four lanes per address) and moves byte fq (first MFMA of the K-tile) and byte 4 + fq
+// (second) of four fragments into bytes 0 .. 3 of one VGPR with v_perm_b32: pk[kk][g] serves MFMA kk of fragments
+// 4 g .. 4 g + 3, fragment 4 g + i with byte select i.
+constexpr int MX_ROW = 8;  // bytes of scales per row and K-tile
+// s: the codes of the tile's row 0 (K-tile 0); ld = K / 32, the bytes of a row; img: the LDS image
+__device__ __forceinline__ void mx_stage(const uint8_t* s, int ld, int kt, char* img, int wid, int lane) {
+  const uint8_t* src = s + static_cast<size_t>(wid * 32 + (lane >> 1)) * ld + (kt * MX_ROW + (lane & 1) * 4);
+  __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(img + wid * 256), 4, 0, 0);
+}
+template <int N>
+struct MxScales {
+  static_assert(N % 4 == 0, "fragments are packed by fours");
+  i32x2 raw[N];
+  int pk[2][N / 4];
+  // row: the lane's row of fragment 0 in the image.  Read as plain vectors, like the operand fragments: through a
+  // struct type (uint2) the compiler takes the read for one that may alias the staging loads in flight and puts
+  // s_waitcnt vmcnt(0) in front of it.
+  __device__ __forceinline__ void read(const char* img, int row) {
+#pragma unroll
+    for (int f = 0; f < N; ++f) raw[f] = *reinterpret_cast<const i32x2*>(img + (row + f * 16) * MX_ROW);
+  }
+  __device__ __forceinline__ void pack(int fq) {
+    const int sel = 0x0c0c0000 | ((4 + fq) << 8) | fq;  // byte fq of both sources into bytes 0 and 1
+#pragma unroll
+    for (int g = 0; g < N / 4; ++g) {
+      const i32x2* r = raw + g * 4;
+      pk[0][g] = __builtin_amdgcn_perm(__builtin_amdgcn_perm(r[3].x, r[2].x, sel),
+                                       __builtin_amdgcn_perm(r[1].x, r[0].x, sel), 0x05040100);
+      pk[1][g] = __builtin_amdgcn_perm(__builtin_amdgcn_perm(r[3].y, r[2].y, sel),
+                                       __builtin_amdgcn_perm(r[1].y, r[0].y, sel), 0x05040100);
+    }
+  }
+};
+struct NoScales {};
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index can be an immediate
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
 
 // The LDS swizzle, both halves.  A K-tile row is 128 B = 8 chunks of 16 B, and the LDS image of a tile is
 // lane-linear: load slot p (lane p of a round of global_load_lds) lands at byte 16 p, i.e. row p >> 3, chunk
@@ -74,7 +157,7 @@ struct Fp8K32 {
 // (slot p fetches, from whichever global row its LDS row holds, the chunk that belongs at its position), swz() the
 // reader's.  The XOR is its own inverse, so both apply the same term; change one and the other must follow.
 template <typename T>
-__device__ __forceinline__ int glds_col(int p) {  // in elements, from the first element of the slot's global row
+__device__ __forceinline__ int glds_col(int p) {  // in units of T, from the first unit of the slot's global row
   const int row = p >> 3, slot = p & 7;
   return (slot ^ ((row >> 1) & 7)) * (CHUNK / static_cast<int>(sizeof(T)));
 }
@@ -137,6 +220,21 @@ struct Scaled {
 // The kernels take Scaled's members as arguments after K, or nothing there.
 template <typename... EP>
 using epilogue_t = std::conditional_t<sizeof...(EP) == 0, Unscaled, Scaled>;
+// An MX kind's kernels take scale_a and scale_b (e8m0 codes, [rows][K / 32]) there instead and have no epilogue.
+struct MxArgs {
+  const uint8_t* sa;
+  const uint8_t* sb;
+};
+template <class OP, typename... EP>
+using kernel_epilogue_t = std::conditional_t<OP::MX, Unscaled, epilogue_t<EP...>>;
+template <class S, bool TAKES, typename... EP>
+__device__ __forceinline__ S from_args(EP... ep) {
+  if constexpr (TAKES) {
+    return S{ep...};
+  } else {
+    return S{};
+  }
+}
 
 // Epilogue through LDS, in a region private to the wave: the accumulator fragments are scattered as bf16 into a
 // row-major WTM x WTN tile `ct`, which then leaves in 16-B row stores.
@@ -187,10 +285,12 @@ template <class OP, int BM, int BN, int WM, int WN, int GROUP_M, typename... EP>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const typename OP::elem* __restrict__ A,
                                                            const typename OP::elem* __restrict__ B,
                                                            uint16_t* __restrict__ C, int M, int N, int K, EP... ep) {
-  const epilogue_t<EP...> epi{ep...};
+  const auto epi = from_args<kernel_epilogue_t<OP, EP...>, !OP::MX>(ep...);
   using T = typename OP::elem;
   using frag = typename OP::frag;
   constexpr int BK = OP::BK, CH = OP::CH;
+  constexpr int BKU = BK / OP::EPU;  // a K-tile and a row of K elements in units of T
+  const int ld = K / OP::EPU;
   constexpr int NW = WM * WN;
   constexpr int TA = BM * ROW_BYTES, TB = BN * ROW_BYTES;  // bytes per operand tile
   constexpr int MR = BM / WM / 16, NR = BN / WN / 16;
@@ -213,21 +313,21 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const typename OP::e
 #pragma unroll
   for (int i = 0; i < (RA > RB ? RA : RB); ++i) {
     const int p = (i * NW + wid) * 64 + lane;
-    off[i] = (p >> 3) * K + glds_col<T>(p);
+    off[i] = (p >> 3) * ld + glds_col<T>(p);
   }
-  const T* Ab = A + static_cast<size_t>(row0) * K;
-  const T* Bb = B + static_cast<size_t>(col0) * K;
+  const T* Ab = A + static_cast<size_t>(row0) * ld;
+  const T* Bb = B + static_cast<size_t>(col0) * ld;
 
   auto stage = [&](int kt, int buf) {
     char* la = lds + buf * (TA + TB);
     char* lb = la + TA;
 #pragma unroll
     for (int i = 0; i < RA; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(Ab + off[i] + kt * BK), (lptr_t)(la + (i * NW + wid) * 1024), 16,
+      __builtin_amdgcn_global_load_lds((gptr_t)(Ab + off[i] + kt * BKU), (lptr_t)(la + (i * NW + wid) * 1024), 16,
                                        0, 0);
 #pragma unroll
     for (int i = 0; i < RB; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(Bb + off[i] + kt * BK), (lptr_t)(lb + (i * NW + wid) * 1024), 16,
+      __builtin_amdgcn_global_load_lds((gptr_t)(Bb + off[i] + kt * BKU), (lptr_t)(lb + (i * NW + wid) * 1024), 16,
                                        0, 0);
   };
 
@@ -238,11 +338,34 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const typename OP::e
     for (int n = 0; n < NR; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int nk = K / BK;
+  // MX: the scales of a K-tile are staged with its operands, into images behind the operand buffers
+  constexpr bool MX = OP::MX;
+  static_assert(!MX || (MR == 4 && NR == 4 && BM == NW * 32 && BN == NW * 32),
+                "the scale path packs four fragments and stages 32 rows per wave");
+  constexpr int SCALES = 2 * (TA + TB);  // [buf][A|B] images of BM and BN rows
+  [[maybe_unused]] std::conditional_t<MX, MxScales<4>, NoScales> sca, scb;
+  [[maybe_unused]] const auto stage_scales = [&](int kt, int buf) {
+    if constexpr (MX) {
+      const auto mx = from_args<MxArgs, MX>(ep...);
+      char* img = lds + SCALES + buf * (BM + BN) * MX_ROW;
+      mx_stage(mx.sa + static_cast<size_t>(row0) * (K / 32), K / 32, kt, img, wid, lane);
+      mx_stage(mx.sb + static_cast<size_t>(col0) * (K / 32), K / 32, kt, img + BM * MX_ROW, wid, lane);
+    }
+  };
+  stage_scales(0, 0);
   stage(0, 0);
   __syncthreads();
   const int fr = lane & 15, fq = lane >> 4;
   for (int kt = 0; kt < nk; ++kt) {
     const int buf = kt & 1;
+    if constexpr (MX) {
+      const char* img = lds + SCALES + buf * (BM + BN) * MX_ROW;
+      sca.read(img, wr * WTM + fr);
+      scb.read(img + BM * MX_ROW, wc * WTN + fr);
+      sca.pack(fq);
+      scb.pack(fq);
+      if (kt + 1 < nk) stage_scales(kt + 1, buf ^ 1);
+    }
     if (kt + 1 < nk) stage(kt + 1, buf ^ 1);
     const char* la = lds + buf * (TA + TB);
     const char* lb = la + TA;
@@ -261,8 +384,16 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const typename OP::e
         for (int c = 0; c < CH; ++c)
           af[c] = *reinterpret_cast<const frag*>(la + swz(wr * WTM + m * 16 + fr, (kk * CH + c) * 4 + fq));
         __builtin_amdgcn_s_setprio(1);
+        if constexpr (MX) {
+          static_for<NR>([&](auto n) {
+            static_for<4>([&](auto sel) {  // m as an immediate
+              if (sel == m) OP::template mma<sel, n>(acc[m][n], af, bfr[n], sca.pk[kk][0], scb.pk[kk][0]);
+            });
+          });
+        } else {
 #pragma unroll
-        for (int n = 0; n < NR; ++n) OP::mma(acc[m][n], af, bfr[n]);
+          for (int n = 0; n < NR; ++n) OP::mma(acc[m][n], af, bfr[n]);
+        }
         __builtin_amdgcn_s_setprio(0);
       }
     }
@@ -299,6 +430,20 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const typename OP::e
 // staggered groups) and waited for (vmcnt(8) before the first barrier of the
 // phase) one phase before it is read (RAW).  Tiles past the end are clamped to
 // the last tile so the counts stay uniform; those loads land in dead buffers.
+//
+// An MX kind adds the block scales (MxScales): per K-tile an image of A's and one of B's, 2 KiB each, behind the
+// operand buffers, [tile & 1][A|B]; staging both is "half S", two global_load_lds per wave.  They are vector-memory
+// loads like the other stages, counted by the same vmcnt and completing in issue order, so where they are issued
+// decides what a count means.  Half S travels with half 0, issued just before it:
+//   p0: read S (8 + 4 ds_read_b64), A0, B2; stage t+1 half 3; vmcnt(10): half 3 of t has landed, in flight at most
+//       t half 1 | t+1 halves S, 0, 2, 3; after the barrier S is packed into 6 registers
+//   p1: stage t+1 half 1; vmcnt(10): half 1 of t has landed, in flight t+1 halves S, 0, 2, 3, 1
+//   p2: stage t+2 halves S, 0; no wait
+//   p3: stage t+2 half 2; vmcnt(10): t+1 halves S, 0, 2 have landed, in flight t+1 halves 3, 1 | t+2 halves S, 0, 2
+// So every count is the old 8 plus the 2 loads of one half S, and the same four operand half-tiles stay in flight.
+// Half S is read in p0 and restaged in p2 like half 0 (WAR), and p3's wait and barrier come before its first read in
+// the next p0 (RAW).  A tile past the end is clamped for the scales as for the operands, so the loads stay inside
+// the scale arrays.
 // ---------------------------------------------------------------------------
 constexpr int PH_HALF = 128 * ROW_BYTES;  // 16 KiB
 
@@ -317,11 +462,15 @@ template <class OP, int GROUP_M, bool M32, typename... EP>
 __global__ __launch_bounds__(512) void gemm_phased_kernel(const typename OP::elem* __restrict__ A,
                                                          const typename OP::elem* __restrict__ B,
                                                          uint16_t* __restrict__ C, int M, int N, int K, EP... ep) {
-  const epilogue_t<EP...> epi{ep...};
+  const auto epi = from_args<kernel_epilogue_t<OP, EP...>, !OP::MX>(ep...);
   using T = typename OP::elem;
   using frag = typename OP::frag;
   static_assert(!M32 || std::is_same_v<OP, Bf16>, "the 32x32 shape is a bf16 ablation");
   constexpr int BK = OP::BK, CH = OP::CH;
+  constexpr int BKU = BK / OP::EPU;  // a K-tile and a row of K elements in units of T
+  const int ld = K / OP::EPU;
+  constexpr bool MX = OP::MX;
+  constexpr int VM = 8 + (MX ? 2 : 0);  // the vmcnt of the phases: four half-tiles, and one half S
   constexpr int BM = 256, BN = 256, WTM = 128, WTN = 64;
   extern __shared__ __attribute__((aligned(16))) char lds[];
 
@@ -332,8 +481,8 @@ __global__ __launch_bounds__(512) void gemm_phased_kernel(const typename OP::ele
 
   int tm, tn;
   tile_of<BM, BN, GROUP_M>(blockIdx.x, gridDim.x, M, N, tm, tn);
-  const T* Ab = A + static_cast<size_t>(tm * BM) * K;
-  const T* Bb = B + static_cast<size_t>(tn * BN) * K;
+  const T* Ab = A + static_cast<size_t>(tm * BM) * ld;
+  const T* Bb = B + static_cast<size_t>(tn * BN) * ld;
 
   // per-lane source offsets of the two 8-KiB rounds of each half
   int off[4][2];
@@ -342,15 +491,15 @@ __global__ __launch_bounds__(512) void gemm_phased_kernel(const typename OP::ele
     const int p = (i * 8 + wid) * 64 + lane;
     const int lr = p >> 3;
     const int sw = glds_col<T>(p);
-    off[0][i] = ((lr >> 6) * 128 + (lr & 63)) * K + sw;
-    off[1][i] = ((lr >> 6) * 128 + 64 + (lr & 63)) * K + sw;
-    off[2][i] = ((lr >> 5) * 64 + (lr & 31)) * K + sw;
-    off[3][i] = ((lr >> 5) * 64 + 32 + (lr & 31)) * K + sw;
+    off[0][i] = ((lr >> 6) * 128 + (lr & 63)) * ld + sw;
+    off[1][i] = ((lr >> 6) * 128 + 64 + (lr & 63)) * ld + sw;
+    off[2][i] = ((lr >> 5) * 64 + (lr & 31)) * ld + sw;
+    off[3][i] = ((lr >> 5) * 64 + 32 + (lr & 31)) * ld + sw;
   }
   const int nk = K / BK;
   auto stage = [&](int tile, int half) {
     const int kt = tile < nk ? tile : nk - 1;
-    const T* src = (half < 2 ? Ab : Bb) + kt * BK;
+    const T* src = (half < 2 ? Ab : Bb) + kt * BKU;
     char* dst = lds + ((tile & 1) * 4 + half) * PH_HALF + wid * 1024;
     __builtin_amdgcn_global_load_lds((gptr_t)(src + off[half][0]), (lptr_t)dst, 16, 0, 0);
     __builtin_amdgcn_global_load_lds((gptr_t)(src + off[half][1]), (lptr_t)(dst + 8 * 1024), 16, 0, 0);
@@ -369,6 +518,19 @@ __global__ __launch_bounds__(512) void gemm_phased_kernel(const typename OP::ele
   const int fr = lane & 15, fq = lane >> 4;
   const int r32 = lane & 31, h32 = lane >> 5;  // M32 operand maps: row / column lane & 31, k = 8 (lane >> 5) + j
   frag af[4][2], bf[2][2][2];  // A: [m][chunk]; B: [nh][n][chunk]  (M32: A [b][kk], B [nh][kk], k-steps of 16)
+
+  // MX: sca.pk[kk][mh] holds the scales of A fragments 4 mh .. 4 mh + 3, scb.pk[kk][0] those of the 4 B fragments
+  [[maybe_unused]] std::conditional_t<MX, MxScales<8>, NoScales> sca;
+  [[maybe_unused]] std::conditional_t<MX, MxScales<4>, NoScales> scb;
+  [[maybe_unused]] const auto stage_scales = [&](int tile) {
+    if constexpr (MX) {
+      const auto mx = from_args<MxArgs, MX>(ep...);
+      const int kt = tile < nk ? tile : nk - 1;
+      char* img = lds + 8 * PH_HALF + (tile & 1) * (BM + BN) * MX_ROW;
+      mx_stage(mx.sa + static_cast<size_t>(tm * BM) * (K / 32), K / 32, kt, img, wid, lane);
+      mx_stage(mx.sb + static_cast<size_t>(tn * BN) * (K / 32), K / 32, kt, img + BM * MX_ROW, wid, lane);
+    }
+  };
 
   auto read_a = [&](const char* base, int mh) {
     const char* h = base + mh * PH_HALF;
@@ -412,53 +574,76 @@ __global__ __launch_bounds__(512) void gemm_phased_kernel(const typename OP::ele
               af[b * 2 + (kk >> 1)][kk & 1], bf[nh][kk >> 1][kk & 1], acc[mh * 2 + b][nh], 0, 0, 0);
     } else {
 #pragma unroll
-      for (int kk = 0; kk < 2 / CH; ++kk)
+      for (int kk = 0; kk < 2 / CH; ++kk) {
+        if constexpr (MX) {
+          static_for<4>([&](auto m) {
+            static_for<4>([&](auto nn) {  // nh * 2 + n as an immediate
+              if (nn >> 1 == nh)
+                OP::template mma<m, nn>(acc[mh * 4 + m][nn], &af[m][kk], &bf[nn >> 1][nn & 1][kk], sca.pk[kk][mh],
+                                        scb.pk[kk][0]);
+            });
+          });
+        } else {
 #pragma unroll
-        for (int m = 0; m < 4; ++m)
+          for (int m = 0; m < 4; ++m)
 #pragma unroll
-          for (int n = 0; n < 2; ++n)
-            OP::mma(acc[mh * 4 + m][nh * 2 + n], &af[m][kk * CH], &bf[nh][n][kk * CH]);
+            for (int n = 0; n < 2; ++n)
+              OP::mma(acc[mh * 4 + m][nh * 2 + n], &af[m][kk * CH], &bf[nh][n][kk * CH]);
+        }
+      }
     }
     __builtin_amdgcn_s_setprio(0);
   };
 
   // prologue: what the steady state has issued before tile 0, phase 0
+  stage_scales(0);
   stage(0, 0);
   stage(0, 2);
   stage(0, 3);
   stage(0, 1);
+  stage_scales(1);
   stage(1, 0);
   stage(1, 2);
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory");
   ph_barrier();
   if (wr == 1) ph_barrier();  // stagger the groups by one barrier
 
   for (int t = 0; t < nk; ++t) {
     const char* base = lds + (t & 1) * 4 * PH_HALF;
     // p0
+    if constexpr (MX) {
+      const char* img = lds + 8 * PH_HALF + (t & 1) * (BM + BN) * MX_ROW;
+      sca.read(img, wr * WTM + fr);
+      scb.read(img + BM * MX_ROW, wc * WTN + fr);
+    }
     read_a(base, 0);
     read_b(base, 0);
     stage(t + 1, 3);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory");
     ph_barrier();
+    if constexpr (MX) {  // after the barrier: the reads' latency passes while the wave waits there
+      sca.pack(fq);
+      scb.pack(fq);
+    }
     mma(0, 0);
     ph_barrier();
     // p1
     read_b(base, 1);
     stage(t + 1, 1);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory");
     ph_barrier();
     mma(0, 1);
     ph_barrier();
     // p2
     read_a(base, 1);
+    stage_scales(t + 2);
     stage(t + 2, 0);
     ph_barrier();
     mma(1, 1);
     ph_barrier();
     // p3
     stage(t + 2, 2);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory");
     ph_barrier();
     mma(1, 0);
     ph_barrier();
@@ -482,11 +667,11 @@ __global__ __launch_bounds__(512) void gemm_phased_kernel(const typename OP::ele
 // ---------------------------------------------------------------------------
 
 // Validates once for every kernel, then launches; a failure's text begins with `who`, the C entry point.  T is the
-// operands' element type; `extra` are the kernel's arguments after K.
-template <auto KERNEL, typename T, int THREADS, int LDS, int BM, int BN, typename... Extra>
+// operands' storage unit and EPU the elements in one (the kind's); `extra` are the kernel's arguments after K.
+template <auto KERNEL, typename T, int THREADS, int LDS, int BM, int BN, int EPU = 1, typename... Extra>
 int launch(const char* who, hipStream_t s, const void* A, const void* B, void* C, int M, int N, int K,
            Extra... extra) {
-  constexpr int BK = ROW_BYTES / sizeof(T);
+  constexpr int BKU = ROW_BYTES / sizeof(T), BK = BKU * EPU;  // a K-tile in units and in elements
   char msg[160];
   if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK) {
     std::snprintf(msg, sizeof(msg), "%s: need M%%%d==0, N%%%d==0, K%%%d==0", who, BM, BN, BK);
@@ -496,12 +681,13 @@ int launch(const char* who, hipStream_t s, const void* A, const void* B, void* C
     std::snprintf(msg, sizeof(msg), "%s: operands must be 16-B aligned", who);
     return fail_arg(msg);
   }
-  // The kernels keep a lane's source offset inside an operand tile in an int: row * K + column, with
-  // row < max(BM, BN) and column <= BK minus one 16-B chunk (off[] of the kernels).  Everything else that grows
-  // with the problem is added to the pointer in 64 bits.
+  // The kernels keep a lane's source offset inside an operand tile in an int, in units: row * (K / EPU) + column,
+  // with row < max(BM, BN) and column <= a K-tile minus one 16-B chunk (off[] of the kernels).  Everything else that
+  // grows with the problem is added to the pointer in 64 bits.
   constexpr int SIDE = BM > BN ? BM : BN;
-  if (static_cast<int64_t>(SIDE - 1) * K + (BK - CHUNK / static_cast<int>(sizeof(T))) > INT32_MAX) {
-    std::snprintf(msg, sizeof(msg), "%s: K too large: %d rows of K elements must stay below 2^31", who, SIDE);
+  if (static_cast<int64_t>(SIDE - 1) * (K / EPU) + (BKU - CHUNK / static_cast<int>(sizeof(T))) > INT32_MAX) {
+    std::snprintf(msg, sizeof(msg), "%s: K too large: %d rows of K elements%s must stay below 2^31", who, SIDE,
+                  EPU == 1 ? "" : ", packed two to the byte,");
     return fail_arg(msg);
   }
   // More dynamic LDS than the default limit has to be asked for.  The flag is per device because

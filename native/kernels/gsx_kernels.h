@@ -21,6 +21,9 @@
 //                          (throughput under per-pod CU partitions);
 //  * fp8 MFMA GEMM       — the same workload on OCP e4m3 operands and the K=128
 //                          MFMA, with per-tensor or per-row scales (gemm_fp8.hip);
+//  * MXFP4 MFMA GEMM     — the same workload on e2m1 operands with e8m0 block scales
+//                          on the block-scaled MFMA, and the quantiser that makes
+//                          such operands from bf16 (gemm_mxfp4.hip);
 //  * CU-masked streams   — hipExtStreamCreateWithCUMask.
 //
 // All functions return 0 or a hipError_t value; gsx_last_error() has text.
@@ -136,6 +139,42 @@ int gsx_gemm_fp8_nt_launch_cfg(void* stream, const void* A, const void* B, void*
 // elapsed milliseconds of `iters` back-to-back gsx_gemm_fp8_nt on `stream`, by hip events (for benches)
 int gsx_event_time_gemm_fp8(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
                             const float* scale_a, const float* scale_b, int scale_mode, int iters, float* ms);
+
+// MXFP4 GEMM (gemm_mxfp4.hip), on v_mfma_scale_f32_16x16x128_f8f6f4 with the same schedules as the other families.
+// The operand format:
+//   A[M][K], B[N][K]   OCP e2m1, two per byte, row-major (torch.float4_e2m1fn_x2): a row is K / 2 bytes, element k
+//                      is in byte k / 2, the low nibble for even k and the high nibble for odd k
+//   scale_a[M][K / 32], scale_b[N][K / 32]
+//                      bytes, row-major, e8m0 (torch.float8_e8m0fnu): code c means 2^(c - 127) and applies to
+//                      elements 32 g .. 32 g + 31 of its row, g the column of the code.  This plain layout is the
+//                      one in memory; what the instruction wants is arranged inside the kernels.
+//   C[i][j] = bf16( sum over g of 2^(sa[i][g] - 127) * 2^(sb[j][g] - 127) * sum over k in block g of A[i][k] B[j][k] )
+//                      accumulated in fp32; C is bf16, row-major.
+// Scale codes 1 .. 254 are the contract.  With code 0 (2^-127) or 255 (NaN) anywhere the result is whatever the
+// instruction gives.  A, B, C, scale_a and scale_b are 16-B aligned and not NULL.  Launches on `stream` and returns
+// without synchronising; everything is validated before the first device call.
+// K is limited by the 32-bit byte offsets inside an operand tile: (max(BM, BN) - 1) * K / 2 + 112 < 2^31, which is
+// K <= 16843008 for a tile side of 256 and K <= 33818624 for 128 (multiples of 256); a longer K is rejected.
+// gsx_gemm_mxfp4_nt requires M % 128 == 0, N % 128 == 0, K % 256 == 0 and dispatches like gsx_gemm_fp8_nt.
+int gsx_gemm_mxfp4_nt(void* stream, const void* A, const void* B, void* C, int M, int N, int K, const void* scale_a,
+                      const void* scale_b);
+// The mxfp4 configurations, a table of their own in gemm_mxfp4.hip: 0 "128x128/4w", 1 "256x256/8w-phased-g4" (the
+// dispatched one), 2 "256x256/8w-phased-g4-unit" (the same kernel without the scale path: every scale is taken as
+// code 127 and scale_a and scale_b are validated but not read; the ablation of the scale path).  Same conventions as
+// the fp8 table; _launch_cfg requires M % BM == 0, N % BN == 0, K % 256 == 0.
+const char* gsx_gemm_mxfp4_cfg_name(int cfg);
+int gsx_gemm_mxfp4_cfg_tile(int cfg, int* bm, int* bn);
+int gsx_gemm_mxfp4_nt_launch_cfg(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
+                                 const void* scale_a, const void* scale_b, int cfg);
+// elapsed milliseconds of `iters` back-to-back gsx_gemm_mxfp4_nt on `stream`, by hip events (for benches)
+int gsx_event_time_gemm_mxfp4(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
+                              const void* scale_a, const void* scale_b, int iters, float* ms);
+// The quantiser: bf16 X[R][K] (K % 32 == 0) -> Q[R][K / 2] and S[R][K / 32] in the format above, per OCP MX v1.0.
+// Per block of 32, e = floor(log2(max|x|)) - 2 and the code is clamp(e + 127, 1, 254); the elements are x / 2^e
+// rounded to nearest even onto the e2m1 grid, saturated to +-6, the sign of a zero kept.  An all-zero block gets code
+// 127; a block that holds an inf or a NaN gets code 255 and unspecified elements (outside the GEMM's contract).  X
+// and Q are 16-B aligned.  Launches on `stream` and returns without synchronising.
+int gsx_quant_mxfp4(void* stream, const void* X, void* Q, void* S, int R, int K);
 
 // HBM pre-flight memory test (memtest.hip).  The expected content of 16-byte word W = origin/16 + word index is
 // generated from (pattern, seed, invert, W) and never stored; `origin` is the byte offset of `base` in the whole

@@ -13,7 +13,9 @@ builds; nothing else of this repository): counterpart of the reference's sample 
 * the compute is the bf16 MFMA GEMM of ``libgsx_kernels.so`` (``--kernel gsx``, found next to this file, at
   ``$GSX_KERNELS_LIB``, or in the repository's build tree) or ``torch.matmul`` / hipBLASLt (``--kernel torch``);
   ``auto`` (default) takes the MFMA kernel when the library is there and says so when it falls back;
-* ``--dtype fp8`` runs the same loop on OCP e4m3 operands: the library's fp8 GEMM, or ``torch._scaled_mm``.
+* ``--dtype fp8`` runs the same loop on OCP e4m3 operands: the library's fp8 GEMM, or ``torch._scaled_mm``;
+* ``--dtype mxfp4`` runs it on MXFP4 operands (e2m1 with e8m0 block scales), made by quantising the random bf16
+  matrices with the library's ``gsx_quant_mxfp4``: the library's mxfp4 GEMM only, ``--kernel torch`` has none.
 """
 from __future__ import annotations
 
@@ -56,6 +58,10 @@ class Kernels:
         if hasattr(L, "gsx_gemm_fp8_nt"):  # an image built before the fp8 kernels has none; --dtype fp8 says so
             L.gsx_gemm_fp8_nt.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32]
             L.gsx_gemm_fp8_nt.restype = i32
+        if hasattr(L, "gsx_gemm_mxfp4_nt"):  # likewise: an image built before the mxfp4 kernels
+            L.gsx_gemm_mxfp4_nt.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
+            L.gsx_quant_mxfp4.argtypes = [vp, vp, vp, vp, i32, i32]
+            L.gsx_gemm_mxfp4_nt.restype = L.gsx_quant_mxfp4.restype = i32
         L.gsx_last_error.argtypes, L.gsx_last_error.restype = [], ctypes.c_char_p
         self.L, self.path = L, path
 
@@ -79,6 +85,22 @@ class Kernels:
             raise RuntimeError(f"{self.path} has no gsx_gemm_fp8_nt: rebuild it")
         self._ck(self.L.gsx_gemm_fp8_nt(s, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m, n, k,
                                         None, None, 0), "gemm_fp8_nt")
+
+    def has_mxfp4(self) -> bool:
+        return hasattr(self.L, "gsx_gemm_mxfp4_nt")
+
+    def quant_mxfp4(self, s, x: int, q: int, sc: int, rows: int, k: int):
+        """bf16 ``x[rows][k]`` -> e2m1 pairs ``q[rows][k / 2]`` and e8m0 block scales ``sc[rows][k / 32]``."""
+        if not self.has_mxfp4():
+            raise RuntimeError(f"{self.path} has no gsx_quant_mxfp4: rebuild it")
+        self._ck(self.L.gsx_quant_mxfp4(s, ctypes.c_void_p(x), ctypes.c_void_p(q), ctypes.c_void_p(sc), rows, k),
+                 "quant_mxfp4")
+
+    def gemm_mxfp4(self, s, a: int, b: int, c: int, m: int, n: int, k: int, sa: int, sb: int):
+        if not self.has_mxfp4():
+            raise RuntimeError(f"{self.path} has no gsx_gemm_mxfp4_nt: rebuild it")
+        self._ck(self.L.gsx_gemm_mxfp4_nt(s, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m, n, k,
+                                          ctypes.c_void_p(sa), ctypes.c_void_p(sb)), "gemm_mxfp4_nt")
 
     def sync(self, s):
         self._ck(self.L.gsx_stream_sync(s), "stream_sync")
@@ -119,8 +141,11 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         hold = torch.empty(int(allocated * (1 << 30) * 0.9) // 2, dtype=torch.bfloat16, device=dev)
         hold.fill_(1)
     m = n = k = size
-    if dtype not in ("bf16", "fp8"):
-        raise SystemExit(f"--dtype {dtype}: bf16 or fp8")
+    if dtype not in ("bf16", "fp8", "mxfp4"):
+        raise SystemExit(f"--dtype {dtype}: bf16, fp8 or mxfp4")
+    if dtype == "mxfp4" and kernel != "gsx":
+        raise SystemExit("--dtype mxfp4 needs the library's kernels (--kernel gsx): "
+                         + ("torch has no such GEMM" if kl is not None else "libgsx_kernels.so was not found"))
     a = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
     b = torch.randn(n, k, device=dev, dtype=torch.bfloat16)
     c = torch.empty(m, n, device=dev, dtype=torch.bfloat16)
@@ -133,6 +158,17 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         own = None if hip_stream is not None else gs
 
         gemm = kl.gemm_fp8 if dtype == "fp8" else kl.gemm
+        if dtype == "mxfp4":  # quantise the random bf16 operands once; the loop runs on the result
+            qa, qb = (torch.empty(r, k // 2, device=dev, dtype=torch.uint8) for r in (m, n))
+            sa, sb = (torch.empty(r, k // 32, device=dev, dtype=torch.uint8) for r in (m, n))
+            torch.cuda.synchronize()
+            kl.quant_mxfp4(gs, a.data_ptr(), qa.data_ptr(), sa.data_ptr(), m, k)
+            kl.quant_mxfp4(gs, b.data_ptr(), qb.data_ptr(), sb.data_ptr(), n, k)
+            kl.sync(gs)
+            a, b = qa, qb
+
+            def gemm(s, pa, pb, pc, m, n, k):
+                kl.gemm_mxfp4(s, pa, pb, pc, m, n, k, sa.data_ptr(), sb.data_ptr())
 
         def step():
             gemm(gs, a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k)
@@ -208,8 +244,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--allocated", type=float, default=float(os.environ.get(f"{p}_CONTAINER", "0") or 0),
                     help="this container's share (the device plugin's *_CONTAINER env)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "gsx", "torch"])
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"],
-                    help="operand type of the GEMM: bf16, or fp8 (OCP e4m3; the output stays bf16)")
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"],
+                    help="operand type of the GEMM: bf16, fp8 (OCP e4m3) or mxfp4 (e2m1 with e8m0 block scales, "
+                         "quantised from bf16 by the library; --kernel gsx only); the output stays bf16")
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--seconds", type=float, default=0.0, help="0 = run forever (like the reference sample)")
     ap.add_argument("--iters", type=int, default=0)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Micro-benchmarks of the HIP kernels on one MI355X: bf16 and fp8 GEMM (ours vs torch/hipBLASLt), HBM fill,
+"""Micro-benchmarks of the HIP kernels on one MI355X: bf16, fp8 and mxfp4 GEMM (ours vs torch/hipBLASLt), HBM fill,
 stamp/verify."""
 import json
 import os
@@ -120,6 +120,91 @@ def gemm_fp8(size_list, iters=20, rounds=3):
     return out
 
 
+def dequant_mxfp4(q, sc):
+    """fp32 values of an MXFP4 operand (``q`` e2m1 pairs, ``sc`` e8m0 block scales), on the GPU."""
+    grid = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], device=q.device)
+    codes = torch.stack([q & 15, q >> 4], dim=2).reshape(q.shape[0], -1).long()
+    vals = grid[codes & 7] * (1 - 2 * (codes >> 3)).float()
+    return vals * torch.exp2(sc.float() - 127).repeat_interleave(32, dim=1)
+
+
+def gemm_mxfp4(size_list, iters=20, rounds=3):
+    """Every mxfp4 configuration on random bf16 operands quantised by ``gsx_quant_mxfp4``, the fp8 default and the
+    bf16 default on operands of the same shape, interleaved in one process: median TFLOP/s of ``rounds`` repeats, each
+    mxfp4 result's max abs error against the fp32 product of the dequantised operands (the ablation row takes every
+    scale as 1, so its error is large by design), and the quantiser's GB/s (bytes read and written) next to
+    ``gsx_hbm_fill`` over the same number of bytes."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    for m, n, k in size_list:
+        a16 = torch.randn(m, k, device="cuda", dtype=torch.bfloat16)
+        b16 = torch.randn(n, k, device="cuda", dtype=torch.bfloat16)
+        a8, b8 = a16.to(torch.float8_e4m3fn), b16.to(torch.float8_e4m3fn)
+        qa, qb = (torch.empty(r, k // 2, device="cuda", dtype=torch.uint8) for r in (m, n))
+        sa, sb = (torch.empty(r, k // 32, device="cuda", dtype=torch.uint8) for r in (m, n))
+        c = torch.empty(m, n, device="cuda", dtype=torch.bfloat16)
+        torch.cuda.synchronize()  # operands come from torch's stream; everything below runs on ours
+        quant = (lambda: (hip.quant_mxfp4(s, a16.data_ptr(), qa.data_ptr(), sa.data_ptr(), m, k),
+                          hip.quant_mxfp4(s, b16.data_ptr(), qb.data_ptr(), sb.data_ptr(), n, k)))
+        quant()
+        s.sync()
+        ref = dequant_mxfp4(qa, sa) @ dequant_mxfp4(qb, sb).t()
+        torch.cuda.synchronize()
+        ptrs = (qa.data_ptr(), qb.data_ptr(), c.data_ptr())
+        scales = (sa.data_ptr(), sb.data_ptr())
+        variants = {f"cfg{cfg}_{name}": (lambda cfg=cfg: hip.gemm_mxfp4_nt_cfg(s, *ptrs, m, n, k, cfg, *scales))
+                    for cfg, name in hip.gemm_mxfp4_cfgs().items()}
+        row = {"m": m, "n": n, "k": k}
+        for name, fn in variants.items():
+            c.zero_()
+            torch.cuda.synchronize()
+            fn()
+            s.sync()
+            row[f"{name}_err"] = round((c.float() - ref).abs().max().item(), 4)
+        row["ref_absmax"] = round(ref.abs().max().item(), 1)
+        del ref
+        variants["gsx"] = lambda: hip.gemm_mxfp4_nt(s, *ptrs, m, n, k, *scales)
+        variants["fp8_gsx"] = lambda: hip.gemm_fp8_nt(s, a8.data_ptr(), b8.data_ptr(), c.data_ptr(), m, n, k)
+        variants["bf16_gsx"] = lambda: hip.gemm_bf16_nt(s, a16.data_ptr(), b16.data_ptr(), c.data_ptr(), m, n, k)
+
+        def timed(fn, reps=iters):
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(ts)
+                for _ in range(reps):
+                    fn()
+                e1.record(ts)
+            e1.synchronize()
+            return e0.elapsed_time(e1) / reps  # ms
+
+        runs = {name: [] for name in variants}
+        qbytes = (m + n) * (2 * k + k // 2 + k // 32)
+        fill = hip.DeviceBuffer(0, qbytes & ~255)
+        qruns, fruns = [], []
+        for r in range(rounds + 1):  # the first round warms up clocks and code objects
+            for name, fn in variants.items():
+                t = 2 * m * n * k / timed(fn) / 1e9
+                if r:
+                    runs[name].append(t)
+            tq = qbytes / timed(quant, 5) / 1e6
+            tf = (qbytes & ~255) / timed(lambda: hip.hbm_fill(s, fill.addr(), qbytes & ~255, r), 5) / 1e6
+            if r:
+                qruns.append(tq)
+                fruns.append(tf)
+        fill.free()
+        for name, r in runs.items():
+            row[f"{name}_tflops"] = round(statistics.median(r), 1)
+        row["mxfp4_over_fp8"] = round(row["gsx_tflops"] / row["fp8_gsx_tflops"], 3)
+        row["quant_GBps"] = round(statistics.median(qruns), 1)
+        row["hbm_fill_GBps"] = round(statistics.median(fruns), 1)
+        out.append(row)
+        del a16, b16, a8, b8, qa, qb, sa, sb, c
+    s.destroy()
+    return out
+
+
 def hbm(nbytes=16 << 30, reps=5):
     s = hip.Stream(0)
     buf = hip.DeviceBuffer(0, nbytes)
@@ -149,7 +234,10 @@ def hbm(nbytes=16 << 30, reps=5):
 if __name__ == "__main__":
     sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (2048, 8192, 4096), (16384, 16384, 8192)]
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
-    res = {"gemm_bf16_nt": gemm(sizes), "gemm_fp8_nt": gemm_fp8(fp8_sizes), "hbm": hbm()}
+    sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
+                "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "hbm": hbm}
+    only = sys.argv[2].split(",") if len(sys.argv) > 2 else list(sections)  # [out.json [section,section..]]
+    res = {name: sections[name]() for name in only}
     print(json.dumps(res))
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as f:
