@@ -148,6 +148,12 @@ def lib():
             "gsx_event_time_gemm_mxfp4": ([vp, vp, vp, vp, i32, i32, i32, vp, vp, i32,
                                            ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_quant_mxfp4": ([vp, vp, vp, vp, i32, i32], i32),
+            "gsx_decode_gemm_nt": ([vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32], i32),
+            "gsx_decode_gemm_nt_launch_cfg": ([vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32], i32),
+            "gsx_decode_gemm_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_decode_gemm_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
+            "gsx_event_time_decode_gemm": ([vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32,
+                                            ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
             "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
                                   i32),
@@ -526,3 +532,57 @@ def quant_mxfp4(stream: Stream, x: int, q: int, s: int, rows: int, k: int):
     and ``s[rows][k / 32]`` e8m0 block scales, the operand format of ``gemm_mxfp4_nt``.  Not synchronised."""
     _ck(lib().gsx_quant_mxfp4(stream.handle, ctypes.c_void_p(x), ctypes.c_void_p(q), ctypes.c_void_p(s), rows, k),
         "quant_mxfp4")
+
+
+# ``kind`` of the decode GEMM (gsx_kernels.h): the operand format, each that of the GEMM family of the same name
+DECODE_KINDS = {"bf16": 0, "fp8": 1, "mxfp4": 2}
+
+
+def _decode_kind(kind: str) -> int:
+    if kind not in DECODE_KINDS:
+        raise ValueError(f"decode kind {kind!r}: one of {', '.join(DECODE_KINDS)}")
+    return DECODE_KINDS[kind]
+
+
+def _decode_args(stream: Stream, kind: str, a: int, b: int, c: int, m: int, n: int, k: int, scale_a: int,
+                 scale_b: int, scale_mode: int) -> tuple:
+    return (stream.handle, _decode_kind(kind), ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m, n, k,
+            ctypes.c_void_p(scale_a), ctypes.c_void_p(scale_b), scale_mode)
+
+
+def decode_gemm_nt(stream: Stream, kind: str, a: int, b: int, c: int, m: int, n: int, k: int, scale_a: int = 0,
+                   scale_b: int = 0, scale_mode: int = SCALE_NONE):
+    """``C[m][n]`` (bf16) ``= A[m][k] * B[n][k]^T`` for ``1 <= m <= 16``: the decode GEMM, which streams ``b`` from
+    HBM once.  ``kind`` is ``"bf16"``, ``"fp8"`` (scales and ``scale_mode`` as :func:`gemm_fp8_nt`) or ``"mxfp4"``
+    (``scale_a[m][k / 32]`` and ``scale_b[n][k / 32]`` as :func:`gemm_mxfp4_nt`, ``scale_mode`` none).  Not
+    synchronised."""
+    _ck(lib().gsx_decode_gemm_nt(*_decode_args(stream, kind, a, b, c, m, n, k, scale_a, scale_b, scale_mode)),
+        "decode_gemm_nt")
+
+
+def decode_gemm_cfgs() -> dict[int, tuple[str, int, int, int]]:
+    """``{index: (name, bn, waves, inflight)}`` of the decode configurations, read from the library's table
+    (native/kernels/gemm_decode.hip): columns of a workgroup's strip, waves per workgroup, K-tiles a wave keeps in
+    flight."""
+    out: dict[int, tuple[str, int, int, int]] = {}
+    while (name := lib().gsx_decode_gemm_cfg_name(len(out))) is not None:
+        v = [ctypes.c_int(0) for _ in range(3)]
+        if lib().gsx_decode_gemm_cfg_shape(len(out), *map(ctypes.byref, v)) != 0:
+            raise HipError(f"decode cfg {len(out)} has a name and no shape")
+        out[len(out)] = (name.decode(), *(x.value for x in v))
+    return out
+
+
+def decode_gemm_nt_cfg(stream: Stream, kind: str, a: int, b: int, c: int, m: int, n: int, k: int, cfg: int,
+                       scale_a: int = 0, scale_b: int = 0, scale_mode: int = SCALE_NONE):
+    """Launch one configuration of the decode GEMM; an unknown config or a shape it cannot take raises HipError."""
+    _ck(lib().gsx_decode_gemm_nt_launch_cfg(*_decode_args(stream, kind, a, b, c, m, n, k, scale_a, scale_b,
+                                                          scale_mode), cfg), f"decode gemm cfg {cfg}")
+
+
+def time_decode_gemm(stream: Stream, kind: str, a: int, b: int, c: int, m: int, n: int, k: int, iters: int,
+                     scale_a: int = 0, scale_b: int = 0, scale_mode: int = SCALE_NONE) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_decode_gemm(*_decode_args(stream, kind, a, b, c, m, n, k, scale_a, scale_b, scale_mode),
+                                         iters, ctypes.byref(ms)), "time_decode_gemm")
+    return ms.value

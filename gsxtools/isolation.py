@@ -16,9 +16,14 @@ exact environment the device plugin's Allocate produces, in four scenarios:
 * ``noisy`` / ``noisy-partitioned``  pod 0 runs a small (latency-bound) GEMM
                     next to 3 pods running large GEMMs, without / with
                     partitions: pod 0's throughput relative to ``solo`` / ``solo64``
-                    is the interference the partition removes.
+                    is the interference the partition removes;
+* ``decode-noisy`` / ``decode-noisy-partitioned``  pod 0 runs the decode workload
+                    (``--batch`` rows against a ring of weights: bound by HBM bandwidth,
+                    which no CU mask partitions) next to 3 pods running large GEMMs.
 
-Reported per scenario: per-pod TFLOP/s, aggregate, and fairness (min/max).
+``--workload decode`` makes every pod of the other scenarios a decode pod.
+Reported per scenario: per-pod TFLOP/s, aggregate, and fairness (min/max); for
+decode pods also the TB/s of weight bytes they streamed.
 Run: ``python -m gsxtools.isolation --seconds 8``.
 """
 from __future__ import annotations
@@ -52,11 +57,13 @@ def pod_envs(n_pods: int, cus_each: int, gpu_total_gib: int, pod_gib: int, with_
 
 
 def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str,
-             dtype: str = "bf16") -> list[dict]:
+             dtype: str = "bf16", workload="gemm", batch: int = 8) -> list[dict]:
+    """``size`` and ``workload`` are one value for every pod or a list with one per pod."""
     start_at = time.time() + 20.0  # time for every process to import torch and warm up
     procs = []
     sizes = size if isinstance(size, list) else [size] * len(envs)
-    for e, sz in zip(envs, sizes):
+    workloads = workload if isinstance(workload, list) else [workload] * len(envs)
+    for e, sz, wl in zip(envs, sizes, workloads):
         env = dict(os.environ)
         env.update({k: v for k, v in e.items() if k not in ("GSX_CU_MASK", "HSA_CU_MASK")})
         if mask_mode in ("stream", "both") and "GSX_CU_MASK" in e:
@@ -70,6 +77,8 @@ def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str
         cmd = [sys.executable, "-m", "gsxtools.workload", "--total",
                e["SHARED_GPU_MEM_DEV"], "--allocated", e["SHARED_GPU_MEM_CONTAINER"], "--kernel", kernel,
                "--size", str(sz), "--seconds", str(seconds), "--dtype", dtype, "--json"]
+        if wl != "gemm":  # the default is left off the command line
+            cmd += ["--workload", wl, "--batch", str(batch)]
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                                       cwd=str(ROOT)))
     out = []
@@ -83,8 +92,18 @@ def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str
 
 def summarize(name: str, res: list[dict]) -> dict:
     t = [r["tflops"] for r in res]
-    return {"scenario": name, "pods": len(t), "per_pod_tflops": [round(x, 1) for x in t],
-            "aggregate_tflops": round(sum(t), 1), "fairness_min_over_max": round(min(t) / max(t), 3) if t else None}
+    out = {"scenario": name, "pods": len(t), "per_pod_tflops": [round(x, 1) for x in t],
+           "aggregate_tflops": round(sum(t), 1), "fairness_min_over_max": round(min(t) / max(t), 3) if t else None}
+    if any("tbps" in r for r in res):  # decode pods: the weight bytes they streamed; None for a GEMM pod
+        b = [r.get("tbps") for r in res]
+        out["per_pod_tbps"] = [None if x is None else round(x, 3) for x in b]
+        out["aggregate_tbps"] = round(sum(x for x in b if x is not None), 3)
+    return out
+
+
+SCENARIOS_DECODE_NOISY = ("decode-noisy", "decode-noisy-partitioned")
+SCENARIOS = ("solo", "shared", "partitioned", "env", "env-gsx", "solo-small", "solo64", "noisy", "noisy-partitioned",
+             *SCENARIOS_DECODE_NOISY)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -98,6 +117,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"],
                     help="the pods' GEMM operand type (mxfp4: with --kernel gsx only)")
     ap.add_argument("--size", type=int, default=8192)
+    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode"],
+                    help="what the pods run: the large GEMM, or the decode workload (--batch rows against a ring of "
+                         "--size x --size weights)")
+    ap.add_argument("--batch", type=int, default=8, choices=range(1, 17), metavar="1..16",
+                    help="the decode pods' activation rows")
     ap.add_argument("--small-size", type=int, default=2048)
     ap.add_argument("--scenarios",
                     default="solo,shared,partitioned,env,env-gsx,solo-small,solo64,noisy,noisy-partitioned")
@@ -109,32 +133,43 @@ def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     results = []
     for sc in a.scenarios.split(","):
+        if sc not in SCENARIOS:
+            raise SystemExit(f"unknown scenario {sc}")
         if sc == "solo":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, False)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "none", a.dtype)
+            res = run_pods(envs, a.seconds, a.kernel, a.size, "none", a.dtype, a.workload, a.batch)
         elif sc == "shared":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, False)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "none", a.dtype)
+            res = run_pods(envs, a.seconds, a.kernel, a.size, "none", a.dtype, a.workload, a.batch)
         elif sc == "partitioned":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, True)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "stream", a.dtype)
+            res = run_pods(envs, a.seconds, a.kernel, a.size, "stream", a.dtype, a.workload, a.batch)
         elif sc == "solo64":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, True)
-            res = run_pods(envs, a.seconds, a.kernel, a.small_size, "stream", a.dtype)
+            # what a partition is worth: to the small GEMM of `noisy`, or to a decode pod (its own size)
+            res = run_pods(envs, a.seconds, a.kernel, a.size if a.workload == "decode" else a.small_size, "stream",
+                           a.dtype, a.workload, a.batch)
         elif sc == "solo-small":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, False)
-            res = run_pods(envs, a.seconds, a.kernel, a.small_size, "none", a.dtype)
+            res = run_pods(envs, a.seconds, a.kernel, a.small_size, "none", a.dtype, a.workload, a.batch)
         elif sc in ("noisy", "noisy-partitioned"):
             masked = sc == "noisy-partitioned"
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, masked)
             sizes = [a.small_size] + [a.size] * (a.pods - 1)
-            res = run_pods(envs, a.seconds, a.kernel, sizes, "stream" if masked else "none", a.dtype)
+            res = run_pods(envs, a.seconds, a.kernel, sizes, "stream" if masked else "none", a.dtype, a.workload,
+                           a.batch)
+        elif sc in SCENARIOS_DECODE_NOISY:
+            masked = sc == "decode-noisy-partitioned"
+            envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, masked)
+            res = run_pods(envs, a.seconds, a.kernel, a.size, "stream" if masked else "none", a.dtype,
+                           ["decode"] + ["gemm"] * (a.pods - 1), a.batch)
         elif sc == "env":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, True)
-            res = run_pods(envs, a.seconds, "torch" if a.kernel == "gsx" else a.kernel, a.size, "env", a.dtype)
+            res = run_pods(envs, a.seconds, "torch" if a.kernel == "gsx" else a.kernel, a.size, "env", a.dtype,
+                           a.workload, a.batch)
         elif sc == "env-gsx":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, True)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "env", a.dtype)
+            res = run_pods(envs, a.seconds, a.kernel, a.size, "env", a.dtype, a.workload, a.batch)
         else:
             raise SystemExit(f"unknown scenario {sc}")
         s = summarize(sc, res)

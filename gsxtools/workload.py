@@ -20,6 +20,9 @@ main = _mod.main
 build_parser = _mod.build_parser
 parse_mask = _mod.parse_mask
 kernels_lib_path = _mod.kernels_lib_path
+matrix_bytes = _mod.matrix_bytes
+default_weights_bytes = _mod.default_weights_bytes
+ring_layers = _mod.ring_layers
 
 if __name__ == "__main__":
     sys.exit(main())

@@ -176,6 +176,37 @@ int gsx_event_time_gemm_mxfp4(void* stream, const void* A, const void* B, void* 
 // and Q are 16-B aligned.  Launches on `stream` and returns without synchronising.
 int gsx_quant_mxfp4(void* stream, const void* X, void* Q, void* S, int R, int K);
 
+// Decode GEMM (gemm_decode.hip): C[M][N] (bf16) = A[M][K] * B[N][K]^T with 1 <= M <= 16, a few activation rows against
+// weights that are read once, bound by HBM bandwidth.  B goes from global memory straight to the MFMA's registers; a
+// workgroup owns a strip of 16 (or 32) columns and its waves split K.  `kind` selects the operand format, each exactly
+// that of the family above with the same name:
+//   GSX_DECODE_BF16   A and B bf16; scale_a and scale_b NULL and scale_mode GSX_GEMM_SCALE_NONE; K % 64 == 0
+//   GSX_DECODE_FP8    A and B OCP e4m3; scale_a, scale_b and scale_mode as gsx_gemm_fp8_nt takes them (fp32, M and N
+//                     of them with GSX_GEMM_SCALE_ROW), c = bf16((acc * sa) * sb); K % 128 == 0
+//   GSX_DECODE_MXFP4  A and B e2m1, two per byte; scale_a[M][K / 32] (exactly M rows) and scale_b[N][K / 32] e8m0,
+//                     plain row-major, codes 1 .. 254, non-NULL and 16-B aligned; scale_mode NONE; K % 256 == 0
+// A, B and C are 16-B aligned and not NULL; N % 16 == 0.  Nothing is read of A or scale_a past row M - 1 and nothing
+// written of C past it.  Row offsets into B, scale_b and C are 64-bit (B may exceed 4 GiB); K is limited only by int.
+// Accumulation is fp32 with one rounding to bf16.  The result is deterministic and does not depend on where
+// workgroups run: there is no communication between them.  For general inputs the summation order (the K-tiles a
+// wave takes, then the waves in order) differs from that of gsx_gemm_*_nt, and so may the last bits.
+// Launches on `stream` and returns without synchronising; everything is validated before the first device call.
+// gsx_decode_gemm_nt picks a configuration by N and K alone (the rule is at decode_pick() in gemm_decode.hip).
+enum { GSX_DECODE_BF16 = 0, GSX_DECODE_FP8 = 1, GSX_DECODE_MXFP4 = 2 };
+int gsx_decode_gemm_nt(void* stream, int kind, const void* A, const void* B, void* C, int M, int N, int K,
+                       const void* scale_a, const void* scale_b, int scale_mode);
+// The decode configurations, one table for the three kinds: 0 "16/4w-f4", 1 "16/8w-f4", 2 "16/8w-f8", 3 "16/16w-f4",
+// 4 "32/8w-f4", 5 "16/8w-f4-nt" (non-temporal loads of B; ablation): columns of a strip (BN) / waves per workgroup -
+// K-tiles a wave keeps in flight.  _cfg_name returns NULL and _cfg_shape nonzero outside the table.  _launch_cfg
+// requires N % BN == 0 and otherwise what gsx_decode_gemm_nt requires.
+const char* gsx_decode_gemm_cfg_name(int cfg);
+int gsx_decode_gemm_cfg_shape(int cfg, int* bn, int* waves, int* inflight);
+int gsx_decode_gemm_nt_launch_cfg(void* stream, int kind, const void* A, const void* B, void* C, int M, int N, int K,
+                                  const void* scale_a, const void* scale_b, int scale_mode, int cfg);
+// elapsed milliseconds of `iters` back-to-back gsx_decode_gemm_nt on `stream`, by hip events (for benches)
+int gsx_event_time_decode_gemm(void* stream, int kind, const void* A, const void* B, void* C, int M, int N, int K,
+                               const void* scale_a, const void* scale_b, int scale_mode, int iters, float* ms);
+
 // HBM pre-flight memory test (memtest.hip).  The expected content of 16-byte word W = origin/16 + word index is
 // generated from (pattern, seed, invert, W) and never stored; `origin` is the byte offset of `base` in the whole
 // tested range, so a range tested chunk by chunk keeps globally unique content.

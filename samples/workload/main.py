@@ -15,13 +15,20 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   ``auto`` (default) takes the MFMA kernel when the library is there and says so when it falls back;
 * ``--dtype fp8`` runs the same loop on OCP e4m3 operands: the library's fp8 GEMM, or ``torch._scaled_mm``;
 * ``--dtype mxfp4`` runs it on MXFP4 operands (e2m1 with e8m0 block scales), made by quantising the random bf16
-  matrices with the library's ``gsx_quant_mxfp4``: the library's mxfp4 GEMM only, ``--kernel torch`` has none.
+  matrices with the library's ``gsx_quant_mxfp4``: the library's mxfp4 GEMM only, ``--kernel torch`` has none;
+* ``--workload decode`` is an inference server's decode phase instead of the large GEMM: ``--batch`` (1..16)
+  activation rows against a ring of ``--size`` x ``--size`` weight matrices, one launch per matrix and step.  The
+  ring (``--weights-gib``; 4 GiB or a quarter of the share) is larger than the 256 MiB Infinity Cache, so the weights
+  come from HBM every time: the work is bound by memory bandwidth, and the result reports ``tbps``, the weight and
+  weight-scale bytes streamed per second, next to ``tflops``.  The library's decode GEMM, or ``torch.matmul`` /
+  ``torch._scaled_mm`` on the same ring.
 """
 from __future__ import annotations
 
 import argparse
 import ctypes
 import json
+import math
 import os
 import sys
 import time
@@ -45,6 +52,29 @@ def kernels_lib_path() -> Path | None:
     return None
 
 
+DECODE_KINDS = {"bf16": 0, "fp8": 1, "mxfp4": 2}  # gsx_kernels.h: GSX_DECODE_*
+GIB = 1 << 30
+
+
+def matrix_bytes(dtype: str, n: int, k: int) -> int:
+    """Bytes of one ``n`` x ``k`` weight matrix with its scales: what one decode launch streams."""
+    if dtype == "mxfp4":
+        return n * k // 2 + n * k // 32
+    return n * k * (2 if dtype == "bf16" else 1)
+
+
+def default_weights_bytes(allocated_gib: float) -> int:
+    """The ring's size when ``--weights-gib`` is not given: 4 GiB, or a quarter of the pod's share if that is
+    smaller (no share: 4 GiB)."""
+    return min(4 * GIB, int(allocated_gib * GIB) // 4) if allocated_gib else 4 * GIB
+
+
+def ring_layers(weights_bytes: int, one_matrix_bytes: int) -> int:
+    """Matrices in the weight ring: enough to cover ``weights_bytes``, and never fewer than two, so that no launch
+    finds its matrix where the last launch left it."""
+    return max(2, math.ceil(weights_bytes / one_matrix_bytes))
+
+
 class Kernels:
     """The slice of libgsx_kernels.so (native/kernels/gsx_kernels.hip) the workload uses."""
 
@@ -62,6 +92,9 @@ class Kernels:
             L.gsx_gemm_mxfp4_nt.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
             L.gsx_quant_mxfp4.argtypes = [vp, vp, vp, vp, i32, i32]
             L.gsx_gemm_mxfp4_nt.restype = L.gsx_quant_mxfp4.restype = i32
+        if hasattr(L, "gsx_decode_gemm_nt"):  # likewise: an image built before the decode kernels
+            L.gsx_decode_gemm_nt.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32]
+            L.gsx_decode_gemm_nt.restype = i32
         L.gsx_last_error.argtypes, L.gsx_last_error.restype = [], ctypes.c_char_p
         self.L, self.path = L, path
 
@@ -102,6 +135,14 @@ class Kernels:
         self._ck(self.L.gsx_gemm_mxfp4_nt(s, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m, n, k,
                                           ctypes.c_void_p(sa), ctypes.c_void_p(sb)), "gemm_mxfp4_nt")
 
+    def decode_gemm(self, s, dtype: str, a: int, b: int, c: int, m: int, n: int, k: int, sa: int = 0, sb: int = 0):
+        """``c[m][n] = a[m][k] * b[n][k]^T`` for m <= 16; mxfp4 takes the e8m0 block scales, the others none."""
+        if not hasattr(self.L, "gsx_decode_gemm_nt"):
+            raise RuntimeError(f"{self.path} has no gsx_decode_gemm_nt: rebuild it")
+        self._ck(self.L.gsx_decode_gemm_nt(s, DECODE_KINDS[dtype], ctypes.c_void_p(a), ctypes.c_void_p(b),
+                                           ctypes.c_void_p(c), m, n, k, ctypes.c_void_p(sa), ctypes.c_void_p(sb), 0),
+                 "decode_gemm_nt")
+
     def sync(self, s):
         self._ck(self.L.gsx_stream_sync(s), "stream_sync")
 
@@ -109,9 +150,79 @@ class Kernels:
         self.L.gsx_stream_destroy(s)
 
 
+def decode_steps(torch, kl, gs, stream, dev, dtype: str, a, c, layers: int):
+    """``(step, sync)`` of the decode workload: the ring of ``layers`` weight matrices ``[n][k]`` (random normal, made
+    one at a time so that nothing larger than one matrix is ever held in bf16), and a step that multiplies the ``m``
+    activation rows ``a`` by each of them in turn into ``c``.  ``kl`` and ``gs`` are the library and its stream, or
+    None for torch's own GEMMs (on ``stream`` if there is one)."""
+    m, k = a.shape
+    n = c.shape[1]
+    wdt = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn, "mxfp4": torch.uint8}[dtype]
+    w = torch.empty(layers, n, k // 2 if dtype == "mxfp4" else k, device=dev, dtype=wdt)
+    if dtype == "mxfp4":  # the library's quantiser makes weights and activations; it takes any row count
+        ws = torch.empty(layers, n, k // 32, device=dev, dtype=torch.uint8)
+        qa = torch.empty(m, k // 2, device=dev, dtype=torch.uint8)
+        sa = torch.empty(m, k // 32, device=dev, dtype=torch.uint8)
+        torch.cuda.synchronize()
+        kl.quant_mxfp4(gs, a.data_ptr(), qa.data_ptr(), sa.data_ptr(), m, k)
+    for i in range(layers):
+        x = torch.randn(n, k, device=dev, dtype=torch.bfloat16)
+        if dtype == "mxfp4":
+            torch.cuda.synchronize()
+            kl.quant_mxfp4(gs, x.data_ptr(), w[i].data_ptr(), ws[i].data_ptr(), n, k)
+            kl.sync(gs)
+        else:
+            w[i].copy_(x.to(wdt))
+        del x
+    if kl is not None:
+        w_bytes = w[0].numel() * w.element_size()
+        if dtype == "mxfp4":
+            a_ptr, sa_ptr, s_bytes = qa.data_ptr(), sa.data_ptr(), ws[0].numel()
+        else:
+            a_ptr, sa_ptr, s_bytes, ws = a.data_ptr(), 0, 0, None
+
+        def step():
+            for i in range(layers):
+                kl.decode_gemm(gs, dtype, a_ptr, w.data_ptr() + i * w_bytes, c.data_ptr(), m, n, k, sa_ptr,
+                               ws.data_ptr() + i * s_bytes if ws is not None else 0)
+
+        def sync():
+            kl.sync(gs)
+
+        step.keep = (w, ws, a)  # the closures hold addresses, not tensors
+        return step, sync
+    one = torch.ones((), device=dev, dtype=torch.float32)
+
+    def matmul(i):
+        if dtype == "fp8":  # hipBLASLt's fp8 GEMM, unit per-tensor scales
+            torch._scaled_mm(a, w[i].t(), scale_a=one, scale_b=one, out_dtype=torch.bfloat16, out=c)
+        else:
+            torch.matmul(a, w[i].t(), out=c)
+
+    try:  # torch may refuse so skinny a shape: its message is the answer then
+        matmul(0)
+    except RuntimeError as e:
+        raise SystemExit(f"--kernel torch --workload decode --dtype {dtype} --batch {m}: {e}") from None
+
+    def step():
+        if stream is not None:
+            with torch.cuda.stream(stream):
+                for i in range(layers):
+                    matmul(i)
+        else:
+            for i in range(layers):
+                matmul(i)
+
+    def sync():
+        (stream or torch.cuda.current_stream()).synchronize()
+
+    return step, sync
+
+
 def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 8192, seconds: float = 0.0,
         iters: int = 0, report_every: float = 5.0, touch: bool = False, quiet: bool = False,
-        probe_limit: bool = False, dtype: str = "bf16") -> dict:
+        probe_limit: bool = False, dtype: str = "bf16", workload: str = "gemm", batch: int = 8,
+        weights_gib: float | None = None) -> dict:
     import torch
 
     lib_path = kernels_lib_path()
@@ -143,20 +254,36 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     m = n = k = size
     if dtype not in ("bf16", "fp8", "mxfp4"):
         raise SystemExit(f"--dtype {dtype}: bf16, fp8 or mxfp4")
+    if workload not in ("gemm", "decode"):
+        raise SystemExit(f"--workload {workload}: gemm or decode")
+    decode = workload == "decode"
+    if decode:
+        if not 1 <= batch <= 16:
+            raise SystemExit(f"--batch {batch}: 1..16")
+        m = batch
     if dtype == "mxfp4" and kernel != "gsx":
         raise SystemExit("--dtype mxfp4 needs the library's kernels (--kernel gsx): "
                          + ("torch has no such GEMM" if kl is not None else "libgsx_kernels.so was not found"))
     a = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
-    b = torch.randn(n, k, device=dev, dtype=torch.bfloat16)
+    if not decode:
+        b = torch.randn(n, k, device=dev, dtype=torch.bfloat16)
     c = torch.empty(m, n, device=dev, dtype=torch.bfloat16)
     if dtype == "fp8":  # OCP e4m3, the MI355X's format; the output stays bf16
-        a, b = a.to(torch.float8_e4m3fn), b.to(torch.float8_e4m3fn)
+        a = a.to(torch.float8_e4m3fn)
+        if not decode:
+            b = b.to(torch.float8_e4m3fn)
         one = torch.ones((), device=dev, dtype=torch.float32)
     own = None
     if kernel == "gsx":
         gs = hip_stream if hip_stream is not None else kl.stream(0)
         own = None if hip_stream is not None else gs
-
+    layers = 1
+    if decode:
+        weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
+        layers = ring_layers(weights_bytes, matrix_bytes(dtype, n, k))
+        step, sync = decode_steps(torch, kl if kernel == "gsx" else None, gs if kernel == "gsx" else None, stream, dev,
+                                  dtype, a, c, layers)
+    elif kernel == "gsx":
         gemm = kl.gemm_fp8 if dtype == "fp8" else kl.gemm
         if dtype == "mxfp4":  # quantise the random bf16 operands once; the loop runs on the result
             qa, qb = (torch.empty(r, k // 2, device=dev, dtype=torch.uint8) for r in (m, n))
@@ -198,7 +325,7 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     start_at = float(os.environ.get("GSX_START_AT", "0") or 0)
     if start_at:  # co-resident pods start their timed loops together (isolation bench)
         time.sleep(max(0.0, start_at - time.time()))
-    flops = 2.0 * m * n * k
+    flops = 2.0 * m * n * k * layers  # of one step: decode launches once per matrix of the ring
     done = 0
     t0 = last = time.perf_counter()
     last_done = 0
@@ -221,6 +348,9 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
            "kernels_lib": str(kl.path) if kl is not None else "",
            "visible_devices": os.environ.get("HIP_VISIBLE_DEVICES", ""),
            "device_total_bytes": torch.cuda.get_device_properties(dev).total_memory}
+    if decode:
+        out.update({"workload": workload, "batch": m, "layers": layers,
+                    "tbps": done * layers * matrix_bytes(dtype, n, k) / el / 1e12})
     if probe_limit and allocated:
         # the share is a ceiling: one more share-sized tensor must be refused by the caching allocator
         try:
@@ -248,6 +378,14 @@ def build_parser() -> argparse.ArgumentParser:
                     help="operand type of the GEMM: bf16, fp8 (OCP e4m3) or mxfp4 (e2m1 with e8m0 block scales, "
                          "quantised from bf16 by the library; --kernel gsx only); the output stays bf16")
     ap.add_argument("--size", type=int, default=8192)
+    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode"],
+                    help="gemm: one large square GEMM per step (compute-bound); decode: --batch activation rows "
+                         "against a ring of --size x --size weight matrices, one launch each (HBM-bandwidth-bound)")
+    ap.add_argument("--batch", type=int, default=8, choices=range(1, 17), metavar="1..16",
+                    help="--workload decode: the activation rows (M)")
+    ap.add_argument("--weights-gib", type=float, default=None,
+                    help="--workload decode: size of the weight ring (default 4, or a quarter of the share if that "
+                         "is smaller; never fewer than two matrices)")
     ap.add_argument("--seconds", type=float, default=0.0, help="0 = run forever (like the reference sample)")
     ap.add_argument("--iters", type=int, default=0)
     ap.add_argument("--touch", action="store_true")
@@ -259,7 +397,8 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     res = run(a.total, a.allocated, kernel=a.kernel, size=a.size, seconds=a.seconds, iters=a.iters, touch=a.touch,
-              quiet=a.json, probe_limit=a.probe_limit, dtype=a.dtype)
+              quiet=a.json, probe_limit=a.probe_limit, dtype=a.dtype, workload=a.workload, batch=a.batch,
+              weights_gib=a.weights_gib)
     print(json.dumps(res) if a.json else res, flush=True)
     return 0
 

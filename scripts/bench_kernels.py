@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Micro-benchmarks of the HIP kernels on one MI355X: bf16, fp8 and mxfp4 GEMM (ours vs torch/hipBLASLt), HBM fill,
-stamp/verify."""
+"""Micro-benchmarks of the HIP kernels on one MI355X: bf16, fp8 and mxfp4 GEMM (ours vs torch/hipBLASLt), the decode
+GEMM (every configuration vs torch and a read-bandwidth yardstick), HBM fill, stamp/verify."""
 import json
 import os
 import statistics
@@ -205,6 +205,129 @@ def gemm_mxfp4(size_list, iters=20, rounds=3):
     return out
 
 
+MEMTEST_RANDOM = 3  # gsx_kernels.h: the pattern the memory test's profile times
+DECODE_SHAPES = [(8192, 8192), (28672, 8192), (8192, 28672)]  # (N, K): square, an MLP's up and down projections
+
+
+def gemm_decode(shapes=DECODE_SHAPES, ms=(1, 4, 16), kinds=("bf16", "fp8", "mxfp4"), ring_bytes=(2 << 30) + 1, reps=3,
+                rounds=3):
+    """The decode GEMM on a ring of weight matrices of more than 2 GiB (the Infinity Cache holds 256 MiB: every launch
+    streams its matrix from HBM): every configuration, the dispatching entry point, and ``torch.matmul`` (bf16) or
+    ``torch._scaled_mm`` (fp8) on the same ring, interleaved in one process.  One timing is ``reps`` passes over the
+    ring between two events; reported are the median TB/s of weight and weight-scale bytes of ``rounds`` repeats and
+    their spread, (max - min) / median.  ``memtest_check_TBps`` is the yardstick: ``gsx_memtest_check``, which reads
+    and compares every word, over the same number of bytes, by the wall clock around the call (it synchronises)."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    one = torch.ones((), device="cuda", dtype=torch.float32)
+    for kind in kinds:
+        for n, k in shapes:
+            wcols = k // 2 if kind == "mxfp4" else k
+            per = n * wcols * (2 if kind == "bf16" else 1) + (n * k // 32 if kind == "mxfp4" else 0)
+            layers = max(2, -(-ring_bytes // per))
+            wdt = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn, "mxfp4": torch.uint8}[kind]
+            w = torch.empty(layers, n, wcols, device="cuda", dtype=wdt)
+            ws = torch.empty(layers, n, k // 32, device="cuda", dtype=torch.uint8) if kind == "mxfp4" else None
+            for i in range(layers):
+                x = torch.randn(n, k, device="cuda", dtype=torch.bfloat16)
+                if kind == "mxfp4":
+                    torch.cuda.synchronize()
+                    hip.quant_mxfp4(s, x.data_ptr(), w[i].data_ptr(), ws[i].data_ptr(), n, k)
+                    s.sync()
+                else:
+                    w[i].copy_(x.to(wdt))
+                del x
+            yard = hip.DeviceBuffer(0, (layers * per) & ~255)
+            hip.memtest_write(s, yard.addr(), yard.nbytes, 0, MEMTEST_RANDOM, 1)
+            s.sync()
+            for m in ms:
+                x = torch.randn(m, k, device="cuda", dtype=torch.bfloat16)
+                sa = 0
+                if kind == "mxfp4":
+                    qa = torch.empty(m, k // 2, device="cuda", dtype=torch.uint8)
+                    sat = torch.empty(m, k // 32, device="cuda", dtype=torch.uint8)
+                    torch.cuda.synchronize()
+                    hip.quant_mxfp4(s, x.data_ptr(), qa.data_ptr(), sat.data_ptr(), m, k)
+                    s.sync()
+                    a, sa = qa, sat.data_ptr()
+                else:
+                    a = x.to(wdt)
+                c = torch.empty(m, n, device="cuda", dtype=torch.bfloat16)
+                torch.cuda.synchronize()
+                wb, sb = w[0].numel() * w.element_size(), (ws[0].numel() if ws is not None else 0)
+
+                def ours(cfg):
+                    for i in range(layers):
+                        args = (s, kind, a.data_ptr(), w.data_ptr() + i * wb, c.data_ptr(), m, n, k)
+                        scales = (sa, ws.data_ptr() + i * sb if ws is not None else 0)
+                        if cfg is None:
+                            hip.decode_gemm_nt(*args, *scales)
+                        else:
+                            hip.decode_gemm_nt_cfg(*args, cfg, *scales)
+
+                def torch_pass():
+                    for i in range(layers):
+                        if kind == "fp8":
+                            torch._scaled_mm(a, w[i].t(), scale_a=one, scale_b=one, out_dtype=torch.bfloat16, out=c)
+                        else:
+                            torch.matmul(a, w[i].t(), out=c)
+
+                variants = {f"cfg{cfg}_{name}": (lambda cfg=cfg: ours(cfg))
+                            for cfg, (name, bn, _, _) in hip.decode_gemm_cfgs().items() if n % bn == 0}
+                variants["gsx"] = lambda: ours(None)
+                row = {"kind": kind, "m": m, "n": n, "k": k, "layers": layers, "ring_bytes": layers * per}
+                if kind != "mxfp4":
+                    try:
+                        with torch.cuda.stream(ts):
+                            torch_pass()
+                        ts.synchronize()
+                        variants["torch"] = torch_pass
+                    except RuntimeError as e:  # torch refuses the shape: said, not hidden
+                        row["torch_refused"] = str(e).splitlines()[0][:200]
+
+                def timed(fn):
+                    torch.cuda.synchronize()
+                    with torch.cuda.stream(ts):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(ts)
+                        for _ in range(reps):
+                            fn()
+                        e1.record(ts)
+                    e1.synchronize()
+                    return reps * layers * per / (e0.elapsed_time(e1) * 1e-3) / 1e12
+
+                def yardstick():
+                    s.sync()
+                    t0 = time.perf_counter()
+                    rep = hip.memtest_check(s, yard.addr(), yard.nbytes, 0, MEMTEST_RANDOM, 1)
+                    dt = time.perf_counter() - t0
+                    assert rep.bad_dwords == 0
+                    return yard.nbytes / dt / 1e12
+
+                runs = {name: [] for name in [*variants, "memtest_check"]}
+                for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                    for name, fn in variants.items():
+                        t = timed(fn)
+                        if r:
+                            runs[name].append(t)
+                    t = yardstick()
+                    if r:
+                        runs["memtest_check"].append(t)
+                for name, v in runs.items():
+                    med = statistics.median(v)
+                    row[f"{name}_TBps"] = round(med, 3)
+                    row[f"{name}_spread"] = round((max(v) - min(v)) / med, 3)
+                out.append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                del x, a, c
+            yard.free()
+            del w, ws
+            torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 def hbm(nbytes=16 << 30, reps=5):
     s = hip.Stream(0)
     buf = hip.DeviceBuffer(0, nbytes)
@@ -235,7 +358,7 @@ if __name__ == "__main__":
     sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (2048, 8192, 4096), (16384, 16384, 8192)]
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
-                "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "hbm": hbm}
+                "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "hbm": hbm}
     only = sys.argv[2].split(",") if len(sys.argv) > 2 else list(sections)  # [out.json [section,section..]]
     res = {name: sections[name]() for name in only}
     print(json.dumps(res))
