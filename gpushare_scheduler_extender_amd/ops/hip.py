@@ -111,6 +111,9 @@ def lib():
                 raise ImportError(f"{SO} missing; run `python native/build.py kernels`")
         L = ctypes.CDLL(str(SO))
         vp, u32p, u64, i32 = ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64, ctypes.c_int
+        # stream, kind, Q, K_cache, V_cache, block_table, seq_lens, O; B, Hq, Hkv, D, page, num_pages, table_stride,
+        # max_seq_len; scale, k_scale, v_scale; workspace, workspace_bytes
+        _attn_sig = [vp, i32] + [vp] * 6 + [i32] * 8 + [ctypes.c_float] * 3 + [vp, u64]
         sig = {
             "gsx_last_error": ([], ctypes.c_char_p),
             "gsx_device_count": ([ctypes.POINTER(i32)], i32),
@@ -154,6 +157,12 @@ def lib():
             "gsx_decode_gemm_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
             "gsx_event_time_decode_gemm": ([vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32,
                                             ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_decode_attn": (_attn_sig, i32),
+            "gsx_decode_attn_launch_cfg": ([*_attn_sig, i32, i32], i32),
+            "gsx_decode_attn_workspace_bytes": ([i32] * 5 + [ctypes.POINTER(u64)], i32),
+            "gsx_decode_attn_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_decode_attn_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 2, i32),
+            "gsx_event_time_decode_attn": ([*_attn_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
             "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
                                   i32),
@@ -585,4 +594,77 @@ def time_decode_gemm(stream: Stream, kind: str, a: int, b: int, c: int, m: int, 
     ms = ctypes.c_float(0)
     _ck(lib().gsx_event_time_decode_gemm(*_decode_args(stream, kind, a, b, c, m, n, k, scale_a, scale_b, scale_mode),
                                          iters, ctypes.byref(ms)), "time_decode_gemm")
+    return ms.value
+
+
+# ``kind`` of the decode attention (gsx_kernels.h): the type of the paged KV cache
+ATTN_KV_KINDS = {"bf16": 0, "fp8": 1}
+
+
+def _attn_args(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int, seq_lens: int, o: int,
+               b: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int, max_seq_len: int,
+               scale: float, k_scale: float, v_scale: float, workspace: int, workspace_bytes: int) -> tuple:
+    if kind not in ATTN_KV_KINDS:
+        raise ValueError(f"attention cache kind {kind!r}: one of {', '.join(ATTN_KV_KINDS)}")
+    return (stream.handle, ATTN_KV_KINDS[kind], *(ctypes.c_void_p(x) for x in (q, k_cache, v_cache, block_table,
+                                                                               seq_lens, o)),
+            b, hq, hkv, d, page, num_pages, table_stride, max_seq_len, scale, k_scale, v_scale,
+            ctypes.c_void_p(workspace), workspace_bytes)
+
+
+def decode_attn(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int, seq_lens: int,
+                o: int, b: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int,
+                max_seq_len: int, scale: float, k_scale: float = 1.0, v_scale: float = 1.0, workspace: int = 0,
+                workspace_bytes: int = 0):
+    """One decode step of grouped-query attention over a paged KV cache: ``o[b][hq][d]`` (bf16) from ``q[b][hq][d]``
+    (bf16) and the caches ``[num_pages][hkv][page][d]`` of ``kind`` ``"bf16"`` or ``"fp8"`` (OCP e4m3 with the
+    per-tensor factors ``k_scale`` and ``v_scale``), reached through ``block_table[b][table_stride]`` and
+    ``seq_lens[b]`` (int32, device addresses).  ``workspace`` is device memory of at least
+    :func:`decode_attn_workspace_bytes` bytes for the split-KV partials.  Not synchronised."""
+    _ck(lib().gsx_decode_attn(*_attn_args(stream, kind, q, k_cache, v_cache, block_table, seq_lens, o, b, hq, hkv, d,
+                                          page, num_pages, table_stride, max_seq_len, scale, k_scale, v_scale,
+                                          workspace, workspace_bytes)), "decode_attn")
+
+
+def decode_attn_workspace_bytes(b: int, hq: int, d: int, page: int, max_seq_len: int) -> int:
+    """Bytes of workspace :func:`decode_attn` can need for these arguments, whatever ``hkv`` (0: none)."""
+    n = ctypes.c_uint64(0)
+    _ck(lib().gsx_decode_attn_workspace_bytes(b, hq, d, page, max_seq_len, ctypes.byref(n)),
+        "decode_attn_workspace_bytes")
+    return n.value
+
+
+def decode_attn_cfgs() -> dict[int, tuple[str, int, int]]:
+    """``{index: (name, waves, inflight)}`` of the attention configurations, read from the library's table
+    (native/kernels/attn_decode.hip): waves per workgroup, tiles of 32 tokens a wave keeps in flight."""
+    out: dict[int, tuple[str, int, int]] = {}
+    while (name := lib().gsx_decode_attn_cfg_name(len(out))) is not None:
+        v = [ctypes.c_int(0) for _ in range(2)]
+        if lib().gsx_decode_attn_cfg_shape(len(out), *map(ctypes.byref, v)) != 0:
+            raise HipError(f"attention cfg {len(out)} has a name and no shape")
+        out[len(out)] = (name.decode(), *(x.value for x in v))
+    return out
+
+
+def decode_attn_cfg(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int, seq_lens: int,
+                    o: int, b: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int,
+                    max_seq_len: int, scale: float, cfg: int, splits: int, k_scale: float = 1.0, v_scale: float = 1.0,
+                    workspace: int = 0, workspace_bytes: int = 0):
+    """Launch one configuration of the decode attention with ``splits`` (1..64) splits of every sequence; the
+    workspace needs ``b * hq * splits * 520`` bytes when ``splits > 1``.  An unknown config raises HipError."""
+    _ck(lib().gsx_decode_attn_launch_cfg(*_attn_args(stream, kind, q, k_cache, v_cache, block_table, seq_lens, o, b,
+                                                     hq, hkv, d, page, num_pages, table_stride, max_seq_len, scale,
+                                                     k_scale, v_scale, workspace, workspace_bytes), cfg, splits),
+        f"decode attn cfg {cfg} splits {splits}")
+
+
+def time_decode_attn(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int, seq_lens: int,
+                     o: int, b: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int,
+                     max_seq_len: int, scale: float, iters: int, k_scale: float = 1.0, v_scale: float = 1.0,
+                     workspace: int = 0, workspace_bytes: int = 0) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_decode_attn(*_attn_args(stream, kind, q, k_cache, v_cache, block_table, seq_lens, o, b,
+                                                     hq, hkv, d, page, num_pages, table_stride, max_seq_len, scale,
+                                                     k_scale, v_scale, workspace, workspace_bytes), iters,
+                                         ctypes.byref(ms)), "time_decode_attn")
     return ms.value

@@ -19,11 +19,15 @@ exact environment the device plugin's Allocate produces, in four scenarios:
                     is the interference the partition removes;
 * ``decode-noisy`` / ``decode-noisy-partitioned``  pod 0 runs the decode workload
                     (``--batch`` rows against a ring of weights: bound by HBM bandwidth,
-                    which no CU mask partitions) next to 3 pods running large GEMMs.
+                    which no CU mask partitions) next to 3 pods running large GEMMs;
+* ``attn-noisy`` / ``attn-noisy-partitioned``  pod 0 runs the attention workload
+                    (``--batch`` sequences of ``--context`` tokens over a ring of paged KV
+                    caches: a gather over pages, bound by HBM bandwidth too) next to 3 pods
+                    running large GEMMs.
 
-``--workload decode`` makes every pod of the other scenarios a decode pod.
+``--workload decode`` or ``--workload attn`` makes every pod of the other scenarios such a pod.
 Reported per scenario: per-pod TFLOP/s, aggregate, and fairness (min/max); for
-decode pods also the TB/s of weight bytes they streamed.
+decode and attention pods also the TB/s of weight or KV bytes they streamed.
 Run: ``python -m gsxtools.isolation --seconds 8``.
 """
 from __future__ import annotations
@@ -41,6 +45,8 @@ from gpushare_scheduler_extender_amd.deviceplugin.devices import Device
 from gpushare_scheduler_extender_amd.k8s.objects import make_pod
 from gpushare_scheduler_extender_amd.models.profile import SHARED_GPU
 
+from . import workload as pod_workload
+
 ROOT = Path(__file__).resolve().parents[1]
 
 
@@ -57,8 +63,9 @@ def pod_envs(n_pods: int, cus_each: int, gpu_total_gib: int, pod_gib: int, with_
 
 
 def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str,
-             dtype: str = "bf16", workload="gemm", batch: int = 8) -> list[dict]:
-    """``size`` and ``workload`` are one value for every pod or a list with one per pod."""
+             dtype: str = "bf16", workload="gemm", batch: int = 8, attn_args: list[str] | None = None) -> list[dict]:
+    """``size`` and ``workload`` are one value for every pod or a list with one per pod; ``attn_args`` are the
+    command-line options an attention pod gets."""
     start_at = time.time() + 20.0  # time for every process to import torch and warm up
     procs = []
     sizes = size if isinstance(size, list) else [size] * len(envs)
@@ -79,6 +86,8 @@ def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str
                "--size", str(sz), "--seconds", str(seconds), "--dtype", dtype, "--json"]
         if wl != "gemm":  # the default is left off the command line
             cmd += ["--workload", wl, "--batch", str(batch)]
+        if wl == "attn":
+            cmd += attn_args or []
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                                       cwd=str(ROOT)))
     out = []
@@ -102,12 +111,20 @@ def summarize(name: str, res: list[dict]) -> dict:
 
 
 SCENARIOS_DECODE_NOISY = ("decode-noisy", "decode-noisy-partitioned")
+SCENARIOS_ATTN_NOISY = ("attn-noisy", "attn-noisy-partitioned")
 SCENARIOS = ("solo", "shared", "partitioned", "env", "env-gsx", "solo-small", "solo64", "noisy", "noisy-partitioned",
-             *SCENARIOS_DECODE_NOISY)
+             *SCENARIOS_DECODE_NOISY, *SCENARIOS_ATTN_NOISY)
+
+
+def attn_cmdline(a: argparse.Namespace) -> list[str]:
+    """The attention pods' options, as the workload's command line takes them."""
+    out = ["--context", str(a.context), "--heads", str(a.heads), "--kv-heads", str(a.kv_heads), "--kv-dtype",
+           a.kv_dtype, "--page", str(a.page)]
+    return out + (["--kv-gib", str(a.kv_gib)] if a.kv_gib is not None else [])
 
 
 def build_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser()
+    ap = pod_workload.BatchRangeParser()
     ap.add_argument("--pods", type=int, default=4)
     ap.add_argument("--cus", type=int, default=64)
     ap.add_argument("--pod-gib", type=int, default=64)
@@ -117,11 +134,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"],
                     help="the pods' GEMM operand type (mxfp4: with --kernel gsx only)")
     ap.add_argument("--size", type=int, default=8192)
-    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode"],
-                    help="what the pods run: the large GEMM, or the decode workload (--batch rows against a ring of "
-                         "--size x --size weights)")
-    ap.add_argument("--batch", type=int, default=8, choices=range(1, 17), metavar="1..16",
-                    help="the decode pods' activation rows")
+    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn"],
+                    help="what the pods run: the large GEMM, the decode workload (--batch rows against a ring of "
+                         "--size x --size weights), or the attention workload (--batch sequences of --context tokens)")
+    ap.add_argument("--batch", type=int, default=8, metavar="N",
+                    help="the decode pods' activation rows (1..16), or the attention pods' sequences (1..256, with "
+                         "--workload attn)")
+    pod_workload.add_attn_arguments(ap)
     ap.add_argument("--small-size", type=int, default=2048)
     ap.add_argument("--scenarios",
                     default="solo,shared,partitioned,env,env-gsx,solo-small,solo64,noisy,noisy-partitioned")
@@ -132,44 +151,54 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     results = []
+    own_size = a.workload in ("decode", "attn")  # pods whose work --size / --small-size does not scale
+
+    def run(*args):  # every scenario's pods get the attention options: only attention pods use them
+        return run_pods(*args, attn_args=attn_cmdline(a))
+
     for sc in a.scenarios.split(","):
         if sc not in SCENARIOS:
             raise SystemExit(f"unknown scenario {sc}")
         if sc == "solo":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, False)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "none", a.dtype, a.workload, a.batch)
+            res = run(envs, a.seconds, a.kernel, a.size, "none", a.dtype, a.workload, a.batch)
         elif sc == "shared":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, False)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "none", a.dtype, a.workload, a.batch)
+            res = run(envs, a.seconds, a.kernel, a.size, "none", a.dtype, a.workload, a.batch)
         elif sc == "partitioned":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, True)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "stream", a.dtype, a.workload, a.batch)
+            res = run(envs, a.seconds, a.kernel, a.size, "stream", a.dtype, a.workload, a.batch)
         elif sc == "solo64":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, True)
             # what a partition is worth: to the small GEMM of `noisy`, or to a decode pod (its own size)
-            res = run_pods(envs, a.seconds, a.kernel, a.size if a.workload == "decode" else a.small_size, "stream",
-                           a.dtype, a.workload, a.batch)
+            res = run(envs, a.seconds, a.kernel, a.size if own_size else a.small_size, "stream",
+                      a.dtype, a.workload, a.batch)
         elif sc == "solo-small":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, False)
-            res = run_pods(envs, a.seconds, a.kernel, a.small_size, "none", a.dtype, a.workload, a.batch)
+            res = run(envs, a.seconds, a.kernel, a.small_size, "none", a.dtype, a.workload, a.batch)
         elif sc in ("noisy", "noisy-partitioned"):
             masked = sc == "noisy-partitioned"
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, masked)
             sizes = [a.small_size] + [a.size] * (a.pods - 1)
-            res = run_pods(envs, a.seconds, a.kernel, sizes, "stream" if masked else "none", a.dtype, a.workload,
-                           a.batch)
+            res = run(envs, a.seconds, a.kernel, sizes, "stream" if masked else "none", a.dtype, a.workload,
+                      a.batch)
         elif sc in SCENARIOS_DECODE_NOISY:
             masked = sc == "decode-noisy-partitioned"
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, masked)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "stream" if masked else "none", a.dtype,
-                           ["decode"] + ["gemm"] * (a.pods - 1), a.batch)
+            res = run(envs, a.seconds, a.kernel, a.size, "stream" if masked else "none", a.dtype,
+                      ["decode"] + ["gemm"] * (a.pods - 1), a.batch)
+        elif sc in SCENARIOS_ATTN_NOISY:
+            masked = sc == "attn-noisy-partitioned"
+            envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, masked)
+            res = run(envs, a.seconds, a.kernel, a.size, "stream" if masked else "none", a.dtype,
+                      ["attn"] + ["gemm"] * (a.pods - 1), a.batch)
         elif sc == "env":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, True)
-            res = run_pods(envs, a.seconds, "torch" if a.kernel == "gsx" else a.kernel, a.size, "env", a.dtype,
-                           a.workload, a.batch)
+            res = run(envs, a.seconds, "torch" if a.kernel == "gsx" else a.kernel, a.size, "env", a.dtype,
+                      a.workload, a.batch)
         elif sc == "env-gsx":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, True)
-            res = run_pods(envs, a.seconds, a.kernel, a.size, "env", a.dtype, a.workload, a.batch)
+            res = run(envs, a.seconds, a.kernel, a.size, "env", a.dtype, a.workload, a.batch)
         else:
             raise SystemExit(f"unknown scenario {sc}")
         s = summarize(sc, res)

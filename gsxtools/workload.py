@@ -23,6 +23,12 @@ kernels_lib_path = _mod.kernels_lib_path
 matrix_bytes = _mod.matrix_bytes
 default_weights_bytes = _mod.default_weights_bytes
 ring_layers = _mod.ring_layers
+kv_layer_bytes = _mod.kv_layer_bytes
+kv_pages = _mod.kv_pages
+default_kv_bytes = _mod.default_kv_bytes
+kv_ring_layers = _mod.kv_ring_layers
+add_attn_arguments = _mod.add_attn_arguments
+BatchRangeParser = _mod._Parser
 
 if __name__ == "__main__":
     sys.exit(main())

@@ -207,6 +207,62 @@ int gsx_decode_gemm_nt_launch_cfg(void* stream, int kind, const void* A, const v
 int gsx_event_time_decode_gemm(void* stream, int kind, const void* A, const void* B, void* C, int M, int N, int K,
                                const void* scale_a, const void* scale_b, int scale_mode, int iters, float* ms);
 
+// Decode attention over a paged KV cache (attn_decode.hip): one new token per sequence, grouped-query attention in
+// which Hq query heads share Hkv KV heads in groups of G = Hq / Hkv.
+//   Q[B][Hq][D], O[B][Hq][D]              bf16, D == 128
+//   K_cache, V_cache [num_pages][Hkv][page][D]
+//                                         bf16 (GSX_ATTN_KV_BF16) or OCP e4m3 (GSX_ATTN_KV_FP8, torch.float8_e4m3fn),
+//                                         both the same; one (page, KV head) is a contiguous run of page * D elements
+//   block_table[B][table_stride]          int32, device memory: entry i of a row is the page of tokens i * page ..
+//   seq_lens[B]                           int32, device memory
+// Requirements: Hq % Hkv == 0 and G <= 16; page % 16 == 0 and 16 <= page <= 256; 1 <= max_seq_len <= table_stride *
+// page; every pointer non-NULL, Q, the caches, O and a workspace 16-B aligned, block_table and seq_lens 4-B aligned;
+// k_scale and v_scale (host floats, the per-tensor dequantisation factors of an e4m3 cache) exactly 1.0f for bf16.
+// A seq_lens[b] above max_seq_len is clamped to it (one below 0 to 0) and a page index into [0, num_pages) by an
+// unsigned min, so no input makes the kernel read outside the caches.  Offsets into the caches are 64-bit: a cache
+// may exceed 4 GiB.  Everything is validated before the first device call; launches on `stream` and returns without
+// synchronising.
+// Numerics, per (sequence, query head g), over the tokens t < seq_len:
+//   x[g][t] = (q_g . k_t) * (scale * k_scale * log2 e)   fp32; bf16 products accumulated in fp32 on
+//                                                        v_mfma_f32_16x16x32_bf16; e4m3 K and V are converted to
+//                                                        bf16 in registers, which is exact
+//   p = exp2(x - m)                                      fp32, m a running maximum
+//   l = sum of p                                         fp32, of the unrounded p
+//   P = bf16(p), round to nearest even                   the operand of the PV MFMA, accumulated in fp32
+//   O = bf16((acc / l) * v_scale)                        rounded once
+// Partial results are triples (m, l, acc), merged in fp32 in a fixed order: the tiles of 32 tokens a wave takes, the
+// waves of a workgroup by index, then the splits by index; a partial without a token has m = -inf, l = 0 and weight
+// 0.  A sequence of length 0 gives a row of zeros.  Slots at or past seq_len and block-table entries past the last
+// used page contribute nothing, whatever the cache holds there (NaN and inf included): their x is replaced by -inf
+// and their V by zeros.  The result is deterministic and does not depend on where workgroups run: nothing passes
+// between workgroups inside a launch.  It depends on `splits`.
+// Split-KV: with splits > 1 each (sequence, KV head) is cut into `splits` runs of tiles, the partials go to
+// `workspace` (B * Hq * splits * 520 bytes) and a second small launch on the same stream merges them; with
+// splits == 1 there is one launch and the workspace is not used (it may be NULL).  gsx_decode_attn picks the
+// configuration and `splits` from B * Hkv and max_seq_len alone (attn_pick() in attn_decode.hip);
+// gsx_decode_attn_workspace_bytes returns what it can need for these arguments with any legal Hkv.
+enum { GSX_ATTN_KV_BF16 = 0, GSX_ATTN_KV_FP8 = 1 };
+int gsx_decode_attn(void* stream, int kind, const void* Q, const void* K_cache, const void* V_cache,
+                    const void* block_table, const void* seq_lens, void* O, int B, int Hq, int Hkv, int D, int page,
+                    int num_pages, int table_stride, int max_seq_len, float scale, float k_scale, float v_scale,
+                    void* workspace, uint64_t workspace_bytes);
+int gsx_decode_attn_workspace_bytes(int B, int Hq, int D, int page, int max_seq_len, uint64_t* bytes);
+// The attention configurations, one table for both cache types: 0 "4w-f1", 1 "4w-f2", 2 "8w-f1", 3 "8w-f2": waves per
+// workgroup - tiles of 32 tokens a wave keeps in flight.  _cfg_name returns NULL and _cfg_shape nonzero outside the
+// table.  _launch_cfg takes 1 <= splits <= 64 and otherwise what gsx_decode_attn takes; a workspace that is too
+// small for `splits` is refused with the bytes needed in the text.
+const char* gsx_decode_attn_cfg_name(int cfg);
+int gsx_decode_attn_cfg_shape(int cfg, int* waves, int* inflight);
+int gsx_decode_attn_launch_cfg(void* stream, int kind, const void* Q, const void* K_cache, const void* V_cache,
+                               const void* block_table, const void* seq_lens, void* O, int B, int Hq, int Hkv, int D,
+                               int page, int num_pages, int table_stride, int max_seq_len, float scale, float k_scale,
+                               float v_scale, void* workspace, uint64_t workspace_bytes, int cfg, int splits);
+// elapsed milliseconds of `iters` back-to-back gsx_decode_attn on `stream`, by hip events (for benches)
+int gsx_event_time_decode_attn(void* stream, int kind, const void* Q, const void* K_cache, const void* V_cache,
+                               const void* block_table, const void* seq_lens, void* O, int B, int Hq, int Hkv, int D,
+                               int page, int num_pages, int table_stride, int max_seq_len, float scale, float k_scale,
+                               float v_scale, void* workspace, uint64_t workspace_bytes, int iters, float* ms);
+
 // HBM pre-flight memory test (memtest.hip).  The expected content of 16-byte word W = origin/16 + word index is
 // generated from (pattern, seed, invert, W) and never stored; `origin` is the byte offset of `base` in the whole
 // tested range, so a range tested chunk by chunk keeps globally unique content.

@@ -21,7 +21,15 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   ring (``--weights-gib``; 4 GiB or a quarter of the share) is larger than the 256 MiB Infinity Cache, so the weights
   come from HBM every time: the work is bound by memory bandwidth, and the result reports ``tbps``, the weight and
   weight-scale bytes streamed per second, next to ``tflops``.  The library's decode GEMM, or ``torch.matmul`` /
-  ``torch._scaled_mm`` on the same ring.
+  ``torch._scaled_mm`` on the same ring;
+* ``--workload attn`` is the other half of a decode step: attention of one new token per sequence over a paged KV
+  cache.  ``--batch`` sequences (1..256) of ``--context`` tokens each, ``--heads`` query heads sharing ``--kv-heads``
+  KV heads at D = 128, pages of ``--page`` tokens handed out through a random permutation, as an allocator leaves
+  them after churn, in bf16 or e4m3 (``--kv-dtype``).  A server has one KV cache per layer: the workload keeps a ring
+  of per-layer caches (``--kv-gib``; 4 GiB or a quarter of the share, never fewer than two layers) and runs one
+  attention per layer and step, so a step streams more than the Infinity Cache.  It reports ``tbps`` (KV bytes read
+  per second) and ``tokens_per_s``.  The library's decode attention, or (``--kernel torch``, bf16 only)
+  ``scaled_dot_product_attention(enable_gqa=True)`` on a contiguous copy of the same data.
 """
 from __future__ import annotations
 
@@ -69,6 +77,31 @@ def default_weights_bytes(allocated_gib: float) -> int:
     return min(4 * GIB, int(allocated_gib * GIB) // 4) if allocated_gib else 4 * GIB
 
 
+ATTN_KV_KINDS = {"bf16": 0, "fp8": 1}  # gsx_kernels.h: GSX_ATTN_KV_*
+ATTN_D = 128
+
+
+def kv_layer_bytes(kv_dtype: str, batch: int, context: int, kv_heads: int) -> int:
+    """Bytes of K and V one attention launch reads: ``batch`` sequences of ``context`` tokens, D = 128."""
+    return 2 * batch * context * kv_heads * ATTN_D * (2 if kv_dtype == "bf16" else 1)
+
+
+def kv_pages(batch: int, context: int, page: int) -> tuple[int, int]:
+    """``(pages per sequence, pages of one layer's cache)``: every sequence owns whole pages."""
+    per_seq = math.ceil(context / page)
+    return per_seq, batch * per_seq
+
+
+def default_kv_bytes(allocated_gib: float) -> int:
+    """The KV ring's size when ``--kv-gib`` is not given: as :func:`default_weights_bytes`."""
+    return default_weights_bytes(allocated_gib)
+
+
+def kv_ring_layers(kv_bytes: int, one_layer_bytes: int) -> int:
+    """Per-layer caches in the ring: enough to cover ``kv_bytes``, never fewer than two."""
+    return ring_layers(kv_bytes, one_layer_bytes)
+
+
 def ring_layers(weights_bytes: int, one_matrix_bytes: int) -> int:
     """Matrices in the weight ring: enough to cover ``weights_bytes``, and never fewer than two, so that no launch
     finds its matrix where the last launch left it."""
@@ -95,6 +128,11 @@ class Kernels:
         if hasattr(L, "gsx_decode_gemm_nt"):  # likewise: an image built before the decode kernels
             L.gsx_decode_gemm_nt.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32]
             L.gsx_decode_gemm_nt.restype = i32
+        if hasattr(L, "gsx_decode_attn"):  # likewise: an image built before the attention kernel
+            L.gsx_decode_attn.argtypes = ([vp, i32] + [vp] * 6 + [i32] * 8 + [ctypes.c_float] * 3
+                                          + [vp, ctypes.c_uint64])
+            L.gsx_decode_attn_workspace_bytes.argtypes = [i32] * 5 + [ctypes.POINTER(ctypes.c_uint64)]
+            L.gsx_decode_attn.restype = L.gsx_decode_attn_workspace_bytes.restype = i32
         L.gsx_last_error.argtypes, L.gsx_last_error.restype = [], ctypes.c_char_p
         self.L, self.path = L, path
 
@@ -142,6 +180,23 @@ class Kernels:
         self._ck(self.L.gsx_decode_gemm_nt(s, DECODE_KINDS[dtype], ctypes.c_void_p(a), ctypes.c_void_p(b),
                                            ctypes.c_void_p(c), m, n, k, ctypes.c_void_p(sa), ctypes.c_void_p(sb), 0),
                  "decode_gemm_nt")
+
+    def attn_workspace_bytes(self, b: int, hq: int, page: int, max_seq_len: int) -> int:
+        if not hasattr(self.L, "gsx_decode_attn"):
+            raise RuntimeError(f"{self.path} has no gsx_decode_attn: rebuild it")
+        n = ctypes.c_uint64(0)
+        self._ck(self.L.gsx_decode_attn_workspace_bytes(b, hq, ATTN_D, page, max_seq_len, ctypes.byref(n)),
+                 "decode_attn_workspace_bytes")
+        return n.value
+
+    def decode_attn(self, s, kv_dtype: str, q: int, kc: int, vc: int, table: int, lens: int, o: int, b: int, hq: int,
+                    hkv: int, page: int, num_pages: int, table_stride: int, max_seq_len: int, scale: float, ws: int,
+                    ws_bytes: int):
+        """One decode step of attention over a paged KV cache (unit cache scales)."""
+        self._ck(self.L.gsx_decode_attn(s, ATTN_KV_KINDS[kv_dtype], *(ctypes.c_void_p(x) for x in
+                                                                      (q, kc, vc, table, lens, o)),
+                                        b, hq, hkv, ATTN_D, page, num_pages, table_stride, max_seq_len, scale, 1.0, 1.0,
+                                        ctypes.c_void_p(ws), ws_bytes), "decode_attn")
 
     def sync(self, s):
         self._ck(self.L.gsx_stream_sync(s), "stream_sync")
@@ -219,10 +274,68 @@ def decode_steps(torch, kl, gs, stream, dev, dtype: str, a, c, layers: int):
     return step, sync
 
 
+def attn_steps(torch, kl, gs, stream, dev, kv_dtype: str, batch: int, context: int, heads: int, kv_heads: int,
+               page: int, layers: int):
+    """``(step, sync)`` of the attention workload: a ring of ``layers`` paged KV caches (random normal), one block
+    table (a random permutation of a layer's pages: every layer has the same map and its own memory), and a step that
+    runs one attention per layer.  ``kl`` and ``gs`` are the library and its stream, or None for torch's SDPA on a
+    contiguous bf16 copy (on ``stream`` if there is one)."""
+    per_seq, pages = kv_pages(batch, context, page)
+    q = torch.randn(batch, heads, ATTN_D, device=dev, dtype=torch.bfloat16)
+    o = torch.empty_like(q)
+    scale = 1.0 / math.sqrt(ATTN_D)
+    if kl is None:
+        kc = torch.randn(layers, batch, kv_heads, context, ATTN_D, device=dev, dtype=torch.bfloat16)
+        vc = torch.randn(layers, batch, kv_heads, context, ATTN_D, device=dev, dtype=torch.bfloat16)
+        q4 = q.unsqueeze(2)  # [B][Hq][1][D]
+        sdpa = torch.nn.functional.scaled_dot_product_attention
+
+        def attend():
+            for i in range(layers):
+                o.copy_(sdpa(q4, kc[i], vc[i], scale=scale, enable_gqa=True).squeeze(2))
+
+        def step():
+            if stream is not None:
+                with torch.cuda.stream(stream):
+                    attend()
+            else:
+                attend()
+
+        def sync():
+            (stream or torch.cuda.current_stream()).synchronize()
+
+        return step, sync
+    kdt = torch.bfloat16 if kv_dtype == "bf16" else torch.float8_e4m3fn
+    kc = torch.empty(layers, pages, kv_heads, page, ATTN_D, device=dev, dtype=kdt)
+    vc = torch.empty_like(kc)
+    for i in range(layers):  # one layer at a time: nothing larger is ever held in bf16
+        for c in (kc, vc):
+            c[i].copy_(torch.randn(pages, kv_heads, page, ATTN_D, device=dev, dtype=torch.bfloat16).to(kdt))
+    table = torch.randperm(pages, device=dev).to(torch.int32).view(batch, per_seq).contiguous()
+    lens = torch.full((batch,), context, device=dev, dtype=torch.int32)
+    ws_bytes = kl.attn_workspace_bytes(batch, heads, page, context)
+    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+    layer_bytes = kc[0].numel() * kc.element_size()
+    torch.cuda.synchronize()
+
+    def step():
+        for i in range(layers):
+            kl.decode_attn(gs, kv_dtype, q.data_ptr(), kc.data_ptr() + i * layer_bytes,
+                           vc.data_ptr() + i * layer_bytes, table.data_ptr(), lens.data_ptr(), o.data_ptr(), batch,
+                           heads, kv_heads, page, pages, per_seq, context, scale, ws.data_ptr(), ws_bytes)
+
+    def sync():
+        kl.sync(gs)
+
+    step.keep = (q, o, kc, vc, table, lens, ws)  # the closures hold addresses, not tensors
+    return step, sync
+
+
 def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 8192, seconds: float = 0.0,
         iters: int = 0, report_every: float = 5.0, touch: bool = False, quiet: bool = False,
         probe_limit: bool = False, dtype: str = "bf16", workload: str = "gemm", batch: int = 8,
-        weights_gib: float | None = None) -> dict:
+        weights_gib: float | None = None, context: int = 8192, heads: int = 64, kv_heads: int = 8,
+        kv_dtype: str = "bf16", kv_gib: float | None = None, page: int = 16) -> dict:
     import torch
 
     lib_path = kernels_lib_path()
@@ -254,9 +367,22 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     m = n = k = size
     if dtype not in ("bf16", "fp8", "mxfp4"):
         raise SystemExit(f"--dtype {dtype}: bf16, fp8 or mxfp4")
-    if workload not in ("gemm", "decode"):
-        raise SystemExit(f"--workload {workload}: gemm or decode")
+    if workload not in ("gemm", "decode", "attn"):
+        raise SystemExit(f"--workload {workload}: gemm, decode or attn")
     decode = workload == "decode"
+    attn = workload == "attn"
+    if attn:
+        if not 1 <= batch <= 256:
+            raise SystemExit(f"--batch {batch}: 1..256 sequences")
+        if kv_dtype not in ATTN_KV_KINDS:
+            raise SystemExit(f"--kv-dtype {kv_dtype}: bf16 or fp8")
+        if kernel != "gsx" and kv_dtype != "bf16":
+            raise SystemExit("--kernel torch --workload attn runs scaled_dot_product_attention on bf16 only")
+        if context < 1 or heads < 1 or kv_heads < 1 or heads % kv_heads or heads // kv_heads > 16:
+            raise SystemExit("--workload attn: --context >= 1, --heads a multiple of --kv-heads, at most 16 times it")
+        if page % 16 or not 16 <= page <= 256:
+            raise SystemExit(f"--page {page}: a multiple of 16 in 16..256")
+        m, n, k = batch, heads, ATTN_D  # nothing of the GEMM's operands is needed: keep them tiny
     if decode:
         if not 1 <= batch <= 16:
             raise SystemExit(f"--batch {batch}: 1..16")
@@ -278,7 +404,14 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         gs = hip_stream if hip_stream is not None else kl.stream(0)
         own = None if hip_stream is not None else gs
     layers = 1
-    if decode:
+    if attn:
+        layer_bytes = kv_layer_bytes(kv_dtype, batch, context, kv_heads)
+        layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB), layer_bytes)
+        step, sync = attn_steps(torch, kl if kernel == "gsx" else None, gs if kernel == "gsx" else None, stream, dev,
+                                kv_dtype, batch, context, heads, kv_heads, page, layers)
+        # QK^T and PV: 2 * 2 * D flops per (sequence, query head, token)
+        flops_attn = 4.0 * batch * heads * context * ATTN_D * layers
+    elif decode:
         weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
         layers = ring_layers(weights_bytes, matrix_bytes(dtype, n, k))
         step, sync = decode_steps(torch, kl if kernel == "gsx" else None, gs if kernel == "gsx" else None, stream, dev,
@@ -326,6 +459,8 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     if start_at:  # co-resident pods start their timed loops together (isolation bench)
         time.sleep(max(0.0, start_at - time.time()))
     flops = 2.0 * m * n * k * layers  # of one step: decode launches once per matrix of the ring
+    if attn:
+        flops = flops_attn
     done = 0
     t0 = last = time.perf_counter()
     last_done = 0
@@ -351,6 +486,11 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     if decode:
         out.update({"workload": workload, "batch": m, "layers": layers,
                     "tbps": done * layers * matrix_bytes(dtype, n, k) / el / 1e12})
+    if attn:
+        out.update({"workload": workload, "batch": batch, "layers": layers, "context": context, "heads": heads,
+                    "kv_heads": kv_heads, "kv_dtype": kv_dtype, "page": page,
+                    "tbps": done * layers * kv_layer_bytes(kv_dtype, batch, context, kv_heads) / el / 1e12,
+                    "tokens_per_s": done * batch / el})
     if probe_limit and allocated:
         # the share is a ceiling: one more share-sized tensor must be refused by the caching allocator
         try:
@@ -366,9 +506,36 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     return out
 
 
+class _Parser(argparse.ArgumentParser):
+    """``--batch`` has a range per workload: 1..16 rows (gemm ignores it, decode uses it), 1..256 sequences for attn,
+    also where only an ``attn-*`` scenario of the isolation harness (its ``--scenarios``) runs an attention pod."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        scenarios = getattr(ns, "scenarios", "").split(",")
+        top = 256 if ns.workload == "attn" or any(sc.startswith("attn-") for sc in scenarios) else 16
+        if not 1 <= ns.batch <= top:
+            self.error(f"argument --batch: {ns.batch} is not in 1..{top} (--workload {ns.workload})")
+        return ns
+
+
+def add_attn_arguments(ap: argparse.ArgumentParser) -> None:
+    """The options of ``--workload attn`` (shared with the isolation harness)."""
+    ap.add_argument("--context", type=int, default=8192, help="--workload attn: tokens of every sequence")
+    ap.add_argument("--heads", type=int, default=64, help="--workload attn: query heads")
+    ap.add_argument("--kv-heads", type=int, default=8, help="--workload attn: KV heads (groups of heads / kv-heads)")
+    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="--workload attn: type of the KV cache (fp8: OCP e4m3; --kernel gsx only)")
+    ap.add_argument("--kv-gib", type=float, default=None,
+                    help="--workload attn: size of the ring of per-layer KV caches (default 4, or a quarter of the "
+                         "share if that is smaller; never fewer than two layers)")
+    ap.add_argument("--page", type=int, default=16,
+                    help="--workload attn: tokens of a KV page (a multiple of 16 in 16..256)")
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = os.environ.get("GSX_ENV_PREFIX", "SHARED_GPU_MEM")
-    ap = argparse.ArgumentParser(description="GEMM loop inside the pod's GPU share (the gpushare sample workload)")
+    ap = _Parser(description="GEMM loop inside the pod's GPU share (the gpushare sample workload)")
     ap.add_argument("--total", type=float, default=float(os.environ.get(f"{p}_DEV", "0") or 0),
                     help="the GPU's gpu-mem (the device plugin's *_DEV env)")
     ap.add_argument("--allocated", type=float, default=float(os.environ.get(f"{p}_CONTAINER", "0") or 0),
@@ -378,11 +545,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="operand type of the GEMM: bf16, fp8 (OCP e4m3) or mxfp4 (e2m1 with e8m0 block scales, "
                          "quantised from bf16 by the library; --kernel gsx only); the output stays bf16")
     ap.add_argument("--size", type=int, default=8192)
-    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode"],
+    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn"],
                     help="gemm: one large square GEMM per step (compute-bound); decode: --batch activation rows "
-                         "against a ring of --size x --size weight matrices, one launch each (HBM-bandwidth-bound)")
-    ap.add_argument("--batch", type=int, default=8, choices=range(1, 17), metavar="1..16",
-                    help="--workload decode: the activation rows (M)")
+                         "against a ring of --size x --size weight matrices, one launch each (HBM-bandwidth-bound); "
+                         "attn: one decode step of attention per layer over a ring of paged KV caches")
+    ap.add_argument("--batch", type=int, default=8, metavar="N",
+                    help="--workload decode: the activation rows (M), 1..16; --workload attn: the sequences, 1..256")
+    add_attn_arguments(ap)
     ap.add_argument("--weights-gib", type=float, default=None,
                     help="--workload decode: size of the weight ring (default 4, or a quarter of the share if that "
                          "is smaller; never fewer than two matrices)")
@@ -398,7 +567,8 @@ def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     res = run(a.total, a.allocated, kernel=a.kernel, size=a.size, seconds=a.seconds, iters=a.iters, touch=a.touch,
               quiet=a.json, probe_limit=a.probe_limit, dtype=a.dtype, workload=a.workload, batch=a.batch,
-              weights_gib=a.weights_gib)
+              weights_gib=a.weights_gib, context=a.context, heads=a.heads, kv_heads=a.kv_heads, kv_dtype=a.kv_dtype,
+              kv_gib=a.kv_gib, page=a.page)
     print(json.dumps(res) if a.json else res, flush=True)
     return 0
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the HIP kernels on one MI355X: bf16, fp8 and mxfp4 GEMM (ours vs torch/hipBLASLt), the decode
-GEMM (every configuration vs torch and a read-bandwidth yardstick), HBM fill, stamp/verify."""
+GEMM (every configuration vs torch and a read-bandwidth yardstick), the decode attention over a paged KV cache (every
+configuration and split count vs torch SDPA and the same yardstick), HBM fill, stamp/verify."""
 import json
 import os
 import statistics
@@ -328,6 +329,133 @@ def gemm_decode(shapes=DECODE_SHAPES, ms=(1, 4, 16), kinds=("bf16", "fp8", "mxfp
     return out
 
 
+ATTN_SHAPES = [(1, 32768), (8, 8192), (64, 2048), (256, 1024)]  # (sequences, tokens each)
+ATTN_HEADS = [(64, 8), (32, 32)]  # (query heads, KV heads): groups of 8, and plain multi-head attention
+ATTN_SPLITS = (1, 2, 4, 8, 16, 32, 64)
+
+
+def attn_decode(shapes=ATTN_SHAPES, heads=ATTN_HEADS, kinds=("bf16", "fp8"), ring_bytes=(1 << 30) + 1, reps=3,
+                rounds=3, page=16, splits=ATTN_SPLITS):
+    """The decode attention on a ring of per-layer paged KV caches of more than 1 GiB (the Infinity Cache holds 256
+    MiB), pages of 16 tokens handed out through a random permutation: every configuration at every split count that
+    leaves a split a tile and the launch no more than 16384 workgroups, the dispatching entry point, and (bf16)
+    ``scaled_dot_product_attention(enable_gqa=True)`` on a contiguous copy of the same layers, interleaved in one
+    process.  One timing is ``reps`` passes over the ring between two events; reported are the median TB/s of KV bytes
+    of ``rounds`` repeats and their spread.  ``memtest_check_TBps`` is the read yardstick over the same number of
+    bytes, as in :func:`gemm_decode`: ONE call timed by the host's clock, report read-back included, so the fixed
+    host cost of a call of 0.25 to 1.5 ms makes it read low, by an amount that was not measured, and the comparison
+    favours the attention, which is timed by events over ``reps`` passes."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    d = 128
+    sdpa = torch.nn.functional.scaled_dot_product_attention
+    for kind in kinds:
+        kdt = torch.bfloat16 if kind == "bf16" else torch.float8_e4m3fn
+        for hq, hkv in heads:
+            for b, ctx in shapes:
+                per_seq = -(-ctx // page)
+                pages = b * per_seq
+                per = 2 * pages * hkv * page * d * (2 if kind == "bf16" else 1)
+                layers = max(2, -(-ring_bytes // per))
+                kc = torch.empty(layers, pages, hkv, page, d, device="cuda", dtype=kdt)
+                vc = torch.empty_like(kc)
+                for i in range(layers):
+                    for c in (kc, vc):
+                        c[i].copy_(torch.randn(pages, hkv, page, d, device="cuda", dtype=torch.bfloat16).to(kdt))
+                table = torch.randperm(pages, device="cuda").to(torch.int32).view(b, per_seq).contiguous()
+                lens = torch.full((b,), ctx, device="cuda", dtype=torch.int32)
+                q = torch.randn(b, hq, d, device="cuda", dtype=torch.bfloat16)
+                o = torch.empty_like(q)
+                ws = torch.empty(b * hq * max(splits) * 520, device="cuda", dtype=torch.uint8)
+                lb = kc[0].numel() * kc.element_size()
+                scale = d ** -0.5
+                yard = hip.DeviceBuffer(0, (layers * per) & ~255)
+                hip.memtest_write(s, yard.addr(), yard.nbytes, 0, MEMTEST_RANDOM, 1)
+                s.sync()
+
+                def ours(cfg, sp):
+                    for i in range(layers):
+                        args = (s, kind, q.data_ptr(), kc.data_ptr() + i * lb, vc.data_ptr() + i * lb,
+                                table.data_ptr(), lens.data_ptr(), o.data_ptr(), b, hq, hkv, d, page, pages, per_seq,
+                                ctx, scale)
+                        if cfg is None:
+                            hip.decode_attn(*args, 1.0, 1.0, ws.data_ptr(), ws.numel())
+                        else:
+                            hip.decode_attn_cfg(*args, cfg, sp, 1.0, 1.0, ws.data_ptr(), ws.numel())
+
+                tiles = -(-ctx // 32)
+                variants = {f"cfg{cfg}_{name}_s{sp}": (lambda cfg=cfg, sp=sp: ours(cfg, sp))
+                            for cfg, (name, _, _) in hip.decode_attn_cfgs().items() for sp in splits
+                            if sp <= tiles and b * hkv * sp <= 16384}
+                variants["gsx"] = lambda: ours(None, None)
+                row = {"kind": kind, "b": b, "context": ctx, "heads": hq, "kv_heads": hkv, "page": page,
+                       "layers": layers, "ring_bytes": layers * per}
+                if kind == "bf16":  # torch's SDPA on a contiguous copy of the same layers
+                    idx = table.long()
+                    kt, vt = (torch.stack([c[i][idx].permute(0, 2, 1, 3, 4).reshape(b, hkv, per_seq * page, d)[:, :, :ctx]
+                                           for i in range(layers)]).contiguous() for c in (kc, vc))
+                    q4 = q.unsqueeze(2)
+
+                    def torch_pass():
+                        for i in range(layers):
+                            o.copy_(sdpa(q4, kt[i], vt[i], scale=scale, enable_gqa=hq != hkv).squeeze(2))
+
+                    variants["torch"] = torch_pass
+
+                def timed(fn):
+                    torch.cuda.synchronize()
+                    with torch.cuda.stream(ts):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(ts)
+                        for _ in range(reps):
+                            fn()
+                        e1.record(ts)
+                    e1.synchronize()
+                    return reps * layers * per / (e0.elapsed_time(e1) * 1e-3) / 1e12
+
+                def yardstick():
+                    s.sync()
+                    t0 = time.perf_counter()
+                    rep = hip.memtest_check(s, yard.addr(), yard.nbytes, 0, MEMTEST_RANDOM, 1)
+                    dt = time.perf_counter() - t0
+                    assert rep.bad_dwords == 0
+                    return yard.nbytes / dt / 1e12
+
+                if kind == "bf16":  # the two agree (on the ring's last layer) before they are compared for speed
+                    torch.cuda.synchronize()  # the operands were made on torch's stream
+                    ours(None, None)
+                    s.sync()
+                    got = o.float().clone()
+                    torch.cuda.synchronize()
+                    with torch.cuda.stream(ts):
+                        torch_pass()
+                    torch.cuda.synchronize()
+                    row["max_abs_diff_vs_torch"] = round((got - o.float()).abs().max().item(), 5)
+                runs = {name: [] for name in [*variants, "memtest_check"]}
+                for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                    for name, fn in variants.items():
+                        t = timed(fn)
+                        if r:
+                            runs[name].append(t)
+                    t = yardstick()
+                    if r:
+                        runs["memtest_check"].append(t)
+                for name, v in runs.items():
+                    med = statistics.median(v)
+                    row[f"{name}_TBps"] = round(med, 3)
+                    row[f"{name}_spread"] = round((max(v) - min(v)) / med, 3)
+                out.append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                yard.free()
+                del kc, vc, table, lens, q, o, ws
+                if kind == "bf16":
+                    del kt, vt
+                torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 def hbm(nbytes=16 << 30, reps=5):
     s = hip.Stream(0)
     buf = hip.DeviceBuffer(0, nbytes)
@@ -358,7 +486,10 @@ if __name__ == "__main__":
     sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (2048, 8192, 4096), (16384, 16384, 8192)]
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
-                "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "hbm": hbm}
+                "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "attn_decode": attn_decode,
+                # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
+                "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
+                "hbm": hbm}
     only = sys.argv[2].split(",") if len(sys.argv) > 2 else list(sections)  # [out.json [section,section..]]
     res = {name: sections[name]() for name in only}
     print(json.dumps(res))
