@@ -1,7 +1,9 @@
 """Problems for the decode attention tests (native/kernels/attn_decode.hip): one new token per sequence, grouped-query
 attention over a paged KV cache in bf16 or e4m3, D = 128.
 
-Plain Python on torch and NumPy, no GPU.  Three things live here:
+Plain Python on torch and NumPy, no GPU.  These things live here (and :func:`pick`, the dispatcher's rule; the
+**window cases**, which are exact like the selection cases but weigh a run of tokens equally, so that a token
+counted twice or not at all shows, are described above :func:`window_spans`):
 
 * :func:`reference`, the fp64 attention of a :class:`Problem`, and :func:`twin`, a NumPy transcription of the numeric
   contract in ``gsx_kernels.h``: fp32 scores times ``scale * k_scale * log2 e``, ``exp2`` against a running maximum,
@@ -62,7 +64,15 @@ PARTIAL_BYTES = (D + 2) * 4  # workspace per (sequence, query head, split)
 CFGS = {0: ("4w-f1", 4, 1), 1: ("4w-f2", 4, 2), 2: ("8w-f1", 8, 1), 3: ("8w-f2", 8, 2)}
 ALL = [*CFGS, None]  # None: the dispatching entry point
 SPLITS = (1, 2, 3, 8)
+MORE_SPLITS = (16, 32, 37, 64)  # what the dispatcher can also choose: run on a shorter list of lengths
 DISPATCHED = 2  # the configuration gsx_decode_attn runs (attn_pick() in attn_decode.hip)
+
+
+def pick(pairs: int, max_seq_len: int) -> int:
+    """The split count ``gsx_decode_attn`` runs for ``pairs`` (sequence, KV head) pairs: a transcription of
+    ``attn_pick()``.  One workgroup for each of 256 CUs, but every wave of a split keeps 4 tiles, and at most 64."""
+    tiles = -(-max_seq_len // TILE)
+    return max(min(-(-256 // pairs), tiles // (4 * CFGS[DISPATCHED][1]), MAX_SPLITS), 1)
 
 
 @functools.lru_cache(maxsize=None)
@@ -91,6 +101,7 @@ class Problem:
     v_scale: float = 1.0
     want: torch.Tensor | None = None
     page_base: int = 0  # the caches here hold physical pages page_base .. only (a cache too large for the host)
+    beyond: int = 0  # pages at the end of the caches that ``num_pages`` does not count (:func:`page_clamp_problem`)
 
     @property
     def b(self) -> int:
@@ -114,7 +125,7 @@ class Problem:
 
     @property
     def num_pages(self) -> int:
-        return self.page_base + self.k_cache.shape[0]
+        return self.page_base + self.k_cache.shape[0] - self.beyond
 
     @property
     def table_stride(self) -> int:
@@ -125,15 +136,26 @@ class Problem:
         return [min(max(int(x), 0), self.max_seq_len) for x in self.seq_lens]
 
     def gather(self, b: int, dtype=np.float64, scaled: bool = True) -> tuple[np.ndarray, np.ndarray]:
-        """``K[Hkv][len][D]`` and ``V[Hkv][len][D]`` of sequence ``b``, through its block table: dequantised, or
-        (``scaled=False``) the stored values."""
+        """``K[Hkv][len][D]`` and ``V[Hkv][len][D]`` of sequence ``b``, through its block table (a page index at or
+        above ``num_pages`` names the last page, as the contract has it): dequantised, or (``scaled=False``) the
+        stored values."""
         n = self.lens()[b]
         t = np.arange(n)
-        pages = self.block_table[b].numpy()[t // self.page] - self.page_base
+        pages = np.minimum(self.block_table[b].numpy()[t // self.page], self.num_pages - 1) - self.page_base
         slots = t % self.page
-        k = self.k_cache[pages, :, slots].to(torch.float64).numpy() * (self.k_scale if scaled else 1.0)
-        v = self.v_cache[pages, :, slots].to(torch.float64).numpy() * (self.v_scale if scaled else 1.0)  # [len][Hkv][D]
+        k = _float64(self.k_cache[pages, :, slots]) * (self.k_scale if scaled else 1.0)
+        v = _float64(self.v_cache[pages, :, slots]) * (self.v_scale if scaled else 1.0)  # [len][Hkv][D]
         return k.transpose(1, 0, 2).astype(dtype), v.transpose(1, 0, 2).astype(dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def _fp8_values() -> np.ndarray:
+    return torch.arange(256, dtype=torch.uint8).view(FP8).to(torch.float64).numpy()
+
+
+def _float64(t: torch.Tensor) -> np.ndarray:
+    """The values of a piece of a cache; e4m3 through a table of the 256 codes (torch converts them one by one)."""
+    return _fp8_values()[t.view(torch.uint8).numpy()] if t.dtype == FP8 else t.to(torch.float64).numpy()
 
 
 def reference(p: Problem) -> np.ndarray:
@@ -160,8 +182,15 @@ def _bf16_round(x: np.ndarray) -> np.ndarray:
     return to_bf16(x).float().numpy()
 
 
-def twin(p: Problem, tile: int = TILE) -> torch.Tensor:
-    """The contract in NumPy, fp32 throughout, in tiles of ``tile`` tokens: bf16 ``[B][Hq][D]``."""
+def tile_ranges(n: int, tile: int = TILE) -> list[tuple[int, int]]:
+    """The tiles of a sequence of ``n`` tokens as ``(first token, one past the last)``, in order."""
+    return [(t0, min(t0 + tile, n)) for t0 in range(0, n, tile)]
+
+
+def twin(p: Problem, tile: int = TILE, ranges=None) -> torch.Tensor:
+    """The contract in NumPy, fp32 throughout, in tiles of ``tile`` tokens: bf16 ``[B][Hq][D]``.  ``ranges(b, n)``, if
+    given, names the runs of tokens that sequence b visits instead of :func:`tile_ranges` (none of them empty): a twin
+    that counts tokens wrongly, for the tests of the tests (:func:`miscounts`)."""
     out = np.zeros((p.b, p.hq, D), dtype=np.float32)
     q = p.q.float().numpy().reshape(p.b, p.hkv, p.g, D)
     c = np.float32(np.float32(np.float32(p.scale) * np.float32(p.k_scale)) * np.float32(LOG2E))
@@ -172,8 +201,8 @@ def twin(p: Problem, tile: int = TILE) -> torch.Tensor:
         m = np.full((p.hkv, p.g), -np.inf, dtype=np.float32)
         l = np.zeros((p.hkv, p.g), dtype=np.float32)
         acc = np.zeros((p.hkv, p.g, D), dtype=np.float32)
-        for t0 in range(0, n, tile):
-            kt, vt = k[:, t0:t0 + tile], v[:, t0:t0 + tile]
+        for t0, t1 in tile_ranges(n, tile) if ranges is None else ranges(b, n):
+            kt, vt = k[:, t0:t1], v[:, t0:t1]
             x = (np.einsum("hgd,htd->hgt", q[b], kt).astype(np.float32) * c).astype(np.float32)
             mn = np.maximum(m, x.max(axis=2))
             with np.errstate(invalid="ignore"):
@@ -255,14 +284,15 @@ def pick_targets(n: int, page: int, cuts, heads: int, rot: int) -> list[int]:
 
 def selection_problem(kind: str, g: int, page: int, lens, *, tables: str = "scattered", hkv: int = 2, cuts=None,
                       extra_stride: int = 0, max_seq_len: int | None = None, over=(), shared: bool = False,
-                      k_scale: float = 1.0, v_scale: float = 1.0, page_base: int = 0) -> Problem:
+                      k_scale: float = 1.0, v_scale: float = 1.0, page_base: int = 0, below=None) -> Problem:
     """A selection case (module docstring) of ``len(lens)`` sequences.  The ``g * hkv`` heads of sequence b target
     the tokens of :func:`pick_targets` (``cuts``: per sequence, the first tokens of its splits), dealt to the KV heads
     in turn, the turn starting one KV head later every round (entry i goes to KV head ``(i + i // hkv) % hkv``): the
     two sides of a cut go to different KV heads, each KV head gets left sides and right sides, and each has targets
     along the whole sequence.  ``tables``: how physical pages are
     handed out; ``shared``: sequence 1 has sequence 0's block table (and must have its length); ``over``: sequences
-    whose ``seq_lens`` entry is raised above ``max_seq_len``, which the kernel clamps; ``extra_stride``: columns of
+    whose ``seq_lens`` entry is raised above ``max_seq_len``, which the kernel clamps; ``below``: ``{sequence: a
+    negative seq_lens entry}`` for sequences of length 0, which the kernel clamps to 0; ``extra_stride``: columns of
     the block table beyond the longest sequence's need; ``page_base``: every physical page index is raised by it and
     the returned caches hold the pages from there on only."""
     lens = list(lens)
@@ -316,6 +346,9 @@ def selection_problem(kind: str, g: int, page: int, lens, *, tables: str = "scat
     for b in over:
         assert lens[b] == max_seq_len
         seq_lens[b] = max_seq_len + 1 + 1000 * b
+    for b, value in (below or {}).items():
+        assert lens[b] == 0 and -2 ** 31 <= value < 0
+        seq_lens[b] = value
     q = np.tile(w[:g], (nb, hkv, 1)).reshape(nb, hq, D)
     kc, vc = torch.from_numpy(k), torch.from_numpy(v)
     kc, vc = (kc.bfloat16(), vc.bfloat16()) if kind == "bf16" else (kc.to(FP8), vc.to(FP8))
@@ -401,7 +434,8 @@ def split_cases(kind: str, cfg, splits: int) -> list[tuple[str, Problem]]:
 
 def table_cases(kind: str) -> list[tuple[str, Problem]]:
     """Reversed and scattered page orders, a table shared by two sequences, a ``table_stride`` larger than needed, a
-    batch that mixes 0 and short lengths with ``max_seq_len``, and ``seq_lens`` above ``max_seq_len``."""
+    batch that mixes 0 and short lengths with ``max_seq_len``, ``seq_lens`` above ``max_seq_len``, and ``seq_lens``
+    of -1 and -2^31 next to a live sequence (rows of zeros)."""
     fs = fp8_scales(kind)
     return [
         ("reversed", selection_problem(kind, 4, 16, [100, 37, 64], tables="reversed", **fs)),
@@ -410,7 +444,266 @@ def table_cases(kind: str) -> list[tuple[str, Problem]]:
         ("stride + 5", selection_problem(kind, 2, 16, [33, 70, 1], extra_stride=5, **fs)),
         ("mixed", selection_problem(kind, 4, 16, [0, 1100, 5, 0, 1100], max_seq_len=1100, **fs)),
         ("clamped", selection_problem(kind, 4, 16, [75, 20, 75], max_seq_len=75, over=(0, 2), **fs)),
+        ("negative", selection_problem(kind, 4, 16, [0, 90, 0], below={0: -1, 2: -2 ** 31}, **fs)),
     ]
+
+
+# ---- window cases -------------------------------------------------------------------------------------------------
+#
+# A selection case cannot tell whether a token was counted once: every weight is 0 or 1, so a token without a target
+# may be dropped or repeated, and a target taken twice gives l = 2 and acc = 2 v, which is v again.  A window case
+# gives head g a contiguous WINDOW of s tokens (s a power of two) with equal weights: ``k_t = 16 * sum of w_g`` over the
+# heads whose window holds t, so a token scores 261.2 for those heads and 0 for the others, p is exactly 1 inside the
+# window and exactly 0 outside, l = s, and every merge weight is exp2(0) or 0.  V is one-hot: token t holds the
+# small integer c(t) at d = t % 128 and zeros elsewhere, so
+#
+#     O[g][d] = (sum of c over the window's tokens with t % 128 == d) / s * v_scale
+#
+# which is exact in bf16 whatever the order (an integer below 256 over a power of two) and is compared on the raw 16
+# bits.  The windows of the G heads of a KV head cover the sequence, neighbours overlapping by at least a token:
+# every token counts in some head's l, and every boundary between two tokens (every cut of a split or a tile) lies
+# inside some head's window, so both sides' partials enter that head's row with weight exactly 1.
+
+def window_spans(n: int, g: int) -> tuple[int, list[int]]:
+    """``(s, starts)``: the window length of a sequence of ``n`` tokens under ``g`` heads and where the g windows
+    begin.  s is the largest power of two <= n below 128 tokens, otherwise 128 r with r the smallest power of two at
+    which g windows at even distances, the first at token 0 and the last ending at n - 1, overlap their neighbours by
+    a token or more.  r <= 64: a column of V holds at most 64 tokens of a window."""
+    if n < D:
+        s = 1 << (n.bit_length() - 1)
+    else:
+        fits = [D * r for r in (1, 2, 4, 8, 16, 32, 64) if n == D * r or (g > 1 and -(-(n - D * r) // (g - 1)) < D * r)]
+        assert fits, f"{g} windows of at most {64 * D} tokens do not cover {n}"
+        s = fits[0]
+    assert s == n or (g > 1 and -(-(n - s) // (g - 1)) < s), (n, g, s)
+    return s, [(i * (n - s)) // max(g - 1, 1) for i in range(g)]
+
+
+def window_weight_max(s: int) -> int:
+    """c(t) lies in 1 .. this.  A column's sum (s / 128 tokens, at least one) stays below 128, where a bf16 step is
+    at most 1/2: one token more or less moves its column by two steps or more.  At s = 8192 that leaves c = 1."""
+    return min(15, 127 // max(s // D, 1))
+
+
+def window_problem(kind: str, g: int, page: int, lens, *, hkv: int = 2, negative: bool = False,
+                   tables: str = "scattered", max_seq_len: int | None = None, k_scale: float = 1.0,
+                   v_scale: float = 1.0) -> Problem:
+    """A window case (above) of ``len(lens)`` sequences.  Head i of KV head h owns window ``(i + h) % g`` of
+    :func:`window_spans`.  ``negative``: ``k_t = -16 * (2 * sum of all w_g - sum of w_g over the heads whose window
+    holds t)``, which scores -261.2 inside a window and -522.4 outside: every score of the case is far below zero, so
+    a running maximum that starts at any finite value never comes down to them (G <= 8 keeps |k| <= 256, exact in
+    e4m3).  Poison as in :func:`selection_problem`: slots at or past ``seq_len`` and the pages nobody owns hold
+    ``k = 32 w``, which would win, and V = NaN."""
+    lens = list(lens)
+    nb, hq, w = len(lens), g * hkv, walsh()
+    assert not negative or g <= 8
+    max_seq_len = max(max(lens), 1) if max_seq_len is None else max_seq_len
+    assert all(n <= max_seq_len for n in lens)
+    npages = [-(-n // page) for n in lens]
+    used = sum(npages)
+    total = used + POISON_PAGES
+    order = _page_order(total, tables)
+    poison = np.array([int(x) for x in order[used:]], dtype=np.int32)
+    stride = max(-(-max_seq_len // page), 1)
+    table = np.empty((nb, stride), dtype=np.int32)
+    k = np.empty((total, hkv, page, D), dtype=np.float32)
+    v = np.full((total, hkv, page, D), np.nan, dtype=np.float32)
+    k[:] = 32 * w[np.arange(page) % g][None, None]
+    want = np.zeros((nb, hq, D))
+    every = w[:g].sum(axis=0)
+    at = 0
+    for b, n in enumerate(lens):
+        table[b] = poison[(b + np.arange(stride)) % POISON_PAGES]
+        table[b, :npages[b]] = order[at:at + npages[b]]
+        at += npages[b]
+        if n == 0:
+            continue
+        s, starts = window_spans(n, g)
+        t = np.arange(n)
+        pp, slot = table[b][t // page].astype(np.int64), t % page
+        for h in range(hkv):
+            c = (1 + (3 * t + t // D + 5 * h + 7 * b) % window_weight_max(s)).astype(np.float32)
+            held = np.zeros((n, D), dtype=np.float32)  # the sum of w_g over the heads whose window holds the token
+            for i in range(g):
+                a = starts[(i + h) % g]
+                held[a:a + s] += w[i]
+                want[b, h * g + i] = np.bincount(t[a:a + s] % D, weights=c[a:a + s], minlength=D) / s * v_scale
+            k[pp, h, slot] = -16 * (2 * every - held) if negative else 16 * held
+            rows = np.zeros((n, D), dtype=np.float32)
+            rows[t, t % D] = c
+            v[pp, h, slot] = rows
+    assert np.abs(k).max() <= 256 and np.array_equal(to_bf16(want).double().numpy(), want)  # exact in both types
+    q = np.tile(w[:g], (nb, hkv, 1)).reshape(nb, hq, D)
+    kc, vc = torch.from_numpy(k), torch.from_numpy(v)
+    kc, vc = (kc.bfloat16(), vc.bfloat16()) if kind == "bf16" else (kc.to(FP8), vc.to(FP8))
+    return Problem(kind, to_bf16(q), kc, vc, torch.from_numpy(table), torch.tensor(lens, dtype=torch.int32),
+                   max_seq_len, (1.0 / math.sqrt(D)) / k_scale, k_scale, v_scale, to_bf16(want))
+
+
+def to_fp8(p: Problem, k_scale: float = 0.5, v_scale: float = 2.0) -> Problem:
+    """An exact bf16 case with its caches stored as e4m3 under these scales (powers of two; every value of an exact
+    case is an e4m3 number): what its builder returns for "fp8", without building it again."""
+    assert p.kind == "bf16" and p.want is not None and p.k_scale == 1.0 and p.v_scale == 1.0
+    return dataclasses.replace(p, kind="fp8", k_cache=p.k_cache.float().to(FP8), v_cache=p.v_cache.float().to(FP8),
+                               scale=p.scale / k_scale, k_scale=k_scale, v_scale=v_scale,
+                               want=(p.want.float() * v_scale).bfloat16())
+
+
+def miscounts(n: int, tile: int = TILE) -> dict[str, list[tuple[int, int]]]:
+    """``{what: the runs of tokens a wrong kernel visits}`` for a sequence of ``n`` tokens (for :func:`twin`'s
+    ``ranges``): one tile taken twice and one left out, at the first, a middle and the last position; the second
+    16-token half of a middle tile left out; a single token left out and one taken twice.  Empty with one tile."""
+    base = tile_ranges(n, tile)
+    nt = len(base)
+    if nt < 2:
+        return {}
+    out = {}
+    for where, i in (("first", 0), ("middle", nt // 2), ("last", nt - 1)):
+        out[f"the {where} tile twice"] = base[:i + 1] + base[i:]
+        out[f"the {where} tile left out"] = base[:i] + base[i + 1:]
+    i = nt // 2 if base[nt // 2][1] - base[nt // 2][0] > 16 else nt // 2 - 1
+    t0, t1 = base[i]
+    out["a 16-token half left out"] = base[:i] + [(t0, t0 + 16)] + base[i + 1:]
+    x = t0 + 5
+    out["a token left out"] = base[:i] + [(t0, x), (x + 1, t1)] + base[i + 1:]
+    out["a token twice"] = base[:i + 1] + [(x, x + 1)] + base[i + 1:]
+    return out
+
+
+def window_split_cases(kind: str, cfg, splits: int) -> list[tuple[str, Problem]]:
+    """:func:`split_lengths` in batches of five, as :func:`split_cases` has them, as window cases at G = 16."""
+    return [(f"windows, lengths {lens}", window_problem(kind, 16, 16, lens, **fp8_scales(kind)))
+            for lens in chunks(split_lengths(cfg, splits))]
+
+
+def negative_cases(kind: str) -> list[tuple[str, Problem]]:
+    """Every score strictly negative (G = 8): one tile, ragged tiles, more than one wave's tiles, the steady loop."""
+    return [(f"negative scores, lengths {lens}", window_problem(kind, 8, 16, lens, negative=True, **fp8_scales(kind)))
+            for lens in ((1, 17, 33, 100, 600), (2033, 129))]
+
+
+# Head counts, page sizes and groups no other case has: (Hkv, page, G, lengths around a tile and a page boundary)
+OTHER_SHAPES = (
+    (1, 32, 3, (31, 33, 63, 65, 129)),
+    (3, 48, 7, (47, 49, 95, 97, 145)),
+    (8, 128, 12, (127, 129, 257)),
+    (3, 256, 12, (255, 257, 513)),
+    (8, 32, 7, (0, 1, 64, 97)),
+)
+
+
+def other_shape_cases(kind: str) -> list[tuple[str, Problem]]:
+    """``OTHER_SHAPES`` as window cases and as selection cases (addressing: a row of V names its page and slot)."""
+    out = []
+    for hkv, page, g, lens in OTHER_SHAPES:
+        name = f"Hkv {hkv}, page {page}, G {g}, lengths {lens}"
+        out.append((f"windows, {name}", window_problem(kind, g, page, lens, hkv=hkv, **fp8_scales(kind))))
+        out.append((f"selection, {name}", selection_problem(kind, g, page, lens, hkv=hkv, **fp8_scales(kind))))
+    return out
+
+
+def more_split_lengths(cfg: int, splits: int) -> list[int]:
+    """The lengths of a split count of ``MORE_SPLITS``: 1, W + 1 and 2 F W + 1 tiles per split (waves without a tile,
+    a ragged round, the steady loop and its drain), the last tile ragged, and the three lengths of
+    :func:`split_lengths` at which a split has no token, the last has one, and the last is one full tile."""
+    _, w, f = CFGS[cfg]
+    return sorted({n * splits * TILE - 15 for n in (1, w + 1, 2 * f * w + 1)}
+                  | {(splits - 1) * TILE - 3, 3 * (splits - 1) * TILE + 1, 3 * (splits - 1) * TILE + TILE})
+
+
+LONG = 8192  # a sequence above this gets a problem of its own: no host tensor much above 70 MB
+
+
+@functools.lru_cache(maxsize=8)
+def _window_case(kind: str, lens: tuple) -> Problem:
+    return window_problem(kind, 16, 16, lens, **fp8_scales(kind))
+
+
+def more_split_cases(kind: str, cfg: int, splits: int) -> list[tuple[str, Problem]]:
+    """:func:`more_split_lengths` as window cases at G = 16, Hkv = 2: the lengths up to ``LONG`` in one batch, every
+    longer one alone.  Configurations share lengths, so the last few problems are kept."""
+    lens = more_split_lengths(cfg, splits)
+    groups = [tuple(n for n in lens if n <= LONG), *((n,) for n in lens if n > LONG)]
+    return [(f"windows, lengths {list(group)}", _window_case(kind, group)) for group in groups if group]
+
+
+# The dispatcher at the smallest shapes where each of its rules decides: (name, Hkv, G, page, lengths, max_seq_len,
+# the split count).  max_seq_len alone sets the count; one sequence is that long (less 15 tokens: a ragged last tile),
+# the others are short, so the caches stay small.
+DISPATCH_SHAPES = (
+    ("the workload's default, 64 pairs", 8, 8, 16, (8177, 5, 0, 100, 33, 1, 700, 64), 8192, 4),
+    ("2 pairs, 4 tiles per wave decide", 2, 16, 64, (8177,), 8192, 8),
+    ("8 pairs, the profile's headline", 2, 8, 256, (40, 32753, 0, 300), 32768, 32),
+    ("7 pairs, an odd count", 1, 16, 256, (17, 37873, 0, 1, 255, 257, 90), 37888, 37),
+    ("4 pairs, the maximum", 1, 16, 256, (1, 65521, 64, 0), 65536, 64),
+    ("3 pairs, 86 wanted", 1, 16, 256, (100, 65521, 7), 65536, 64),
+)
+
+
+def dispatch_cases(shape) -> dict[str, list[tuple[str, Problem]]]:
+    """A window case and a selection case (targets on both sides of every cut of the dispatched split count) of one
+    row of ``DISPATCH_SHAPES``, per cache type; the e4m3 ones are the bf16 ones stored as e4m3."""
+    name, hkv, g, page, lens, max_seq_len, splits = shape
+    assert pick(len(lens) * hkv, max_seq_len) == splits
+    both = [(f"windows, {name}", window_problem("bf16", g, page, lens, hkv=hkv, max_seq_len=max_seq_len)),
+            (f"selection, {name}", selection_problem("bf16", g, page, lens, hkv=hkv, max_seq_len=max_seq_len,
+                                                     cuts=[split_cuts(n, splits) for n in lens]))]
+    return {"bf16": both, "fp8": [(what, to_fp8(p)) for what, p in both]}
+
+
+# ---- the contract's clamps and the e4m3 codes ---------------------------------------------------------------------
+
+def _raw(t: torch.Tensor) -> torch.Tensor:
+    return t.view(torch.uint8) if t.dtype == FP8 else t.view(torch.int16)
+
+
+def page_clamp_problem(kind: str) -> Problem:
+    """A page index at or above ``num_pages`` names page ``num_pages - 1``.  A selection case in which the block-table
+    entry of a page in use (tokens 48 .. 63 of sequence 0, between two other pages of it) is ``num_pages + 1`` and that
+    page's data lies in physical page ``num_pages - 1``; the caches hold three pages more than ``num_pages`` counts
+    (``Problem.beyond``), all poison.  A kernel that clamps is exact; one that does not reads poison inside the
+    allocation and fails the comparison, and nothing can fault.  A NEGATIVE page index is not tested: the unsigned
+    minimum turns it into the last page as well, but a kernel without the clamp would read in front of the caches."""
+    p = selection_problem(kind, 8, 16, [100, 37, 64], **fp8_scales(kind))
+    n, b, entry = p.num_pages, 0, 3
+    moved, spare = int(p.block_table[b, entry]), int(p.block_table[1, -1])  # spare: a poison page (37 tokens: 3 pages)
+    assert p.table_stride > 3 and bool(torch.isnan(p.v_cache[spare].float()).all())
+    perm = torch.arange(n)
+    perm[moved], perm[n - 1] = n - 1, moved  # the new page j holds the old page perm[j]
+    table = p.block_table.clone()
+    table[p.block_table == n - 1] = moved
+    table[b, entry] = n + 1
+    caches = [_raw(c)[torch.cat([perm, torch.full((3,), spare)])].view(c.dtype) for c in (p.k_cache, p.v_cache)]
+    return dataclasses.replace(p, k_cache=caches[0], v_cache=caches[1], block_table=table, beyond=3)
+
+
+def fp8_codes_problem() -> tuple[Problem, np.ndarray]:
+    """Every e4m3 code in V: ``(problem, codes[32][128])``.  A selection case of one sequence at G = 16, Hkv = 2 whose
+    32 heads target 32 different tokens; the target row of head j holds ``codes[j]``, in which each of the 254
+    codes that are no NaN stands at each of the 16 byte positions of a 16-B chunk (0x7F and 0xFF, the NaNs, are
+    replaced by 0x7E and 0xFE), subnormals, -0 and 448 among them.  Every other token holds other finite codes.
+    ``want`` is the value times ``v_scale``, exact in bf16; code 0x80 is -0 and the accumulate makes +0 of it, so
+    zeros are compared by value.  K is converted by the same function as V and the random cases test where its
+    operands land, so K has no sweep of its own."""
+    g, hkv, page, n = 16, 2, 16, 261
+    p = selection_problem("fp8", g, page, [n], **fp8_scales("fp8"))
+    hit = targets(p)[0]
+    assert len(set(hit)) == g * hkv
+    def finite(x):  # 0x7F and 0xFF, the NaNs, become 0x7E and 0xFE
+        return np.where(x % 128 == 127, x - 1, x).astype(np.uint8)
+
+    j, d = np.meshgrid(np.arange(g * hkv), np.arange(D), indexing="ij")
+    codes = finite((8 * j + d // 16 + 37 * (d % 16)) % 256)
+    t = np.arange(n)
+    pp, slot = p.block_table[0].numpy()[t // page].astype(np.int64), t % page
+    v = p.v_cache.view(torch.uint8).clone()
+    for h in range(hkv):
+        v[pp, h, slot] = torch.from_numpy(finite((29 * t[:, None] + 11 * np.arange(D)[None] + 7 * h) % 256))
+        for i in range(g):
+            tok = hit[h * g + i]
+            v[pp[tok], h, slot[tok]] = torch.from_numpy(codes[h * g + i])
+    want = (torch.from_numpy(codes).view(FP8).float() * p.v_scale).bfloat16()[None]
+    return dataclasses.replace(p, v_cache=v.view(FP8), want=want), codes
 
 
 # ---- random cases -------------------------------------------------------------------------------------------------
@@ -469,6 +762,10 @@ RANDOM_CASES = (  # (seed, G, page, lengths, q scale)
     (3, 4, 16, (1100, 95), 2.0),
     (4, 1, 64, (300, 31, 2), 2.0),
 )
+# Graded merge weights at 16, 32 and 64 splits (the window cases' are 0 or 1).  4096 tokens, two tiles to a split of
+# 64, is the longest length this case may have: there f is still below u / 4 max |v| and the twin inside the bound.
+RANDOM_MORE = (5, 8, 16, (4096, 45), 1.0)
+RANDOM_MORE_SPLITS = (16, 32, 64)
 
 
 def bits(t: torch.Tensor) -> torch.Tensor:
@@ -477,8 +774,11 @@ def bits(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
 
 
-def assert_bits_equal(got: torch.Tensor, want: torch.Tensor, what: str) -> None:
+def assert_bits_equal(got: torch.Tensor, want: torch.Tensor, what: str, zeros_by_value: bool = False) -> None:
+    """``zeros_by_value``: -0 and +0 count as equal; every other element has to match in all 16 bits."""
     g, w = bits(got.cpu()), bits(want)
+    if zeros_by_value:
+        g, w = g.masked_fill(g == 0x8000, 0), w.masked_fill(w == 0x8000, 0)
     bad = (g != w).nonzero()
     if len(bad):
         b, h, d = (int(x) for x in bad[0])

@@ -1,7 +1,9 @@
 """CPU checks for the decode attention (native/kernels/attn_decode.hip): the selection cases of
-``tests/attn_decode_cases.py`` against the fp64 reference and the NumPy twin of the numeric contract, the random cases'
-bound, the configuration table, every argument the entry points refuse, the tools' parsers and the size of the
-workload's KV ring.  No GPU: the refused calls never reach the device."""
+``tests/attn_decode_cases.py`` against the fp64 reference and the NumPy twin of the numeric contract, the window cases
+likewise and against twins that count a token twice or not at all, the random cases' bound, the dispatcher's rule
+against the library's workspace query, the configuration table, every argument the entry points refuse, the tools'
+parsers and the size of the workload's KV ring.  No GPU: the refused calls never reach the device."""
+import dataclasses
 import math
 
 import numpy as np
@@ -114,10 +116,219 @@ def test_targets_visit_every_boundary(kind):
     assert {t for row in ac.targets(few) for t in row} == set(marks)
 
 
+def _windows(p, b):
+    """``inside[Hkv][G][n]``: the tokens of sequence b that score a head's maximum, read back from Q and the K cache."""
+    k, _ = p.gather(b, scaled=False)
+    q = p.q.to(torch.float64).numpy().reshape(p.b, p.hkv, p.g, ac.D)[b]
+    x = np.einsum("hgd,htd->hgt", q, k)
+    return x == x.max(axis=2, keepdims=True), x
+
+
+def _windows_cover(name, p, split_counts, negative=False):
+    """Read back from the caches: every head's window is one run of s tokens (s a power of two, the same for the
+    heads of a sequence), all other tokens score 2048 less, the windows of every KV head cover the sequence, and
+    both sides of every cut of every split count in ``split_counts`` lie in one window."""
+    for b, n in enumerate(p.lens()):
+        if n == 0:
+            continue
+        inside, x = _windows(p, b)
+        s = int(inside[0, 0].sum())
+        assert s & (s - 1) == 0 and s == ac.window_spans(n, p.g)[0] and bool((inside.sum(axis=2) == s).all()), (name, b)
+        top = -2048 if negative else 2048
+        assert set(np.unique(x)) <= {top, top - 2048}, (name, b, np.unique(x))
+        for h in range(p.hkv):
+            for g in range(p.g):
+                (where,) = np.nonzero(inside[h, g])
+                assert where[-1] - where[0] == s - 1, (name, b, h, g)
+            assert bool(inside[h].any(axis=0).all()), f"{name}: sequence {b}, KV head {h}: a token that no head counts"
+            for splits in split_counts:
+                for cut in ac.split_cuts(n, splits):
+                    assert bool((inside[h, :, cut - 1] & inside[h, :, cut]).any()), (name, b, h, splits, cut)
+
+
+@pytest.mark.parametrize("cfg", ac.ALL, ids=lambda c: "dispatch" if c is None else str(c))
+@pytest.mark.parametrize("kind", ac.KINDS)
+def test_window_cases_of_the_splits_are_exact(kind, cfg):
+    """The lengths of ``split_lengths`` as window cases: exact, the windows cover, every cut lies inside a window."""
+    for splits in ac.SPLITS:
+        for name, p in ac.window_split_cases(kind, cfg, splits):
+            assert p.g == 16 and p.hkv == 2
+            _windows_cover(f"{kind} cfg {cfg} splits {splits}, {name}", p, (splits,))
+            _exact(f"{kind} cfg {cfg} splits {splits}, {name}", p, (16, 32) if splits == 1 else (32,))
+        assert sorted(n for _, p in ac.window_split_cases(kind, cfg, splits) for n in p.lens()) == \
+            ac.split_lengths(cfg, splits)
+
+
+@pytest.mark.parametrize("kind", ac.KINDS)
+def test_window_cases_with_negative_scores_and_of_other_shapes_are_exact(kind):
+    """The variant whose scores are all far below zero, and ``OTHER_SHAPES`` as window and as selection cases."""
+    for name, p in ac.negative_cases(kind):
+        assert p.g == 8
+        for b in range(p.b):
+            assert _windows(p, b)[1].max() == -2048  # -261.2 in the exp2 argument; the others -522.4
+        _windows_cover(f"{kind}, {name}", p, ac.SPLITS, negative=True)
+        _exact(f"{kind}, {name}", p)
+    cases = ac.other_shape_cases(kind)
+    assert {p.hkv for _, p in cases} == {1, 3, 8} and {p.page for _, p in cases} == {32, 48, 128, 256}
+    assert {p.g for _, p in cases} == {3, 7, 12}
+    for name, p in cases:
+        if name.startswith("windows"):
+            _windows_cover(f"{kind}, {name}", p, ac.SPLITS)
+        _exact(f"{kind}, {name}", p)
+
+
+MISCOUNT_LENGTHS = ((1, 2, 17, 33, 100), (129, 600, 2033), (4785,), (8433,))
+
+
+@pytest.mark.parametrize("kind", ac.KINDS)
+def test_a_miscounted_token_changes_a_window_case(kind):
+    """Why the window cases exist.  A twin that takes a tile twice or leaves one out (first, middle, last), leaves out
+    a 16-token half or a single token, or takes a token twice, changes the result of every sequence of more than one
+    tile, at the lengths where the ring's steady loop and drain run among them."""
+    seen = set()
+    for lens in MISCOUNT_LENGTHS:
+        p = ac.window_problem(kind, 16, 16, lens, **ac.fp8_scales(kind))
+        _exact(f"{kind}, lengths {lens}", p)
+        many = [b for b, n in enumerate(lens) if n > ac.TILE]
+        for what in ac.miscounts(max(lens)):
+            got = ac.twin(p, ranges=lambda b, n: ac.miscounts(n).get(what, ac.tile_ranges(n)))  # noqa: B023
+            for b in range(p.b):
+                same = torch.equal(ac.bits(got[b]), ac.bits(p.want[b]))
+                assert same == (b not in many), f"{kind}, {lens[b]} tokens, {what}: " + ("unseen" if same else "seen")
+            seen.add(what)
+    assert len(seen) == 9, seen
+
+
+def test_a_miscounted_tile_leaves_a_selection_case_as_it_is():
+    """The same twins on ``split_cases``: a tile taken twice changes nothing (l = 2, acc = 2 v), and neither does a
+    tile left out that holds no target.  The selection cases test addressing, not counting."""
+    doubled = dropped = 0
+    for splits in (1, 3):
+        for name, p in ac.split_cases("bf16", 2, splits):
+            hit = ac.targets(p)
+
+            def free(n, b):  # the ranges without the first tile that holds no target, if there is one
+                base = ac.tile_ranges(n)
+                for i, (t0, t1) in enumerate(base):
+                    if not any(t0 <= t < t1 for t in hit[b]):
+                        return base[:i] + base[i + 1:]
+                return base
+
+            for what in ("the first tile twice", "the middle tile twice", "the last tile twice"):
+                got = ac.twin(p, ranges=lambda b, n: ac.miscounts(n).get(what, ac.tile_ranges(n)))  # noqa: B023
+                ac.assert_bits_equal(got, p.want, f"splits {splits}, {name}, {what}")
+                doubled += sum(n > ac.TILE for n in p.lens())
+            got = ac.twin(p, ranges=lambda b, n: free(n, b))
+            ac.assert_bits_equal(got, p.want, f"splits {splits}, {name}, a tile without a target left out")
+            dropped += sum(len(free(n, b)) < len(ac.tile_ranges(n)) for b, n in enumerate(p.lens()))
+    assert doubled >= 25 and dropped >= 4, (doubled, dropped)
+
+
+@pytest.mark.parametrize("cfg", list(ac.CFGS))
+@pytest.mark.parametrize("kind", ac.KINDS)
+def test_window_cases_of_more_splits_are_exact(kind, cfg):
+    """16, 32, 37 and 64 splits: per split 1, W + 1 and 2 F W + 1 tiles, a split without a token, a last split of one
+    token and one of a full tile.  The twin at tile 16 as well where the sequences are short."""
+    _, w, f = ac.CFGS[cfg]
+    for splits in ac.MORE_SPLITS:
+        lens = ac.more_split_lengths(cfg, splits)
+        assert {-(-(-(-n // ac.TILE)) // splits) for n in lens} >= {1, 3, w + 1, 2 * f * w + 1}
+        assert any(-(-n // ac.TILE) < splits for n in lens)  # a split without a token
+        assert any(n - ac.split_cuts(n, splits)[-1] == 1 for n in lens)  # a last split of one token
+        assert any(n - ac.split_cuts(n, splits)[-1] == ac.TILE and len(ac.split_cuts(n, splits)) == splits - 1
+                   for n in lens)  # and of one full tile
+        cases = ac.more_split_cases(kind, cfg, splits)
+        assert sorted(n for _, p in cases for n in p.lens()) == lens
+        for name, p in cases:
+            assert max(p.k_cache.numel(), p.v_cache.numel()) * 4 <= 70 << 20 and (p.b == 1 or max(p.lens()) <= ac.LONG)
+            _windows_cover(f"{kind} cfg {cfg} splits {splits}, {name}", p, (splits,))
+            _exact(f"{kind} cfg {cfg} splits {splits}, {name}", p, (16, 32) if max(p.lens()) <= ac.LONG else (32,))
+
+
+@pytest.mark.parametrize("shape", ac.DISPATCH_SHAPES, ids=[s[0] for s in ac.DISPATCH_SHAPES])
+def test_dispatch_cases_are_exact(shape):
+    """The rows of ``DISPATCH_SHAPES``: ``pick()`` gives the split count the row names, the window case covers and has
+    every cut of that count inside a window, the selection case has targets on both sides of every such cut, and
+    both are exact for both cache types (the e4m3 ones are the bf16 ones stored as e4m3)."""
+    name, hkv, g, page, lens, max_seq_len, splits = shape
+    assert ac.pick(len(lens) * hkv, max_seq_len) == splits and max(lens) == max_seq_len - 15
+    cases = ac.dispatch_cases(shape)
+    for kind in ac.KINDS:
+        (_, win), (_, sel) = cases[kind]
+        assert win.kind == sel.kind == kind and win.max_seq_len == sel.max_seq_len == max_seq_len
+        for p in (win, sel):
+            assert (p.hkv, p.g, p.page, p.lens()) == (hkv, g, page, list(lens))
+        _exact(f"{kind}, windows, {name}", win, (32,))
+        _exact(f"{kind}, selection, {name}", sel, (32,))
+    _windows_cover(name, cases["bf16"][0][1], (splits,))
+    sel = cases["bf16"][1][1]
+    hit = ac.targets(sel)
+    for b, n in enumerate(lens):
+        cuts = ac.split_cuts(n, splits)
+        sides = {t for c in cuts for t in (c - 1, c)}
+        if g * hkv >= 2 * splits:  # enough heads for both sides of every cut
+            assert sides <= set(hit[b]), (name, b)
+        elif n == max(lens):  # otherwise every head of the long sequence, but two at most, sits at a cut
+            assert len(sides & set(hit[b])) >= g * hkv - 2, (name, b, sorted(hit[b]))
+
+
+def test_an_exact_case_stored_as_e4m3_is_the_builders():
+    for build in (lambda kind, fs: ac.window_problem(kind, 8, 32, [100, 0, 33], hkv=3, **fs),
+                  lambda kind, fs: ac.selection_problem(kind, 8, 32, [100, 0, 33], hkv=3, **fs)):
+        a, b = ac.to_fp8(build("bf16", {})), build("fp8", ac.fp8_scales("fp8"))
+        assert (a.kind, a.scale, a.k_scale, a.v_scale, a.max_seq_len) == (b.kind, b.scale, b.k_scale, b.v_scale,
+                                                                          b.max_seq_len)
+        for x, y in ((a.k_cache, b.k_cache), (a.v_cache, b.v_cache)):  # NaN where NaN is (its sign is free), else the byte
+            nan = torch.isnan(x.float())
+            assert x.dtype == y.dtype == ac.FP8 and torch.equal(nan, torch.isnan(y.float()))
+            assert torch.equal(x.view(torch.uint8)[~nan], y.view(torch.uint8)[~nan])
+        assert torch.equal(a.block_table, b.block_table) and torch.equal(ac.bits(a.want), ac.bits(b.want))
+
+
+@pytest.mark.parametrize("kind", ac.KINDS)
+def test_clamp_cases_are_exact(kind):
+    """``seq_lens`` below zero, and a page index at or above ``num_pages``."""
+    p = dict(ac.table_cases(kind))["negative"]
+    assert [int(x) for x in p.seq_lens] == [-1, 90, -2 ** 31] and p.lens() == [0, 90, 0]
+    assert not p.want[0].any() and not p.want[2].any() and bool(p.want[1].any())
+    c = ac.page_clamp_problem(kind)
+    assert c.k_cache.shape[0] == c.v_cache.shape[0] == c.num_pages + 3
+    over = (c.block_table >= c.num_pages).nonzero()
+    assert over.tolist() == [[0, 3]] and int(c.block_table[0, 3]) == c.num_pages + 1 and c.lens()[0] > 4 * c.page
+    assert bool(torch.isnan(c.v_cache[c.num_pages:].float()).all())  # poison beyond num_pages
+    assert not bool(torch.isnan(c.v_cache[c.num_pages - 1].float()).any())  # the page the clamp lands on is in use
+    _exact(f"{kind}, page index above num_pages", c)
+    # without the clamp the entry names a poison page inside the allocation, and the result is another
+    unclamped = ac.twin(dataclasses.replace(c, beyond=0))
+    assert not torch.equal(ac.bits(unclamped[0]), ac.bits(c.want[0])) and bool(torch.isnan(unclamped[0]).any())
+    assert torch.equal(ac.bits(unclamped[1:]), ac.bits(c.want[1:]))
+
+
+def test_fp8_codes_case_holds_every_code_at_every_byte_position():
+    p, codes = ac.fp8_codes_problem()
+    assert codes.shape == (32, 128) and p.kind == "fp8" and (p.g, p.hkv) == (16, 2)
+    finite = sorted(set(range(256)) - {0x7F, 0xFF})
+    for pos in range(16):
+        assert sorted(set(codes[:, pos::16].ravel().tolist())) == finite, pos
+    # the value of a code, from the format: sign, 4 bits of exponent with bias 7, 3 of mantissa; exponent 0 is subnormal
+    c = codes.astype(np.int64)
+    e, m = (c >> 3) & 15, c & 7
+    value = np.where(e == 0, m / 8 * 2.0 ** -6, (1 + m / 8) * 2.0 ** (e - 7)) * np.where(c & 128, -1.0, 1.0)
+    assert np.array_equal(p.want[0].double().numpy(), value * p.v_scale)
+    assert value.max() == 448 and np.abs(value[value != 0]).min() == 2.0 ** -9
+    v = p.v_cache.view(torch.uint8)
+    owned = ~torch.isnan(p.v_cache.float())
+    assert bool(owned.any()) and not bool(((v & 0x7F) == 0x7F)[owned].any())  # every owned slot is finite
+    ac.assert_bits_equal(ac.to_bf16(ac.reference(p)), p.want, "the fp64 reference", zeros_by_value=True)
+    for tile in (16, 32):
+        ac.assert_bits_equal(ac.twin(p, tile), p.want, f"the twin at tile {tile}", zeros_by_value=True)
+
+
 @pytest.mark.parametrize("kind", ac.KINDS)
 def test_random_cases_fit_the_bound(kind):
     """``f <= u / 4 max |v|`` (the bf16 terms dominate), and the twin is inside the bound at tiles of 16, 32 and 64."""
-    for case in ac.RANDOM_CASES:
+    assert max(ac.RANDOM_MORE[3]) == 4096  # the longest the case may be; the assertions below hold at it
+    for case in (*ac.RANDOM_CASES, ac.RANDOM_MORE):
         p = ac.random_problem(kind, *case)
         bound, rel, share = ac.error_bound(p)
         assert rel <= ac.U / 4 and share <= 1.0, (case, rel)
@@ -157,6 +368,36 @@ def test_attn_workspace_bytes(hip):
         v = {"b": 2, "hq": 8, "d": 128, "page": 16, "n": 100, **kw}
         with pytest.raises(hip.HipError, match=f"gsx_decode_attn_workspace_bytes: {text}"):
             hip.decode_attn_workspace_bytes(v["b"], v["hq"], v["d"], v["page"], v["n"])
+
+
+def test_pick_is_the_librarys_dispatch_rule(hip):
+    """``attn_decode_cases.pick`` against the library, through the workspace query alone (a launch is never used to
+    probe the rule: where one split is picked nothing would be refused).  With Hq <= 16 the query counts B pairs, so
+    its bytes over B * Hq * 520 are the split count, and 0 bytes mean one split.  Then "any legal Hkv": whatever Hkv
+    a caller passes with the B and Hq of the query, the dispatcher picks no more splits than the query allowed for."""
+    def query(b, hq, n):
+        got = hip.decode_attn_workspace_bytes(b, hq, 128, 16, n)
+        assert got % (b * hq * ac.PARTIAL_BYTES) == 0
+        return max(got // (b * hq * ac.PARTIAL_BYTES), 1)
+
+    lengths = sorted({1, 31, 33, 1000, 100000, 1 << 30}
+                     | {1024 * k + dn for k in range(1, 67) for dn in (-32, -31, -1, 0, 1)})  # around every 32 * 32 * k
+    seen = set()
+    for pairs in (*range(1, 9), 9, 31, 32, 33, 64, 255, 256, 257, 512):
+        for n in lengths:
+            want = ac.pick(pairs, n)
+            assert query(pairs, 16, n) == want, (pairs, n, want)
+            seen.add(want)
+        assert query(pairs, 5, 8192) == ac.pick(pairs, 8192)
+    assert seen >= {1, 2, 3, 4, 8, 32, 37, 43, 64} and max(seen) == ac.MAX_SPLITS
+    assert [ac.pick(*row) for row in ((64, 8192), (2, 8192), (8, 32768), (7, 37888), (4, 65536), (3, 65536))] == \
+        [4, 8, 32, 37, 64, 64]
+    for b in (1, 2, 3, 8, 64):
+        for hq in (1, 8, 16, 17, 32, 48, 64, 96, 128):
+            legal = [hkv for hkv in range(1, hq + 1) if hq % hkv == 0 and hq // hkv <= 16]
+            for n in (100, 1100, 4096, 8192, 32768, 37888, 65536, 1 << 20):
+                allowed = query(b, hq, n)
+                assert all(ac.pick(b * hkv, n) <= allowed for hkv in legal), (b, hq, n, allowed)
 
 
 # ---- what the entry points refuse --------------------------------------------------------------------------------------

@@ -2,8 +2,11 @@
 
 Problems, the fp64 reference and the error bound are those of ``tests/attn_decode_cases.py``, which
 ``tests/test_attn_decode_cases.py`` checks on the CPU.  The selection cases are compared on the raw 16 bits of every
-element: they test addressing (block tables, pages, splits, waves, masking) and need no tolerance.  The random cases are
-compared with the derived bound.  No case holds a page index out of range: a wrong kernel fails a comparison.
+element: they test addressing (block tables, pages, splits, waves, masking) and need no tolerance.  The window cases,
+compared in the same way, test that every token is counted exactly once.  The random cases are compared with the
+derived bound.  One case holds a page index above ``num_pages - 1`` (``attn_decode_cases.page_clamp_problem``), and
+its caches reach three pages further than ``num_pages`` says; no other index is out of range and none is negative, so
+a wrong kernel fails a comparison and reads nothing outside an allocation.
 """
 import json
 import os
@@ -50,7 +53,8 @@ def stream(hip):
 @pytest.fixture(scope="module")
 def ws():
     """The workspace of every test.  ``Dev.run`` sets the part a launch may use to fp32 NaN first (a few KiB for
-    these cases): a partial the kernel fails to write is then merged as NaN, never as an earlier problem's."""
+    most cases, a few MiB at 64 splits): a partial the kernel fails to write is then merged as NaN, never as an earlier
+    problem's."""
     return torch.full((WS_BYTES // 4,), NAN, device="cuda", dtype=torch.float32)
 
 
@@ -71,6 +75,9 @@ class Dev:
         else:
             used = p.b * p.hq * splits * ac.PARTIAL_BYTES if splits > 1 else 0
         assert used <= ws.numel() * 4
+        # ``s`` does not wait for torch's stream, nor torch's for it: an earlier launch, on any stream, has to have
+        # merged its partials before they are overwritten, and the fill has to be done before this launch
+        torch.cuda.synchronize()
         ws[:used // 4].fill_(NAN)
         torch.cuda.synchronize()
         args = (s, p.kind, q.data_ptr(), k.data_ptr(), v.data_ptr(), bt.data_ptr(), sl.data_ptr(), o.data_ptr(), p.b,
@@ -130,8 +137,9 @@ def test_attn_selects_at_every_wave_and_split_boundary(hip, stream, ws, kind, cf
 @kind_cfg
 def test_attn_follows_block_tables(hip, stream, ws, kind, cfg):
     """Reversed and scattered page orders, a table shared by two sequences, a ``table_stride`` larger than needed, a
-    batch that mixes 0 and short lengths with ``max_seq_len``, and ``seq_lens`` entries above ``max_seq_len`` that the
-    kernel clamps (the slots past it are poison)."""
+    batch that mixes 0 and short lengths with ``max_seq_len``, ``seq_lens`` entries above ``max_seq_len`` that the
+    kernel clamps (the slots past it are poison), and entries of -1 and -2^31, clamped to 0: rows of zeros next to a
+    live sequence."""
     _check(hip, stream, ws, ac.table_cases(kind), cfg, f"{kind} cfg {cfg}")
 
 
@@ -236,6 +244,146 @@ def test_attn_is_deterministic_placement_free_and_within_the_bound(hip, stream, 
                 assert bool((err <= bound).all()), f"{what}: error up to {worst:.3f} of the bound"
     finally:
         masked.destroy()
+
+
+# ---- 6a. windows: every token counted once ----------------------------------------------------------------------------
+
+KIND_ROW = [(kind, cfg) for kind in ac.KINDS for cfg in ac.CFGS]
+kind_row = pytest.mark.parametrize("kind,cfg", KIND_ROW, ids=[f"{k}-{c}" for k, c in KIND_ROW])
+
+
+@kind_cfg
+def test_attn_counts_every_token_once_at_every_wave_and_split_boundary(hip, stream, ws, kind, cfg):
+    """The lengths of test 2 as window cases (``attn_decode_cases.window_problem``): every head weighs a window of
+    s tokens equally and the windows cover the sequence, so a tile, a half or a token that the ring, the drain or a
+    split's range takes twice or leaves out changes l and a column of some head's row.  A selection case cannot see
+    that: its weights are 0 or 1 (``tests/test_attn_decode_cases.py`` shows both)."""
+    for splits in _splits_of(cfg):
+        runs = [(name, p, Dev(p).run(hip, stream, ws, cfg, splits))
+                for name, p in ac.window_split_cases(kind, cfg, splits or 1)]
+        stream.sync()
+        for name, p, o in runs:
+            ac.assert_bits_equal(o, p.want, f"{kind} cfg {cfg}, splits {splits}, {name}")
+
+
+@kind_cfg
+def test_attn_windows_with_every_score_far_below_zero(hip, stream, ws, kind, cfg):
+    """-261 inside a window and -522 outside it: a running maximum that starts at a finite value stays there, and
+    every probability underflows."""
+    _check(hip, stream, ws, ac.negative_cases(kind), cfg, f"{kind} cfg {cfg}")
+
+
+@kind_cfg
+def test_attn_other_head_counts_page_sizes_and_groups(hip, stream, ws, kind, cfg):
+    """Hkv of 1, 3 and 8, pages of 32, 48, 128 and 256 tokens, G of 3, 7 and 12, at lengths around a tile and a page
+    boundary: window cases, and selection cases for the addressing."""
+    _check(hip, stream, ws, ac.other_shape_cases(kind), cfg, f"{kind} cfg {cfg}")
+
+
+@kind_row
+def test_attn_counts_every_token_once_at_16_to_64_splits(hip, stream, ws, kind, cfg):
+    """``MORE_SPLITS`` (16, 32, 37 and 64) through ``_launch_cfg``: 1, W + 1 and 2 F W + 1 tiles per split, and a
+    split without a token, with one token and with one full tile.  Every cut lies inside some head's window, so every
+    split's partial enters some head's row with weight exactly 1."""
+    for splits in ac.MORE_SPLITS:
+        for name, p in ac.more_split_cases(kind, cfg, splits):
+            o = Dev(p).run(hip, stream, ws, cfg, splits)
+            stream.sync()
+            ac.assert_bits_equal(o, p.want, f"{kind} cfg {cfg}, splits {splits}, {name}")
+
+
+@pytest.fixture(scope="module")
+def random_more():
+    """``{kind: (problem, fp64 reference, bound)}`` of ``RANDOM_MORE``, computed once."""
+    out = {}
+    for kind in ac.KINDS:
+        p = ac.random_problem(kind, *ac.RANDOM_MORE)
+        out[kind] = (p, ac.reference(p), ac.error_bound(p)[0])
+    return out
+
+
+@kind_row
+def test_attn_merges_16_32_and_64_splits_within_the_bound(hip, stream, ws, random_more, kind, cfg):
+    """Random normal operands, 4096 and 45 tokens: the splits' partials are merged with graded weights (a window
+    case's are 0 or 1), inside the derived bound of the fp64 reference."""
+    p, ref, bound = random_more[kind]
+    d = Dev(p)
+    for splits in ac.RANDOM_MORE_SPLITS:
+        o = d.run(hip, stream, ws, cfg, splits)
+        stream.sync()
+        what = f"{kind} cfg {cfg} splits {splits} case {ac.RANDOM_MORE[0]}"
+        err = np.abs(o.cpu().double().numpy() - ref)
+        assert not np.isnan(err).any(), f"{what}: NaN in the result"
+        worst = float((err / np.maximum(bound, 1e-300)).max())
+        print(f"{what}: largest error / bound = {worst:.4f}")
+        assert bool((err <= bound).all()), f"{what}: error up to {worst:.3f} of the bound"
+
+
+# ---- 6b. the dispatcher -----------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def dispatch_problems():
+    """``get(i)``: the cases of row i of ``DISPATCH_SHAPES`` for both cache types; one row is kept at a time."""
+    kept = {}
+
+    def get(i):
+        if i not in kept:
+            kept.clear()
+            kept[i] = ac.dispatch_cases(ac.DISPATCH_SHAPES[i])
+        return kept[i]
+
+    return get
+
+
+SHAPE_KIND = [(i, kind) for i in range(len(ac.DISPATCH_SHAPES)) for kind in ac.KINDS]
+
+
+@pytest.mark.parametrize("shape,kind", SHAPE_KIND,
+                         ids=[f"{ac.DISPATCH_SHAPES[i][-1]}-splits-{i}-{k}" for i, k in SHAPE_KIND])
+def test_attn_dispatches_the_split_count_of_pick(hip, stream, ws, dispatch_problems, shape, kind):
+    """``gsx_decode_attn`` at the smallest shapes where each rule of ``attn_pick`` decides (4, 8, 32, 37 and 64 splits;
+    ``DISPATCH_SHAPES``): a window case and a selection case with targets at the cuts, exact.  The split count is read
+    from the NaN-prefilled workspace: B * Hq * splits partials of 130 floats are written (a split without a token
+    writes zeros and (-inf, 0)), and nothing behind them."""
+    splits = ac.DISPATCH_SHAPES[shape][-1]
+    for what, p in dispatch_problems(shape)[kind]:
+        assert ac.pick(p.b * p.hkv, p.max_seq_len) == splits
+        allowed = hip.decode_attn_workspace_bytes(p.b, p.hq, ac.D, p.page, p.max_seq_len) // 4
+        written = p.b * p.hq * splits * (ac.D + 2)
+        assert written <= allowed and allowed + written <= ws.numel()
+        ws[allowed:allowed + written].fill_(NAN)  # Dev.run fills what the query allows; and behind it, for this test
+        o = Dev(p).run(hip, stream, ws, None)
+        stream.sync()
+        ac.assert_bits_equal(o, p.want, f"{kind}, {what}")
+        nan = torch.isnan(ws[:allowed + written])
+        assert not bool(nan[:written].any()), f"{kind}, {what}: fewer than {splits} splits were dispatched"
+        assert bool(nan[written:].all()), f"{kind}, {what}: more than {splits} splits were dispatched"
+
+
+# ---- 6c. the contract's clamps, and the e4m3 codes --------------------------------------------------------------------
+
+@kind_cfg
+def test_attn_clamps_a_page_index_above_num_pages(hip, stream, ws, kind, cfg):
+    """A block-table entry of a page in use is ``num_pages + 1``; its data lies in page ``num_pages - 1``, where the
+    unsigned minimum of the contract sends it, and the caches go on for three pages of poison.  (``seq_lens`` below
+    zero are among the table cases of test 3.)  Negative page indices are not tested: without the clamp they would
+    leave the allocation."""
+    p = ac.page_clamp_problem(kind)
+    assert int(p.block_table.max()) == p.num_pages + 1 and p.k_cache.shape[0] == p.num_pages + 3
+    _check(hip, stream, ws, [("a page index of num_pages + 1", p)], cfg, f"{kind} cfg {cfg}")
+
+
+@pytest.mark.parametrize("cfg", ac.ALL, ids=lambda c: "dispatch" if c is None else str(c))
+def test_attn_converts_every_e4m3_code_of_v(hip, stream, ws, cfg):
+    """The 32 target rows hold each of the 254 e4m3 codes that are no NaN at each byte position of a 16-B chunk:
+    O is the value times ``v_scale``, exact, subnormals and 448 included; -0 comes out as a zero.  K goes through the
+    same conversion function, and the random cases test where its operands land."""
+    p, _ = ac.fp8_codes_problem()
+    d = Dev(p)
+    for splits in _splits_of(cfg):
+        o = d.run(hip, stream, ws, cfg, splits)
+        stream.sync()
+        ac.assert_bits_equal(o, p.want, f"cfg {cfg} splits {splits}", zeros_by_value=True)
 
 
 # ---- 7. the timing entry point ----------------------------------------------------------------------------------------
