@@ -114,6 +114,9 @@ def lib():
         # stream, kind, Q, K_cache, V_cache, block_table, seq_lens, O; B, Hq, Hkv, D, page, num_pages, table_stride,
         # max_seq_len; scale, k_scale, v_scale; workspace, workspace_bytes
         _attn_sig = [vp, i32] + [vp] * 6 + [i32] * 8 + [ctypes.c_float] * 3 + [vp, u64]
+        # stream, kind, QKV, qkv_stride, Q_out, K_cache, V_cache, block_table, seq_lens, lens_out, rope_cos, rope_sin;
+        # rope_len, B, T, Hq, Hkv, D, page, num_pages, table_stride, max_seq_len; k_inv_scale, v_inv_scale
+        _kv_append_sig = [vp, i32, vp, ctypes.c_int64] + [vp] * 8 + [i32] * 10 + [ctypes.c_float] * 2
         sig = {
             "gsx_last_error": ([], ctypes.c_char_p),
             "gsx_device_count": ([ctypes.POINTER(i32)], i32),
@@ -163,6 +166,8 @@ def lib():
             "gsx_decode_attn_cfg_name": ([i32], ctypes.c_char_p),
             "gsx_decode_attn_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 2, i32),
             "gsx_event_time_decode_attn": ([*_attn_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_kv_append": (_kv_append_sig, i32),
+            "gsx_event_time_kv_append": ([*_kv_append_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
             "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
                                   i32),
@@ -667,4 +672,46 @@ def time_decode_attn(stream: Stream, kind: str, q: int, k_cache: int, v_cache: i
                                                      hq, hkv, d, page, num_pages, table_stride, max_seq_len, scale,
                                                      k_scale, v_scale, workspace, workspace_bytes), iters,
                                          ctypes.byref(ms)), "time_decode_attn")
+    return ms.value
+
+
+def _kv_append_args(stream: Stream, kind: str, qkv: int, qkv_stride: int, q_out: int, k_cache: int, v_cache: int,
+                    block_table: int, seq_lens: int, lens_out: int, rope_cos: int, rope_sin: int, rope_len: int, b: int,
+                    t: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int, max_seq_len: int,
+                    k_inv_scale: float, v_inv_scale: float) -> tuple:
+    if kind not in ATTN_KV_KINDS:
+        raise ValueError(f"KV cache kind {kind!r}: one of {', '.join(ATTN_KV_KINDS)}")
+    return (stream.handle, ATTN_KV_KINDS[kind], ctypes.c_void_p(qkv), qkv_stride,
+            *(ctypes.c_void_p(x) for x in (q_out, k_cache, v_cache, block_table, seq_lens, lens_out, rope_cos,
+                                           rope_sin)),
+            rope_len, b, t, hq, hkv, d, page, num_pages, table_stride, max_seq_len, k_inv_scale, v_inv_scale)
+
+
+def kv_append(stream: Stream, kind: str, qkv: int, qkv_stride: int, q_out: int, k_cache: int, v_cache: int,
+              block_table: int, seq_lens: int, lens_out: int, rope_cos: int, rope_sin: int, rope_len: int, b: int,
+              t: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int, max_seq_len: int,
+              k_inv_scale: float = 1.0, v_inv_scale: float = 1.0):
+    """RoPE and KV-cache append for ``b`` sequences of ``t`` new tokens each: row ``n`` of ``qkv[b * t][qkv_stride]``
+    (bf16: ``hq`` query, ``hkv`` key, ``hkv`` value heads of ``d`` = 128) is token ``n % t`` of sequence ``n // t`` at
+    position ``seq_lens[n // t] + n % t``.  Q and K are rotated by ``rope_cos`` / ``rope_sin`` (fp32
+    ``[rope_len][d / 2]``); Q goes to ``q_out[b * t][hq][d]`` and K and V into the token's slot of the paged caches
+    ``[num_pages][hkv][page][d]`` of ``kind`` ``"bf16"`` or ``"fp8"`` (OCP e4m3, saturating, after a multiplication by
+    ``k_inv_scale`` / ``v_inv_scale``).  ``lens_out`` (0: none) receives the new lengths.  All addresses are device
+    addresses.  Not synchronised."""
+    _ck(lib().gsx_kv_append(*_kv_append_args(stream, kind, qkv, qkv_stride, q_out, k_cache, v_cache, block_table,
+                                             seq_lens, lens_out, rope_cos, rope_sin, rope_len, b, t, hq, hkv, d, page,
+                                             num_pages, table_stride, max_seq_len, k_inv_scale, v_inv_scale)),
+        "kv_append")
+
+
+def time_kv_append(stream: Stream, kind: str, qkv: int, qkv_stride: int, q_out: int, k_cache: int, v_cache: int,
+                   block_table: int, seq_lens: int, lens_out: int, rope_cos: int, rope_sin: int, rope_len: int, b: int,
+                   t: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int, max_seq_len: int,
+                   iters: int, k_inv_scale: float = 1.0, v_inv_scale: float = 1.0) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_kv_append(*_kv_append_args(stream, kind, qkv, qkv_stride, q_out, k_cache, v_cache,
+                                                        block_table, seq_lens, lens_out, rope_cos, rope_sin, rope_len,
+                                                        b, t, hq, hkv, d, page, num_pages, table_stride, max_seq_len,
+                                                        k_inv_scale, v_inv_scale), iters, ctypes.byref(ms)),
+        "time_kv_append")
     return ms.value

@@ -25,7 +25,9 @@ exact environment the device plugin's Allocate produces, in four scenarios:
                     caches: a gather over pages, bound by HBM bandwidth too) next to 3 pods
                     running large GEMMs.
 
-``--workload decode`` or ``--workload attn`` makes every pod of the other scenarios such a pod.
+``--workload decode`` or ``--workload attn`` makes every pod of the other scenarios such a pod.  ``--workload server``
+(a whole decode layer per ring layer: projections, RoPE and KV append, attention) does so for ``solo``, ``solo64``,
+``shared`` and ``partitioned``; it runs on the library's kernels only.
 Reported per scenario: per-pod TFLOP/s, aggregate, and fairness (min/max); for
 decode and attention pods also the TB/s of weight or KV bytes they streamed.
 Run: ``python -m gsxtools.isolation --seconds 8``.
@@ -86,7 +88,7 @@ def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str
                "--size", str(sz), "--seconds", str(seconds), "--dtype", dtype, "--json"]
         if wl != "gemm":  # the default is left off the command line
             cmd += ["--workload", wl, "--batch", str(batch)]
-        if wl == "attn":
+        if wl in ("attn", "server"):
             cmd += attn_args or []
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                                       cwd=str(ROOT)))
@@ -123,6 +125,14 @@ def attn_cmdline(a: argparse.Namespace) -> list[str]:
     return out + (["--kv-gib", str(a.kv_gib)] if a.kv_gib is not None else [])
 
 
+SCENARIOS_SERVER = ("solo", "solo64", "shared", "partitioned")
+
+
+def server_cmdline(a: argparse.Namespace) -> list[str]:
+    """The server pods' options: the attention's shape, and the size of the weight ring."""
+    return attn_cmdline(a) + (["--weights-gib", str(a.weights_gib)] if a.weights_gib is not None else [])
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = pod_workload.BatchRangeParser()
     ap.add_argument("--pods", type=int, default=4)
@@ -134,13 +144,16 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"],
                     help="the pods' GEMM operand type (mxfp4: with --kernel gsx only)")
     ap.add_argument("--size", type=int, default=8192)
-    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn"],
+    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server"],
                     help="what the pods run: the large GEMM, the decode workload (--batch rows against a ring of "
-                         "--size x --size weights), or the attention workload (--batch sequences of --context tokens)")
+                         "--size x --size weights), the attention workload (--batch sequences of --context tokens), "
+                         "or the server workload (a decode layer per ring layer; solo, solo64, shared, partitioned)")
     ap.add_argument("--batch", type=int, default=8, metavar="N",
                     help="the decode pods' activation rows (1..16), or the attention pods' sequences (1..256, with "
                          "--workload attn)")
     pod_workload.add_attn_arguments(ap)
+    ap.add_argument("--weights-gib", type=float, default=None,
+                    help="--workload server: size of the pods' weight ring (default: the workload's)")
     ap.add_argument("--small-size", type=int, default=2048)
     ap.add_argument("--scenarios",
                     default="solo,shared,partitioned,env,env-gsx,solo-small,solo64,noisy,noisy-partitioned")
@@ -151,14 +164,16 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     results = []
-    own_size = a.workload in ("decode", "attn")  # pods whose work --size / --small-size does not scale
+    own_size = a.workload in ("decode", "attn", "server")  # pods whose work --size / --small-size does not scale
 
-    def run(*args):  # every scenario's pods get the attention options: only attention pods use them
-        return run_pods(*args, attn_args=attn_cmdline(a))
+    def run(*args):  # every scenario's pods get the attention options: only attention and server pods use them
+        return run_pods(*args, attn_args=server_cmdline(a) if a.workload == "server" else attn_cmdline(a))
 
     for sc in a.scenarios.split(","):
         if sc not in SCENARIOS:
             raise SystemExit(f"unknown scenario {sc}")
+        if a.workload == "server" and sc not in SCENARIOS_SERVER:
+            raise SystemExit(f"--workload server: scenario {sc} is not one of {', '.join(SCENARIOS_SERVER)}")
         if sc == "solo":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, False)
             res = run(envs, a.seconds, a.kernel, a.size, "none", a.dtype, a.workload, a.batch)

@@ -28,6 +28,8 @@ kv_pages = _mod.kv_pages
 default_kv_bytes = _mod.default_kv_bytes
 kv_ring_layers = _mod.kv_ring_layers
 add_attn_arguments = _mod.add_attn_arguments
+server_layer_weight_bytes = _mod.server_layer_weight_bytes
+server_window = _mod.server_window
 BatchRangeParser = _mod._Parser
 
 if __name__ == "__main__":

@@ -24,6 +24,12 @@
 //  * MXFP4 MFMA GEMM     — the same workload on e2m1 operands with e8m0 block scales
 //                          on the block-scaled MFMA, and the quantiser that makes
 //                          such operands from bf16 (gemm_mxfp4.hip);
+//  * decode GEMM / attention — an inference server's decode step: M <= 16 rows against
+//                          weights streamed from HBM (gemm_decode.hip), attention
+//                          over a paged KV cache in bf16 or e4m3 (attn_decode.hip);
+//  * RoPE + KV append    — rotates Q and K and writes the new tokens' K and V into
+//                          their page slots, quantised for an e4m3 cache: what makes
+//                          the cache the attention reads (kv_append.hip);
 //  * CU-masked streams   — hipExtStreamCreateWithCUMask.
 //
 // All functions return 0 or a hipError_t value; gsx_last_error() has text.
@@ -262,6 +268,48 @@ int gsx_event_time_decode_attn(void* stream, int kind, const void* Q, const void
                                const void* block_table, const void* seq_lens, void* O, int B, int Hq, int Hkv, int D,
                                int page, int num_pages, int table_stride, int max_seq_len, float scale, float k_scale,
                                float v_scale, void* workspace, uint64_t workspace_bytes, int iters, float* ms);
+
+// RoPE and KV-cache append (kv_append.hip): the producer of the caches gsx_decode_attn reads, same kinds and layout.
+//   QKV[B * T][qkv_stride]                bf16, elements: row n is token n's Hq query heads, then Hkv key heads, then
+//                                         Hkv value heads, D == 128 each (the fused projection's output)
+//   Q_out[B * T][Hq][D]                   bf16, contiguous; with T == 1 the Q[B][Hq][D] of gsx_decode_attn
+//   K_cache, V_cache [num_pages][Hkv][page][D]   bf16 (GSX_ATTN_KV_BF16) or OCP e4m3 (GSX_ATTN_KV_FP8)
+//   block_table[B][table_stride], seq_lens[B]    int32, device memory, as gsx_decode_attn takes them
+//   lens_out[B]                           int32, device memory, or NULL
+//   rope_cos, rope_sin [rope_len][D / 2]  fp32, device memory
+// Token n belongs to sequence b = n / T and is its new token t = n % T (T == 1: a decode step; larger: a prefill
+// chunk).  base = clamp(seq_lens[b], 0, max_seq_len), the clamp the attention applies, and pos = base + t.  A token
+// is LIVE when pos < max_seq_len and block_table[b][pos / page] lies in [0, num_pages).  A live token writes slot
+// pos % page of that page for every KV head in both caches (64-bit offsets: a cache may exceed 4 GiB) and its
+// rotated queries to Q_out.  Any other token writes nothing to the caches and zeros to its Q_out row: a bad page index
+// is dropped, not clamped (a clamped write would land in another sequence's page), so no input makes the kernel write
+// outside the caches, Q_out or lens_out.  lens_out[b] = min(base + T, max_seq_len), written by exactly one workgroup
+// per sequence; it must not overlap seq_lens, which other workgroups are still reading.  Two sequences that share a
+// page and write the same slot race: that is the caller's business.
+// Numerics, bit for bit.  Half-split ("NeoX") pairing: (x1, x2) = (x[i], x[i + 64]), c = rope_cos[pos][i],
+// s = rope_sin[pos][i], i < 64:
+//   x1' = fl(fl(x1 * c) - fl(x2 * s))     x2' = fl(fl(x2 * c) + fl(x1 * s))
+// every fp32 operation rounded on its own, nothing contracted into an FMA; the tables are whatever fp32 the caller
+// supplies.  Q_out = bf16(x'), round to nearest even.  bf16 cache: K = bf16(x'), V a raw 16-bit copy, and k_inv_scale
+// and v_inv_scale exactly 1.0f.  e4m3 cache: K = e4m3(fl(x' * k_inv_scale)), V = e4m3(fl(v * v_inv_scale)), round to
+// nearest even onto OCP e4m3fn, saturating: every finite value beyond +-448, and +-inf, give +-448 (0x7e / 0xfe); a NaN
+// gives a NaN code (0x7f or 0xff).  The inverse scales are finite and > 0; gsx_decode_attn's k_scale and v_scale are
+// their reciprocals.  Intermediate magnitudes below 2^-100 that are not exact zeros are outside the contract.
+// Requirements: a known kind; D == 128; Hq % Hkv == 0 and Hq / Hkv <= 16; page % 16 == 0 and 16 <= page <= 256;
+// B, T >= 1 and B * T below 2^31; 1 <= max_seq_len <= table_stride * page; rope_len >= max_seq_len; qkv_stride >=
+// (Hq + 2 Hkv) * D and qkv_stride % 8 == 0; every pointer but lens_out non-NULL; QKV, Q_out, the caches and the tables
+// 16-B aligned, the int32 arrays 4-B aligned; Q_out does not overlap QKV.  Everything is validated before the first
+// device call; launches on `stream` and returns without synchronising.
+int gsx_kv_append(void* stream, int kind, const void* QKV, int64_t qkv_stride, void* Q_out, void* K_cache,
+                  void* V_cache, const void* block_table, const void* seq_lens, void* lens_out, const float* rope_cos,
+                  const float* rope_sin, int rope_len, int B, int T, int Hq, int Hkv, int D, int page, int num_pages,
+                  int table_stride, int max_seq_len, float k_inv_scale, float v_inv_scale);
+// elapsed milliseconds of `iters` back-to-back gsx_kv_append on `stream`, by hip events (for benches)
+int gsx_event_time_kv_append(void* stream, int kind, const void* QKV, int64_t qkv_stride, void* Q_out, void* K_cache,
+                             void* V_cache, const void* block_table, const void* seq_lens, void* lens_out,
+                             const float* rope_cos, const float* rope_sin, int rope_len, int B, int T, int Hq, int Hkv,
+                             int D, int page, int num_pages, int table_stride, int max_seq_len, float k_inv_scale,
+                             float v_inv_scale, int iters, float* ms);
 
 // HBM pre-flight memory test (memtest.hip).  The expected content of 16-byte word W = origin/16 + word index is
 // generated from (pattern, seed, invert, W) and never stored; `origin` is the byte offset of `base` in the whole

@@ -29,7 +29,15 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   of per-layer caches (``--kv-gib``; 4 GiB or a quarter of the share, never fewer than two layers) and runs one
   attention per layer and step, so a step streams more than the Infinity Cache.  It reports ``tbps`` (KV bytes read
   per second) and ``tokens_per_s``.  The library's decode attention, or (``--kernel torch``, bf16 only)
-  ``scaled_dot_product_attention(enable_gqa=True)`` on a contiguous copy of the same data.
+  ``scaled_dot_product_attention(enable_gqa=True)`` on a contiguous copy of the same data;
+* ``--workload server`` is a whole decode layer per ring layer and step, on the library's kernels only: the fused QKV
+  projection of ``--batch`` rows (1..16; hidden = ``--heads`` x 128, bf16 weights) through the decode GEMM, RoPE and
+  the append of the new token's K and V to the layer's paged cache (``gsx_kv_append``; ``--kv-dtype`` selects the
+  cache), the decode attention over the cache that has just grown, and the output projection, which gives the next
+  layer's activations.  Nothing in a step waits for the host.  The sequence lengths live on the device and grow from
+  ``--context`` minus a window to ``--context``, then start again, so the run can go on forever.  The weight ring is
+  sized by ``--weights-gib`` and the KV ring by ``--kv-gib``; it reports ``tokens_per_s`` and ``tbps`` (weight plus KV
+  bytes read per second).
 """
 from __future__ import annotations
 
@@ -102,6 +110,22 @@ def kv_ring_layers(kv_bytes: int, one_layer_bytes: int) -> int:
     return ring_layers(kv_bytes, one_layer_bytes)
 
 
+SERVER_WINDOW = 64
+
+
+def server_layer_weight_bytes(heads: int, kv_heads: int) -> int:
+    """Bytes of one decode layer's bf16 weights: the QKV projection ``[(heads + 2 kv_heads) * 128][hidden]`` and the
+    output projection ``[hidden][hidden]``, hidden = ``heads * 128``."""
+    hidden = heads * ATTN_D
+    return ((heads + 2 * kv_heads) * ATTN_D * hidden + hidden * hidden) * 2
+
+
+def server_window(context: int) -> int:
+    """Steps after which the server workload's sequences start again: they grow from ``context - window`` to
+    ``context`` tokens, inside the pages the block table has for ``context``."""
+    return min(SERVER_WINDOW, context)
+
+
 def ring_layers(weights_bytes: int, one_matrix_bytes: int) -> int:
     """Matrices in the weight ring: enough to cover ``weights_bytes``, and never fewer than two, so that no launch
     finds its matrix where the last launch left it."""
@@ -133,6 +157,10 @@ class Kernels:
                                           + [vp, ctypes.c_uint64])
             L.gsx_decode_attn_workspace_bytes.argtypes = [i32] * 5 + [ctypes.POINTER(ctypes.c_uint64)]
             L.gsx_decode_attn.restype = L.gsx_decode_attn_workspace_bytes.restype = i32
+        if hasattr(L, "gsx_kv_append"):  # likewise: an image built before the append kernel
+            L.gsx_kv_append.argtypes = ([vp, i32, vp, ctypes.c_int64] + [vp] * 8 + [i32] * 10
+                                        + [ctypes.c_float] * 2)
+            L.gsx_kv_append.restype = i32
         L.gsx_last_error.argtypes, L.gsx_last_error.restype = [], ctypes.c_char_p
         self.L, self.path = L, path
 
@@ -197,6 +225,17 @@ class Kernels:
                                                                       (q, kc, vc, table, lens, o)),
                                         b, hq, hkv, ATTN_D, page, num_pages, table_stride, max_seq_len, scale, 1.0, 1.0,
                                         ctypes.c_void_p(ws), ws_bytes), "decode_attn")
+
+    def kv_append(self, s, kv_dtype: str, qkv: int, qkv_stride: int, q_out: int, kc: int, vc: int, table: int,
+                  lens: int, lens_out: int, cos: int, sin: int, rope_len: int, b: int, t: int, hq: int, hkv: int,
+                  page: int, num_pages: int, table_stride: int, max_seq_len: int):
+        """RoPE on Q and K and the new tokens' K and V into their page slots (unit cache scales)."""
+        if not hasattr(self.L, "gsx_kv_append"):
+            raise RuntimeError(f"{self.path} has no gsx_kv_append: rebuild it")
+        self._ck(self.L.gsx_kv_append(s, ATTN_KV_KINDS[kv_dtype], ctypes.c_void_p(qkv), qkv_stride,
+                                      *(ctypes.c_void_p(x) for x in (q_out, kc, vc, table, lens, lens_out, cos, sin)),
+                                      rope_len, b, t, hq, hkv, ATTN_D, page, num_pages, table_stride, max_seq_len,
+                                      1.0, 1.0), "kv_append")
 
     def sync(self, s):
         self._ck(self.L.gsx_stream_sync(s), "stream_sync")
@@ -331,6 +370,77 @@ def attn_steps(torch, kl, gs, stream, dev, kv_dtype: str, batch: int, context: i
     return step, sync
 
 
+def server_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, heads: int, kv_heads: int, page: int,
+                 w_layers: int, kv_layers: int):
+    """``(step, sync, finite)`` of the server workload: a ring of ``w_layers`` decode layers' bf16 weights (random
+    normal over sqrt(hidden), so activations keep their size), a ring of ``kv_layers`` paged KV caches behind one block
+    table, and a step that runs ``max(w_layers, kv_layers)`` decode layers back to back on the library's stream: QKV
+    projection, RoPE and append, attention, output projection.  Layer 0 always reads the same activations.  The
+    lengths ping-pong between two device buffers through ``lens_out``; every :func:`server_window` steps the constant
+    start buffer is the input again.  ``finite()`` says whether the last activations are finite."""
+    hidden, nqkv = heads * ATTN_D, (heads + 2 * kv_heads) * ATTN_D
+    per_seq, pages = kv_pages(batch, context, page)
+    window = server_window(context)
+    layers = max(w_layers, kv_layers)
+    wqkv = torch.empty(w_layers, nqkv, hidden, device=dev, dtype=torch.bfloat16)
+    wo = torch.empty(w_layers, hidden, hidden, device=dev, dtype=torch.bfloat16)
+    for i in range(w_layers):  # one matrix at a time: nothing larger is ever held in fp32
+        wqkv[i].copy_(torch.randn(nqkv, hidden, device=dev) / math.sqrt(hidden))
+        wo[i].copy_(torch.randn(hidden, hidden, device=dev) / math.sqrt(hidden))
+    kdt = torch.bfloat16 if kv_dtype == "bf16" else torch.float8_e4m3fn
+    kc = torch.empty(kv_layers, pages, kv_heads, page, ATTN_D, device=dev, dtype=kdt)
+    vc = torch.empty_like(kc)
+    for i in range(kv_layers):
+        for c in (kc, vc):
+            c[i].copy_(torch.randn(pages, kv_heads, page, ATTN_D, device=dev, dtype=torch.bfloat16).to(kdt))
+    table = torch.randperm(pages, device=dev).to(torch.int32).view(batch, per_seq).contiguous()
+    start = torch.full((batch,), context - window, device=dev, dtype=torch.int32)
+    lens = [torch.zeros(batch, device=dev, dtype=torch.int32) for _ in range(2)]
+    ang = (torch.arange(context, device=dev, dtype=torch.float64)[:, None]
+           * 10000.0 ** (-torch.arange(ATTN_D // 2, device=dev, dtype=torch.float64) / (ATTN_D // 2))[None])
+    cos, sin = ang.cos().float().contiguous(), ang.sin().float().contiguous()
+    x = [torch.randn(batch, hidden, device=dev, dtype=torch.bfloat16) for _ in range(3)]  # x[0]: layer 0's, constant
+    qkv = torch.empty(batch, nqkv, device=dev, dtype=torch.bfloat16)
+    q = torch.empty(batch, heads, ATTN_D, device=dev, dtype=torch.bfloat16)
+    o = torch.empty_like(q)
+    ws_bytes = kl.attn_workspace_bytes(batch, heads, page, context)
+    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+    wqkv_bytes, wo_bytes = wqkv[0].numel() * 2, wo[0].numel() * 2
+    cache_bytes = kc[0].numel() * kc.element_size()
+    scale = 1.0 / math.sqrt(ATTN_D)
+    torch.cuda.synchronize()
+    count = [0]
+
+    def step():
+        k = count[0] % window
+        count[0] += 1
+        lens_in = start if k == 0 else lens[(k - 1) % 2]
+        lens_out = lens[k % 2]
+        for i in range(layers):
+            xin = x[0] if i == 0 else x[1 + i % 2]
+            xout = x[1 + (i + 1) % 2]
+            kci, vci = kc.data_ptr() + (i % kv_layers) * cache_bytes, vc.data_ptr() + (i % kv_layers) * cache_bytes
+            kl.decode_gemm(gs, "bf16", xin.data_ptr(), wqkv.data_ptr() + (i % w_layers) * wqkv_bytes, qkv.data_ptr(),
+                           batch, nqkv, hidden)
+            kl.kv_append(gs, kv_dtype, qkv.data_ptr(), nqkv, q.data_ptr(), kci, vci, table.data_ptr(),
+                         lens_in.data_ptr(), lens_out.data_ptr(), cos.data_ptr(), sin.data_ptr(), context, batch, 1,
+                         heads, kv_heads, page, pages, per_seq, context)
+            kl.decode_attn(gs, kv_dtype, q.data_ptr(), kci, vci, table.data_ptr(), lens_out.data_ptr(), o.data_ptr(),
+                           batch, heads, kv_heads, page, pages, per_seq, context, scale, ws.data_ptr(), ws_bytes)
+            kl.decode_gemm(gs, "bf16", o.data_ptr(), wo.data_ptr() + (i % w_layers) * wo_bytes, xout.data_ptr(), batch,
+                           hidden, hidden)
+
+    def sync():
+        kl.sync(gs)
+
+    def finite():
+        kl.sync(gs)
+        return all(bool(torch.isfinite(t.float()).all()) for t in (*x, qkv, q, o))
+
+    step.keep = (wqkv, wo, kc, vc, table, start, lens, cos, sin, x, qkv, q, o, ws)  # the closures hold addresses
+    return step, sync, finite
+
+
 def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 8192, seconds: float = 0.0,
         iters: int = 0, report_every: float = 5.0, touch: bool = False, quiet: bool = False,
         probe_limit: bool = False, dtype: str = "bf16", workload: str = "gemm", batch: int = 8,
@@ -367,10 +477,18 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     m = n = k = size
     if dtype not in ("bf16", "fp8", "mxfp4"):
         raise SystemExit(f"--dtype {dtype}: bf16, fp8 or mxfp4")
-    if workload not in ("gemm", "decode", "attn"):
-        raise SystemExit(f"--workload {workload}: gemm, decode or attn")
+    if workload not in ("gemm", "decode", "attn", "server"):
+        raise SystemExit(f"--workload {workload}: gemm, decode, attn or server")
     decode = workload == "decode"
-    attn = workload == "attn"
+    server = workload == "server"
+    attn = workload == "attn" or server  # the server workload has the attention's shape options
+    if server:
+        if kernel != "gsx":
+            raise SystemExit("--workload server runs on the library's kernels only (--kernel gsx)")
+        if dtype != "bf16":
+            raise SystemExit("--workload server: the weights are bf16 only (the KV cache: --kv-dtype)")
+        if not 1 <= batch <= 16:
+            raise SystemExit(f"--batch {batch}: 1..16")
     if attn:
         if not 1 <= batch <= 256:
             raise SystemExit(f"--batch {batch}: 1..256 sequences")
@@ -404,7 +522,19 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         gs = hip_stream if hip_stream is not None else kl.stream(0)
         own = None if hip_stream is not None else gs
     layers = 1
-    if attn:
+    finite = None
+    if server:
+        weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
+        w_layers = ring_layers(weights_bytes, server_layer_weight_bytes(heads, kv_heads))
+        kv_layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB),
+                                   kv_layer_bytes(kv_dtype, batch, context, kv_heads))
+        layers = max(w_layers, kv_layers)
+        step, sync, finite = server_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, kv_heads, page,
+                                          w_layers, kv_layers)
+        # the two projections, and QK^T and PV over the context
+        flops_attn = layers * (batch * server_layer_weight_bytes(heads, kv_heads)
+                               + 4.0 * batch * heads * context * ATTN_D)
+    elif attn:
         layer_bytes = kv_layer_bytes(kv_dtype, batch, context, kv_heads)
         layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB), layer_bytes)
         step, sync = attn_steps(torch, kl if kernel == "gsx" else None, gs if kernel == "gsx" else None, stream, dev,
@@ -486,7 +616,15 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     if decode:
         out.update({"workload": workload, "batch": m, "layers": layers,
                     "tbps": done * layers * matrix_bytes(dtype, n, k) / el / 1e12})
-    if attn:
+    if server:
+        step_bytes = layers * (server_layer_weight_bytes(heads, kv_heads)
+                               + kv_layer_bytes(kv_dtype, batch, context, kv_heads))
+        out.update({"workload": workload, "batch": batch, "layers": layers, "weight_layers": w_layers,
+                    "kv_layers": kv_layers, "context": context, "heads": heads, "kv_heads": kv_heads,
+                    "kv_dtype": kv_dtype, "page": page, "window": server_window(context),
+                    "tbps": done * step_bytes / el / 1e12, "tokens_per_s": done * batch / el,
+                    "activations_finite": finite()})
+    elif attn:
         out.update({"workload": workload, "batch": batch, "layers": layers, "context": context, "heads": heads,
                     "kv_heads": kv_heads, "kv_dtype": kv_dtype, "page": page,
                     "tbps": done * layers * kv_layer_bytes(kv_dtype, batch, context, kv_heads) / el / 1e12,
@@ -545,16 +683,19 @@ def build_parser() -> argparse.ArgumentParser:
                     help="operand type of the GEMM: bf16, fp8 (OCP e4m3) or mxfp4 (e2m1 with e8m0 block scales, "
                          "quantised from bf16 by the library; --kernel gsx only); the output stays bf16")
     ap.add_argument("--size", type=int, default=8192)
-    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn"],
+    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server"],
                     help="gemm: one large square GEMM per step (compute-bound); decode: --batch activation rows "
                          "against a ring of --size x --size weight matrices, one launch each (HBM-bandwidth-bound); "
-                         "attn: one decode step of attention per layer over a ring of paged KV caches")
+                         "attn: one decode step of attention per layer over a ring of paged KV caches; server: a "
+                         "whole decode layer per ring layer (QKV projection, RoPE and KV append, attention, output "
+                         "projection) over caches that grow")
     ap.add_argument("--batch", type=int, default=8, metavar="N",
-                    help="--workload decode: the activation rows (M), 1..16; --workload attn: the sequences, 1..256")
+                    help="--workload decode and server: the activation rows (M), 1..16; --workload attn: the sequences, "
+                         "1..256")
     add_attn_arguments(ap)
     ap.add_argument("--weights-gib", type=float, default=None,
-                    help="--workload decode: size of the weight ring (default 4, or a quarter of the share if that "
-                         "is smaller; never fewer than two matrices)")
+                    help="--workload decode and server: size of the weight ring (default 4, or a quarter of the share "
+                         "if that is smaller; never fewer than two matrices or layers)")
     ap.add_argument("--seconds", type=float, default=0.0, help="0 = run forever (like the reference sample)")
     ap.add_argument("--iters", type=int, default=0)
     ap.add_argument("--touch", action="store_true")

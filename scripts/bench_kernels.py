@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the HIP kernels on one MI355X: bf16, fp8 and mxfp4 GEMM (ours vs torch/hipBLASLt), the decode
 GEMM (every configuration vs torch and a read-bandwidth yardstick), the decode attention over a paged KV cache (every
-configuration and split count vs torch SDPA and the same yardstick), HBM fill, stamp/verify."""
+configuration and split count vs torch SDPA and the same yardstick), RoPE + KV append (vs a read-and-rewrite
+yardstick), HBM fill, stamp/verify."""
 import json
 import os
 import statistics
@@ -456,6 +457,113 @@ def attn_decode(shapes=ATTN_SHAPES, heads=ATTN_HEADS, kinds=("bf16", "fp8"), rin
     return out
 
 
+KV_APPEND_SHAPES = [(8, 2048), (64, 512), (1, 16384)]  # (sequences, new tokens each): prefill chunks of 16384 tokens
+KV_APPEND_DECODE = (8, 64, 256)  # sequences of a decode step (T = 1)
+
+
+def kv_append(shapes=KV_APPEND_SHAPES, heads=ATTN_HEADS, kinds=("bf16", "fp8"), ring_bytes=(1 << 30) + 1, reps=3,
+              rounds=3, page=16, decode=KV_APPEND_DECODE, decode_iters=200):
+    """RoPE + KV append.  Prefill-sized: ``b`` sequences of ``t`` new tokens from length 0 into a ring of per-layer
+    paged caches of more than 1 GiB, pages of 16 tokens handed out through a random permutation, a real cos / sin
+    table; one timing is ``reps`` passes over the ring between two events, reported as the median TB/s of ``rounds``
+    repeats (and their spread) of the bytes read (QKV rows and cos / sin rows) plus the bytes written (Q_out and the
+    cache rows).  ``memtest_rewrite_TBps`` is the yardstick: ``gsx_memtest_check`` with ``rewrite``, which reads and
+    writes every byte of a buffer of half the pass's byte total, so both directions count as they do for the kernel;
+    as in :func:`attn_decode` it is ONE call timed by the host's clock, report read-back included, so it reads low by
+    the fixed host cost of a call and the comparison favours the kernel.  Decode-sized (``T = 1``): microseconds per
+    call over ``decode_iters`` back-to-back calls on one layer."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    d = 128
+    for kind in kinds:
+        kdt = torch.bfloat16 if kind == "bf16" else torch.float8_e4m3fn
+        esz = 2 if kind == "bf16" else 1
+        for hq, hkv in heads:
+            rows = hq + 2 * hkv
+            for b, t in [*shapes, *((n, 1) for n in decode)]:
+                tokens = b * t
+                per_seq = -(-t // page)
+                pages = b * per_seq
+                cache = 2 * pages * hkv * page * d * esz  # K and V of one layer
+                layers = max(2, -(-ring_bytes // cache)) if t > 1 else 2
+                moved = tokens * (rows * d * 2 + 2 * (d // 2) * 4 + hq * d * 2 + 2 * hkv * d * esz)
+                kc = torch.zeros(layers, pages, hkv, page, d, device="cuda", dtype=torch.uint8 if esz == 1 else kdt)
+                vc = torch.zeros_like(kc)
+                table = torch.randperm(pages, device="cuda").to(torch.int32).view(b, per_seq).contiguous()
+                lens = torch.zeros(b, device="cuda", dtype=torch.int32)
+                qkv = torch.randn(tokens, rows * d, device="cuda", dtype=torch.bfloat16)
+                qo = torch.empty(tokens, hq, d, device="cuda", dtype=torch.bfloat16)
+                ang = (torch.arange(t, device="cuda", dtype=torch.float64)[:, None]
+                       * 10000.0 ** (-torch.arange(d // 2, device="cuda", dtype=torch.float64) / (d // 2))[None])
+                cos, sin = ang.cos().float().contiguous(), ang.sin().float().contiguous()
+                lb = kc[0].numel() * kc.element_size()
+                torch.cuda.synchronize()
+
+                def args(i):
+                    return (s, kind, qkv.data_ptr(), rows * d, qo.data_ptr(), kc.data_ptr() + i * lb,
+                            vc.data_ptr() + i * lb, table.data_ptr(), lens.data_ptr(), 0, cos.data_ptr(),
+                            sin.data_ptr(), t, b, t, hq, hkv, d, page, pages, per_seq, t)
+
+                row = {"kind": kind, "b": b, "t": t, "heads": hq, "kv_heads": hkv, "page": page, "layers": layers,
+                       "bytes_per_call": moved}
+                if t == 1:
+                    us = []
+                    for r in range(rounds + 1):
+                        ms = hip.time_kv_append(*args(r % layers), decode_iters)
+                        if r:
+                            us.append(ms * 1e3 / decode_iters)
+                    row["gsx_us_per_call"] = round(statistics.median(us), 2)
+                    row["gsx_spread"] = round((max(us) - min(us)) / statistics.median(us), 3)
+                else:
+                    yard = hip.DeviceBuffer(0, (layers * moved // 2) & ~255)
+                    hip.memtest_write(s, yard.addr(), yard.nbytes, 0, MEMTEST_RANDOM, 1)
+                    s.sync()
+                    flipped = [False]
+
+                    def ours():
+                        for i in range(layers):
+                            hip.kv_append(*args(i))
+
+                    def timed(fn):
+                        torch.cuda.synchronize()
+                        with torch.cuda.stream(ts):
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record(ts)
+                            for _ in range(reps):
+                                fn()
+                            e1.record(ts)
+                        e1.synchronize()
+                        return reps * layers * moved / (e0.elapsed_time(e1) * 1e-3) / 1e12
+
+                    def yardstick():  # every call leaves the complement of what it found
+                        s.sync()
+                        t0 = time.perf_counter()
+                        rep = hip.memtest_check(s, yard.addr(), yard.nbytes, 0, MEMTEST_RANDOM, 1, flipped[0], True)
+                        dt = time.perf_counter() - t0
+                        flipped[0] = not flipped[0]
+                        assert rep.bad_dwords == 0
+                        return 2 * yard.nbytes / dt / 1e12
+
+                    runs = {"gsx": [], "memtest_rewrite": []}
+                    for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                        for name, fn in (("gsx", lambda: timed(ours)), ("memtest_rewrite", yardstick)):
+                            v = fn()
+                            if r:
+                                runs[name].append(v)
+                    for name, v in runs.items():
+                        med = statistics.median(v)
+                        row[f"{name}_TBps"] = round(med, 3)
+                        row[f"{name}_spread"] = round((max(v) - min(v)) / med, 3)
+                    yard.free()
+                out.append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                del kc, vc, table, lens, qkv, qo, cos, sin
+                torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 def hbm(nbytes=16 << 30, reps=5):
     s = hip.Stream(0)
     buf = hip.DeviceBuffer(0, nbytes)
@@ -487,6 +595,7 @@ if __name__ == "__main__":
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
                 "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "attn_decode": attn_decode,
+                "kv_append": kv_append,
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
                 "hbm": hbm}
