@@ -117,6 +117,11 @@ def lib():
         # stream, kind, QKV, qkv_stride, Q_out, K_cache, V_cache, block_table, seq_lens, lens_out, rope_cos, rope_sin;
         # rope_len, B, T, Hq, Hkv, D, page, num_pages, table_stride, max_seq_len; k_inv_scale, v_inv_scale
         _kv_append_sig = [vp, i32, vp, ctypes.c_int64] + [vp] * 8 + [i32] * 10 + [ctypes.c_float] * 2
+        # stream, out_kind, X, x_stride, R_in, R_out, r_stride, W, Y, y_stride, scale_out; M, H; eps
+        _norm_sig = [vp, i32, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, i32, i32,
+                     ctypes.c_float]
+        # stream, out_kind, GU, gu_stride, Y, y_stride, scale_out; M, I
+        _silu_sig = [vp, i32, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, i32, i32]
         sig = {
             "gsx_last_error": ([], ctypes.c_char_p),
             "gsx_device_count": ([ctypes.POINTER(i32)], i32),
@@ -168,6 +173,10 @@ def lib():
             "gsx_event_time_decode_attn": ([*_attn_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_kv_append": (_kv_append_sig, i32),
             "gsx_event_time_kv_append": ([*_kv_append_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_add_rmsnorm": (_norm_sig, i32),
+            "gsx_event_time_add_rmsnorm": ([*_norm_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_silu_mul": (_silu_sig, i32),
+            "gsx_event_time_silu_mul": ([*_silu_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
             "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
                                   i32),
@@ -714,4 +723,64 @@ def time_kv_append(stream: Stream, kind: str, qkv: int, qkv_stride: int, q_out: 
                                                         b, t, hq, hkv, d, page, num_pages, table_stride, max_seq_len,
                                                         k_inv_scale, v_inv_scale), iters, ctypes.byref(ms)),
         "time_kv_append")
+    return ms.value
+
+
+# ``out_kind`` of the norm and activation kernels (gsx_kernels.h): bf16, or OCP e4m3 with one scale per row
+ACT_OUT_KINDS = {"bf16": 0, "fp8": 1}
+
+
+def _act_kind(out_kind: str) -> int:
+    if out_kind not in ACT_OUT_KINDS:
+        raise ValueError(f"output kind {out_kind!r}: one of {', '.join(ACT_OUT_KINDS)}")
+    return ACT_OUT_KINDS[out_kind]
+
+
+def _add_rmsnorm_args(stream: Stream, out_kind: str, x: int, x_stride: int, r_in: int, r_out: int, r_stride: int,
+                      w: int, y: int, y_stride: int, scale_out: int, m: int, h: int, eps: float) -> tuple:
+    return (stream.handle, _act_kind(out_kind), ctypes.c_void_p(x), x_stride, ctypes.c_void_p(r_in),
+            ctypes.c_void_p(r_out), r_stride, ctypes.c_void_p(w), ctypes.c_void_p(y), y_stride,
+            ctypes.c_void_p(scale_out), m, h, eps)
+
+
+def add_rmsnorm(stream: Stream, out_kind: str, x: int, x_stride: int, r_in: int, r_out: int, r_stride: int, w: int,
+                y: int, y_stride: int, scale_out: int, m: int, h: int, eps: float):
+    """Fused residual add and RMSNorm of ``m`` rows of ``h`` bf16 elements: ``hid = bf16(x + r_in)`` (``x`` itself
+    with ``r_in`` 0), ``r_out = hid`` (0: not written; ``r_out == r_in``: in place) and ``y = hid / sqrt(mean(hid^2) +
+    eps) * w``.  ``out_kind`` ``"bf16"`` writes ``y`` as bf16 and takes ``scale_out`` 0; ``"fp8"`` writes OCP e4m3
+    bytes and ``scale_out[m]`` (fp32) ``= max|y| / 448`` per row: the ``a`` and ``scale_a`` of
+    ``decode_gemm_nt("fp8", ..., scale_mode=SCALE_ROW)``.  Strides are in elements.  All addresses are device
+    addresses; 0 means NULL.  Not synchronised."""
+    _ck(lib().gsx_add_rmsnorm(*_add_rmsnorm_args(stream, out_kind, x, x_stride, r_in, r_out, r_stride, w, y, y_stride,
+                                                 scale_out, m, h, eps)), "add_rmsnorm")
+
+
+def time_add_rmsnorm(stream: Stream, out_kind: str, x: int, x_stride: int, r_in: int, r_out: int, r_stride: int,
+                     w: int, y: int, y_stride: int, scale_out: int, m: int, h: int, eps: float, iters: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_add_rmsnorm(*_add_rmsnorm_args(stream, out_kind, x, x_stride, r_in, r_out, r_stride, w, y,
+                                                            y_stride, scale_out, m, h, eps), iters, ctypes.byref(ms)),
+        "time_add_rmsnorm")
+    return ms.value
+
+
+def _silu_mul_args(stream: Stream, out_kind: str, gu: int, gu_stride: int, y: int, y_stride: int, scale_out: int,
+                   m: int, i: int) -> tuple:
+    return (stream.handle, _act_kind(out_kind), ctypes.c_void_p(gu), gu_stride, ctypes.c_void_p(y), y_stride,
+            ctypes.c_void_p(scale_out), m, i)
+
+
+def silu_mul(stream: Stream, out_kind: str, gu: int, gu_stride: int, y: int, y_stride: int, scale_out: int, m: int,
+             i: int):
+    """SwiGLU: row ``r`` of ``gu[m][gu_stride]`` (bf16) holds ``i`` gate values, then ``i`` up values;
+    ``y[r][c] = silu(gate[c]) * up[c]``, as bf16 or (``out_kind`` ``"fp8"``) as OCP e4m3 with ``scale_out[m]``, as
+    :func:`add_rmsnorm` writes them.  All addresses are device addresses; 0 means NULL.  Not synchronised."""
+    _ck(lib().gsx_silu_mul(*_silu_mul_args(stream, out_kind, gu, gu_stride, y, y_stride, scale_out, m, i)), "silu_mul")
+
+
+def time_silu_mul(stream: Stream, out_kind: str, gu: int, gu_stride: int, y: int, y_stride: int, scale_out: int,
+                  m: int, i: int, iters: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_silu_mul(*_silu_mul_args(stream, out_kind, gu, gu_stride, y, y_stride, scale_out, m, i),
+                                      iters, ctypes.byref(ms)), "time_silu_mul")
     return ms.value

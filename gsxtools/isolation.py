@@ -27,7 +27,8 @@ exact environment the device plugin's Allocate produces, in four scenarios:
 
 ``--workload decode`` or ``--workload attn`` makes every pod of the other scenarios such a pod.  ``--workload server``
 (a whole decode layer per ring layer: projections, RoPE and KV append, attention) does so for ``solo``, ``solo64``,
-``shared`` and ``partitioned``; it runs on the library's kernels only.
+``shared`` and ``partitioned``; it runs on the library's kernels only.  ``--workload layer`` (the same with a residual
+stream, two RMSNorms and the SwiGLU MLP of ``--ffn`` columns: a whole decoder layer) takes the same scenarios.
 Reported per scenario: per-pod TFLOP/s, aggregate, and fairness (min/max); for
 decode and attention pods also the TB/s of weight or KV bytes they streamed.
 Run: ``python -m gsxtools.isolation --seconds 8``.
@@ -88,7 +89,7 @@ def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str
                "--size", str(sz), "--seconds", str(seconds), "--dtype", dtype, "--json"]
         if wl != "gemm":  # the default is left off the command line
             cmd += ["--workload", wl, "--batch", str(batch)]
-        if wl in ("attn", "server"):
+        if wl in ("attn", "server", "layer"):
             cmd += attn_args or []
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                                       cwd=str(ROOT)))
@@ -133,6 +134,14 @@ def server_cmdline(a: argparse.Namespace) -> list[str]:
     return attn_cmdline(a) + (["--weights-gib", str(a.weights_gib)] if a.weights_gib is not None else [])
 
 
+SCENARIOS_LAYER = SCENARIOS_SERVER
+
+
+def layer_cmdline(a: argparse.Namespace) -> list[str]:
+    """The layer pods' options: the server pods', and the MLP's width."""
+    return server_cmdline(a) + (["--ffn", str(a.ffn)] if a.ffn is not None else [])
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = pod_workload.BatchRangeParser()
     ap.add_argument("--pods", type=int, default=4)
@@ -144,16 +153,19 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"],
                     help="the pods' GEMM operand type (mxfp4: with --kernel gsx only)")
     ap.add_argument("--size", type=int, default=8192)
-    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server"],
+    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server", "layer"],
                     help="what the pods run: the large GEMM, the decode workload (--batch rows against a ring of "
                          "--size x --size weights), the attention workload (--batch sequences of --context tokens), "
-                         "or the server workload (a decode layer per ring layer; solo, solo64, shared, partitioned)")
+                         "the server workload (a decode layer per ring layer; solo, solo64, shared, partitioned), or the "
+                         "layer workload (a whole decoder layer per ring layer; the same scenarios)")
     ap.add_argument("--batch", type=int, default=8, metavar="N",
                     help="the decode pods' activation rows (1..16), or the attention pods' sequences (1..256, with "
                          "--workload attn)")
     pod_workload.add_attn_arguments(ap)
     ap.add_argument("--weights-gib", type=float, default=None,
-                    help="--workload server: size of the pods' weight ring (default: the workload's)")
+                    help="--workload server and layer: size of the pods' weight ring (default: the workload's)")
+    ap.add_argument("--ffn", type=int, default=None,
+                    help="--workload layer: width of the pods' MLP (default: the workload's)")
     ap.add_argument("--small-size", type=int, default=2048)
     ap.add_argument("--scenarios",
                     default="solo,shared,partitioned,env,env-gsx,solo-small,solo64,noisy,noisy-partitioned")
@@ -164,16 +176,17 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     results = []
-    own_size = a.workload in ("decode", "attn", "server")  # pods whose work --size / --small-size does not scale
+    own_size = a.workload in ("decode", "attn", "server", "layer")  # pods whose work --size does not scale
+    pod_args = {"server": server_cmdline, "layer": layer_cmdline}.get(a.workload, attn_cmdline)(a)
 
-    def run(*args):  # every scenario's pods get the attention options: only attention and server pods use them
-        return run_pods(*args, attn_args=server_cmdline(a) if a.workload == "server" else attn_cmdline(a))
+    def run(*args):  # every scenario's pods get the attention options: only attention, server and layer pods use them
+        return run_pods(*args, attn_args=pod_args)
 
     for sc in a.scenarios.split(","):
         if sc not in SCENARIOS:
             raise SystemExit(f"unknown scenario {sc}")
-        if a.workload == "server" and sc not in SCENARIOS_SERVER:
-            raise SystemExit(f"--workload server: scenario {sc} is not one of {', '.join(SCENARIOS_SERVER)}")
+        if a.workload in ("server", "layer") and sc not in SCENARIOS_SERVER:
+            raise SystemExit(f"--workload {a.workload}: scenario {sc} is not one of {', '.join(SCENARIOS_SERVER)}")
         if sc == "solo":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, False)
             res = run(envs, a.seconds, a.kernel, a.size, "none", a.dtype, a.workload, a.batch)

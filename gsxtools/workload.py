@@ -30,6 +30,8 @@ kv_ring_layers = _mod.kv_ring_layers
 add_attn_arguments = _mod.add_attn_arguments
 server_layer_weight_bytes = _mod.server_layer_weight_bytes
 server_window = _mod.server_window
+default_ffn = _mod.default_ffn
+layer_weight_bytes = _mod.layer_weight_bytes
 BatchRangeParser = _mod._Parser
 
 if __name__ == "__main__":

@@ -30,6 +30,9 @@
 //  * RoPE + KV append    — rotates Q and K and writes the new tokens' K and V into
 //                          their page slots, quantised for an e4m3 cache: what makes
 //                          the cache the attention reads (kv_append.hip);
+//  * add + RMSNorm, SwiGLU — the residual stream, the normalisation and the MLP's activation of
+//                          a decoder layer, to bf16 or to e4m3 with a scale per row
+//                          (norm_act.hip);
 //  * CU-masked streams   — hipExtStreamCreateWithCUMask.
 //
 // All functions return 0 or a hipError_t value; gsx_last_error() has text.
@@ -310,6 +313,60 @@ int gsx_event_time_kv_append(void* stream, int kind, const void* QKV, int64_t qk
                              const float* rope_cos, const float* rope_sin, int rope_len, int B, int T, int Hq, int Hkv,
                              int D, int page, int num_pages, int table_stride, int max_seq_len, float k_inv_scale,
                              float v_inv_scale, int iters, float* ms);
+
+// Fused residual add + RMSNorm, and SwiGLU (norm_act.hip): what a decoder layer has between its projections.  Both
+// write bf16, or OCP e4m3 with one fp32 scale per row, which is exactly the A and scale_a that
+// gsx_decode_gemm_nt(GSX_DECODE_FP8, .., GSX_GEMM_SCALE_ROW) takes.  Strides are in elements of the row's type.
+//   GSX_ACT_OUT_BF16      Y[M][y_stride] bf16 = bf16(y32), round to nearest even; scale_out NULL
+//   GSX_ACT_OUT_FP8_ROW   Y[M][y_stride] bytes, OCP e4m3fn; scale_out[M] fp32, device memory, 4-B aligned.  Per row,
+//                         amax = max |y32| over the unrounded fp32 values, scale_out[m] = fl(amax / 448) and
+//                         Y = e4m3(fl(y32 * fl(448 / amax))), round to nearest even, saturating at +-448 (the
+//                         conversion of gsx_kv_append): the row's largest element is 0x7e or 0xfe.  A row of zeros
+//                         has scale 1.0f and every code 0x00.  The encoded value is within 3 * 2^-24 (relative) of
+//                         y32 / scale_out[m]: two divisions and one multiplication.
+// gsx_add_rmsnorm: X[M][x_stride] bf16 (a sublayer's output), W[H] bf16, R_in and R_out bf16 [M][r_stride] (the
+// residual stream; either may be NULL; R_out == R_in updates it in place).  Per row:
+//   h = bf16(fl(x + r))           round to nearest even; with R_in NULL h = x, a raw 16-bit copy
+//   R_out = h                     if R_out is given
+//   ss = sum of h^2               fp32; every square is exact
+//   rinv = 1 / sqrt(ss / H + eps)
+//   y32 = (h * rinv) * w          fp32
+// The norm works on the rounded h.  A row whose ss / H + eps is 0 is outside the contract.
+// gsx_silu_mul: row m of GU[M][gu_stride] (bf16) holds I gate values, then I up values (the fused gate / up
+// projection's output); y32 = g / (1 + exp(-g)) * u.  The contract covers finite inputs with |g| <= 64; an exact
+// result of nonzero magnitude below 2^-100 is outside it.  A non-finite g or u makes that element unspecified with
+// GSX_ACT_OUT_BF16 and its whole row (scale included) with GSX_ACT_OUT_FP8_ROW; nothing is ever written outside Y and
+// scale_out.
+// Numerics: a bound, not bit-exactness (an FMA may stand for a multiply and an add).  y32 lies within a relative
+// error delta of the exact value, u = 2^-24 per correctly rounded fp32 operation:
+//   norm   delta = (n_chain + n_tree + 6) u.  The sum of squares adds a thread's 8 * ceil(H / 2048) squares in turn
+//          (n_chain; at most 64) and combines 256 threads in a fixed tree of n_tree = 8 levels, so ss is off by at most
+//          (n_chain + n_tree) u <= 72 u.  Then ss / H, + eps, sqrtf and 1 / x, each correctly rounded (the square
+//          root halves what precedes it; the bound does not claim that), h * rinv and * w: 6 u.
+//   silu   delta(g) = (4 + |g|) 2^-23.  t = fl(g * -log2 e) is off by 2 u |t| with the constant's own rounding, which
+//          v_exp_f32 turns into |g| 2^-23 relative; v_exp_f32 itself 2^-23; 1 + e: u; v_rcp_f32: 2^-23; the two
+//          multiplies: 2 u.  In all (|g| + 3.5) 2^-23.  The 2^-23 of v_exp_f32 and v_rcp_f32 is the ISA's documented
+//          1 ulp.
+// The result is deterministic and does not depend on M, on a row's index or on where workgroups run: nothing passes
+// between workgroups.
+// Requirements: a known out_kind; M >= 1; 8 <= H <= 16384 and H % 8 == 0; I >= 8, I % 8 == 0, and I <= 32768 with
+// GSX_ACT_OUT_FP8_ROW (a workgroup holds a row); every stride at least its row (gu_stride >= 2 I) and a multiple of 8;
+// X, W, GU and Y non-NULL; scale_out NULL exactly with GSX_ACT_OUT_BF16; X, R_in, R_out, W, GU and Y 16-B aligned (rows
+// of e4m3 are then 8-B aligned); Y overlaps no input; R_out overlaps nothing but an R_in equal to it; scale_out
+// overlaps nothing; eps finite and >= 0.  Row offsets are 64-bit: M * stride may exceed 2^31.  Everything is validated
+// before the first device call; launches on `stream` and returns without synchronising.
+enum { GSX_ACT_OUT_BF16 = 0, GSX_ACT_OUT_FP8_ROW = 1 };
+int gsx_add_rmsnorm(void* stream, int out_kind, const void* X, int64_t x_stride, const void* R_in, void* R_out,
+                    int64_t r_stride, const void* W, void* Y, int64_t y_stride, float* scale_out, int M, int H,
+                    float eps);
+int gsx_silu_mul(void* stream, int out_kind, const void* GU, int64_t gu_stride, void* Y, int64_t y_stride,
+                 float* scale_out, int M, int I);
+// elapsed milliseconds of `iters` back-to-back calls on `stream`, by hip events (for benches)
+int gsx_event_time_add_rmsnorm(void* stream, int out_kind, const void* X, int64_t x_stride, const void* R_in,
+                               void* R_out, int64_t r_stride, const void* W, void* Y, int64_t y_stride,
+                               float* scale_out, int M, int H, float eps, int iters, float* ms);
+int gsx_event_time_silu_mul(void* stream, int out_kind, const void* GU, int64_t gu_stride, void* Y, int64_t y_stride,
+                            float* scale_out, int M, int I, int iters, float* ms);
 
 // HBM pre-flight memory test (memtest.hip).  The expected content of 16-byte word W = origin/16 + word index is
 // generated from (pattern, seed, invert, W) and never stored; `origin` is the byte offset of `base` in the whole

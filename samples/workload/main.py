@@ -37,7 +37,15 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   layer's activations.  Nothing in a step waits for the host.  The sequence lengths live on the device and grow from
   ``--context`` minus a window to ``--context``, then start again, so the run can go on forever.  The weight ring is
   sized by ``--weights-gib`` and the KV ring by ``--kv-gib``; it reports ``tokens_per_s`` and ``tbps`` (weight plus KV
-  bytes read per second).
+  bytes read per second);
+* ``--workload layer`` is a whole decoder layer per ring layer and step, again on the library's kernels only: the
+  server workload's attention half between a residual stream and its normalisations, and the MLP, which holds two
+  thirds of a layer's weights.  Per layer: ``gsx_add_rmsnorm`` (the residual add fused with the RMSNorm), the QKV
+  projection, RoPE and KV append, the attention, the output projection, ``gsx_add_rmsnorm`` again, the fused gate / up
+  projection to ``2 x --ffn`` columns, ``gsx_silu_mul`` and the down projection.  ``--ffn`` is the MLP's width (default
+  3.5 x hidden, rounded to a multiple of 64).  Layer 0 of every step starts the residual stream afresh from a constant
+  input, so an endless run stays finite.  The weights are bf16; it takes the server workload's other options and
+  reports the same fields and ``ffn``.
 """
 from __future__ import annotations
 
@@ -126,6 +134,18 @@ def server_window(context: int) -> int:
     return min(SERVER_WINDOW, context)
 
 
+def default_ffn(hidden: int) -> int:
+    """The MLP's width when ``--ffn`` is not given: 3.5 x ``hidden``, rounded to a multiple of 64."""
+    return max(64, round(3.5 * hidden / 64) * 64)
+
+
+def layer_weight_bytes(heads: int, kv_heads: int, ffn: int) -> int:
+    """Bytes of one decoder layer's bf16 weights: the server layer's two projections, the fused gate / up projection
+    ``[2 ffn][hidden]`` and the down projection ``[hidden][ffn]`` (the norm weights, 4 x hidden bytes, are not
+    counted)."""
+    return server_layer_weight_bytes(heads, kv_heads) + 3 * ffn * heads * ATTN_D * 2
+
+
 def ring_layers(weights_bytes: int, one_matrix_bytes: int) -> int:
     """Matrices in the weight ring: enough to cover ``weights_bytes``, and never fewer than two, so that no launch
     finds its matrix where the last launch left it."""
@@ -161,6 +181,11 @@ class Kernels:
             L.gsx_kv_append.argtypes = ([vp, i32, vp, ctypes.c_int64] + [vp] * 8 + [i32] * 10
                                         + [ctypes.c_float] * 2)
             L.gsx_kv_append.restype = i32
+        if hasattr(L, "gsx_add_rmsnorm"):  # likewise: an image built before the norm and activation kernels
+            i64 = ctypes.c_int64
+            L.gsx_add_rmsnorm.argtypes = [vp, i32, vp, i64, vp, vp, i64, vp, vp, i64, vp, i32, i32, ctypes.c_float]
+            L.gsx_silu_mul.argtypes = [vp, i32, vp, i64, vp, i64, vp, i32, i32]
+            L.gsx_add_rmsnorm.restype = L.gsx_silu_mul.restype = i32
         L.gsx_last_error.argtypes, L.gsx_last_error.restype = [], ctypes.c_char_p
         self.L, self.path = L, path
 
@@ -236,6 +261,18 @@ class Kernels:
                                       *(ctypes.c_void_p(x) for x in (q_out, kc, vc, table, lens, lens_out, cos, sin)),
                                       rope_len, b, t, hq, hkv, ATTN_D, page, num_pages, table_stride, max_seq_len,
                                       1.0, 1.0), "kv_append")
+
+    def add_rmsnorm(self, s, x: int, r_in: int, r_out: int, w: int, y: int, m: int, h: int, eps: float):
+        """``hid = bf16(x + r_in)`` (``x`` with ``r_in`` 0) to ``r_out``, and its RMSNorm times ``w`` to ``y``: bf16,
+        contiguous rows."""
+        if not hasattr(self.L, "gsx_add_rmsnorm"):
+            raise RuntimeError(f"{self.path} has no gsx_add_rmsnorm: rebuild it")
+        self._ck(self.L.gsx_add_rmsnorm(s, 0, ctypes.c_void_p(x), h, ctypes.c_void_p(r_in), ctypes.c_void_p(r_out), h,
+                                        ctypes.c_void_p(w), ctypes.c_void_p(y), h, None, m, h, eps), "add_rmsnorm")
+
+    def silu_mul(self, s, gu: int, y: int, m: int, i: int):
+        """``y[m][i] = silu(gu[:, :i]) * gu[:, i:]``: bf16, contiguous rows."""
+        self._ck(self.L.gsx_silu_mul(s, 0, ctypes.c_void_p(gu), 2 * i, ctypes.c_void_p(y), i, None, m, i), "silu_mul")
 
     def sync(self, s):
         self._ck(self.L.gsx_stream_sync(s), "stream_sync")
@@ -441,11 +478,104 @@ def server_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, he
     return step, sync, finite
 
 
+LAYER_EPS = 1e-5
+
+
+def layer_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, heads: int, kv_heads: int, page: int,
+                ffn: int, w_layers: int, kv_layers: int):
+    """``(step, sync, finite)`` of the layer workload: :func:`server_steps` with a residual stream, the two
+    normalisations and the MLP.  A ring of ``w_layers`` decoder layers' bf16 weights (random normal over the square
+    root of the input width; norm weights of 1), a ring of ``kv_layers`` paged KV caches, and a step that runs
+    ``max(w_layers, kv_layers)`` layers back to back on the library's stream.  Layer 0 takes the constant input with
+    no residual and writes the residual buffer; every later add updates it in place."""
+    hidden, nqkv = heads * ATTN_D, (heads + 2 * kv_heads) * ATTN_D
+    per_seq, pages = kv_pages(batch, context, page)
+    window = server_window(context)
+    layers = max(w_layers, kv_layers)
+    bf = torch.bfloat16
+    wqkv = torch.empty(w_layers, nqkv, hidden, device=dev, dtype=bf)
+    wo = torch.empty(w_layers, hidden, hidden, device=dev, dtype=bf)
+    wgu = torch.empty(w_layers, 2 * ffn, hidden, device=dev, dtype=bf)
+    wdown = torch.empty(w_layers, hidden, ffn, device=dev, dtype=bf)
+    for i in range(w_layers):  # one matrix at a time: nothing larger is ever held in fp32
+        for w, k in ((wqkv, hidden), (wo, hidden), (wgu, hidden), (wdown, ffn)):
+            w[i].copy_(torch.randn(w.shape[1], k, device=dev) / math.sqrt(k))
+    ln = torch.ones(w_layers, 2, hidden, device=dev, dtype=bf)
+    kdt = bf if kv_dtype == "bf16" else torch.float8_e4m3fn
+    kc = torch.empty(kv_layers, pages, kv_heads, page, ATTN_D, device=dev, dtype=kdt)
+    vc = torch.empty_like(kc)
+    for i in range(kv_layers):
+        for c in (kc, vc):
+            c[i].copy_(torch.randn(pages, kv_heads, page, ATTN_D, device=dev, dtype=bf).to(kdt))
+    table = torch.randperm(pages, device=dev).to(torch.int32).view(batch, per_seq).contiguous()
+    start = torch.full((batch,), context - window, device=dev, dtype=torch.int32)
+    lens = [torch.zeros(batch, device=dev, dtype=torch.int32) for _ in range(2)]
+    ang = (torch.arange(context, device=dev, dtype=torch.float64)[:, None]
+           * 10000.0 ** (-torch.arange(ATTN_D // 2, device=dev, dtype=torch.float64) / (ATTN_D // 2))[None])
+    cos, sin = ang.cos().float().contiguous(), ang.sin().float().contiguous()
+    x0 = torch.randn(batch, hidden, device=dev, dtype=bf)  # layer 0's input, constant
+    resid, xn, sub = (torch.zeros(batch, hidden, device=dev, dtype=bf) for _ in range(3))
+    qkv = torch.empty(batch, nqkv, device=dev, dtype=bf)
+    q = torch.empty(batch, heads, ATTN_D, device=dev, dtype=bf)
+    o = torch.empty_like(q)
+    gu = torch.empty(batch, 2 * ffn, device=dev, dtype=bf)
+    act = torch.empty(batch, ffn, device=dev, dtype=bf)
+    ws_bytes = kl.attn_workspace_bytes(batch, heads, page, context)
+    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+    wqkv_b, wo_b, wgu_b, wdown_b = (w[0].numel() * 2 for w in (wqkv, wo, wgu, wdown))
+    cache_bytes = kc[0].numel() * kc.element_size()
+    scale = 1.0 / math.sqrt(ATTN_D)
+    torch.cuda.synchronize()
+    count = [0]
+
+    def step():
+        k = count[0] % window
+        count[0] += 1
+        lens_in = start if k == 0 else lens[(k - 1) % 2]
+        lens_out = lens[k % 2]
+        for i in range(layers):
+            wi = i % w_layers
+            kci, vci = kc.data_ptr() + (i % kv_layers) * cache_bytes, vc.data_ptr() + (i % kv_layers) * cache_bytes
+            ln1 = ln.data_ptr() + wi * 2 * hidden * 2
+            if i == 0:  # the residual stream starts afresh
+                kl.add_rmsnorm(gs, x0.data_ptr(), 0, resid.data_ptr(), ln1, xn.data_ptr(), batch, hidden, LAYER_EPS)
+            else:
+                kl.add_rmsnorm(gs, sub.data_ptr(), resid.data_ptr(), resid.data_ptr(), ln1, xn.data_ptr(), batch,
+                               hidden, LAYER_EPS)
+            kl.decode_gemm(gs, "bf16", xn.data_ptr(), wqkv.data_ptr() + wi * wqkv_b, qkv.data_ptr(), batch, nqkv,
+                           hidden)
+            kl.kv_append(gs, kv_dtype, qkv.data_ptr(), nqkv, q.data_ptr(), kci, vci, table.data_ptr(),
+                         lens_in.data_ptr(), lens_out.data_ptr(), cos.data_ptr(), sin.data_ptr(), context, batch, 1,
+                         heads, kv_heads, page, pages, per_seq, context)
+            kl.decode_attn(gs, kv_dtype, q.data_ptr(), kci, vci, table.data_ptr(), lens_out.data_ptr(), o.data_ptr(),
+                           batch, heads, kv_heads, page, pages, per_seq, context, scale, ws.data_ptr(), ws_bytes)
+            kl.decode_gemm(gs, "bf16", o.data_ptr(), wo.data_ptr() + wi * wo_b, sub.data_ptr(), batch, hidden, hidden)
+            kl.add_rmsnorm(gs, sub.data_ptr(), resid.data_ptr(), resid.data_ptr(), ln1 + hidden * 2, xn.data_ptr(),
+                           batch, hidden, LAYER_EPS)
+            kl.decode_gemm(gs, "bf16", xn.data_ptr(), wgu.data_ptr() + wi * wgu_b, gu.data_ptr(), batch, 2 * ffn,
+                           hidden)
+            kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), batch, ffn)
+            kl.decode_gemm(gs, "bf16", act.data_ptr(), wdown.data_ptr() + wi * wdown_b, sub.data_ptr(), batch, hidden,
+                           ffn)
+
+    def sync():
+        kl.sync(gs)
+
+    def finite():
+        kl.sync(gs)
+        return all(bool(torch.isfinite(t.float()).all()) for t in (resid, xn, sub, qkv, q, o, gu, act))
+
+    # the closures hold addresses, not tensors
+    step.keep = (wqkv, wo, wgu, wdown, ln, kc, vc, table, start, lens, cos, sin, x0, resid, xn, sub, qkv, q, o, gu, act,
+                 ws)
+    return step, sync, finite
+
+
 def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 8192, seconds: float = 0.0,
         iters: int = 0, report_every: float = 5.0, touch: bool = False, quiet: bool = False,
         probe_limit: bool = False, dtype: str = "bf16", workload: str = "gemm", batch: int = 8,
         weights_gib: float | None = None, context: int = 8192, heads: int = 64, kv_heads: int = 8,
-        kv_dtype: str = "bf16", kv_gib: float | None = None, page: int = 16) -> dict:
+        kv_dtype: str = "bf16", kv_gib: float | None = None, page: int = 16, ffn: int | None = None) -> dict:
     import torch
 
     lib_path = kernels_lib_path()
@@ -477,18 +607,23 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     m = n = k = size
     if dtype not in ("bf16", "fp8", "mxfp4"):
         raise SystemExit(f"--dtype {dtype}: bf16, fp8 or mxfp4")
-    if workload not in ("gemm", "decode", "attn", "server"):
-        raise SystemExit(f"--workload {workload}: gemm, decode, attn or server")
+    if workload not in ("gemm", "decode", "attn", "server", "layer"):
+        raise SystemExit(f"--workload {workload}: gemm, decode, attn, server or layer")
     decode = workload == "decode"
-    server = workload == "server"
+    layer = workload == "layer"
+    server = workload == "server" or layer  # the layer workload is the server workload with more in a layer
     attn = workload == "attn" or server  # the server workload has the attention's shape options
     if server:
         if kernel != "gsx":
-            raise SystemExit("--workload server runs on the library's kernels only (--kernel gsx)")
+            raise SystemExit(f"--workload {workload} runs on the library's kernels only (--kernel gsx)")
         if dtype != "bf16":
-            raise SystemExit("--workload server: the weights are bf16 only (the KV cache: --kv-dtype)")
+            raise SystemExit(f"--workload {workload}: the weights are bf16 only (the KV cache: --kv-dtype)")
         if not 1 <= batch <= 16:
             raise SystemExit(f"--batch {batch}: 1..16")
+    if layer:
+        ffn = default_ffn(heads * ATTN_D) if ffn is None else ffn
+        if ffn < 64 or ffn % 64:
+            raise SystemExit(f"--ffn {ffn}: a multiple of 64, at least 64")
     if attn:
         if not 1 <= batch <= 256:
             raise SystemExit(f"--batch {batch}: 1..256 sequences")
@@ -525,15 +660,20 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     finite = None
     if server:
         weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
-        w_layers = ring_layers(weights_bytes, server_layer_weight_bytes(heads, kv_heads))
+        one_layer_bytes = (layer_weight_bytes(heads, kv_heads, ffn) if layer
+                           else server_layer_weight_bytes(heads, kv_heads))
+        w_layers = ring_layers(weights_bytes, one_layer_bytes)
         kv_layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB),
                                    kv_layer_bytes(kv_dtype, batch, context, kv_heads))
         layers = max(w_layers, kv_layers)
-        step, sync, finite = server_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, kv_heads, page,
-                                          w_layers, kv_layers)
-        # the two projections, and QK^T and PV over the context
-        flops_attn = layers * (batch * server_layer_weight_bytes(heads, kv_heads)
-                               + 4.0 * batch * heads * context * ATTN_D)
+        if layer:
+            step, sync, finite = layer_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, kv_heads, page, ffn,
+                                             w_layers, kv_layers)
+        else:
+            step, sync, finite = server_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, kv_heads, page,
+                                              w_layers, kv_layers)
+        # the projections (2 flops per weight and row: a weight is 2 bytes), and QK^T and PV over the context
+        flops_attn = layers * (batch * one_layer_bytes + 4.0 * batch * heads * context * ATTN_D)
     elif attn:
         layer_bytes = kv_layer_bytes(kv_dtype, batch, context, kv_heads)
         layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB), layer_bytes)
@@ -617,13 +757,14 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         out.update({"workload": workload, "batch": m, "layers": layers,
                     "tbps": done * layers * matrix_bytes(dtype, n, k) / el / 1e12})
     if server:
-        step_bytes = layers * (server_layer_weight_bytes(heads, kv_heads)
-                               + kv_layer_bytes(kv_dtype, batch, context, kv_heads))
+        step_bytes = layers * (one_layer_bytes + kv_layer_bytes(kv_dtype, batch, context, kv_heads))
         out.update({"workload": workload, "batch": batch, "layers": layers, "weight_layers": w_layers,
                     "kv_layers": kv_layers, "context": context, "heads": heads, "kv_heads": kv_heads,
                     "kv_dtype": kv_dtype, "page": page, "window": server_window(context),
                     "tbps": done * step_bytes / el / 1e12, "tokens_per_s": done * batch / el,
                     "activations_finite": finite()})
+        if layer:
+            out["ffn"] = ffn
     elif attn:
         out.update({"workload": workload, "batch": batch, "layers": layers, "context": context, "heads": heads,
                     "kv_heads": kv_heads, "kv_dtype": kv_dtype, "page": page,
@@ -683,19 +824,22 @@ def build_parser() -> argparse.ArgumentParser:
                     help="operand type of the GEMM: bf16, fp8 (OCP e4m3) or mxfp4 (e2m1 with e8m0 block scales, "
                          "quantised from bf16 by the library; --kernel gsx only); the output stays bf16")
     ap.add_argument("--size", type=int, default=8192)
-    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server"],
+    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server", "layer"],
                     help="gemm: one large square GEMM per step (compute-bound); decode: --batch activation rows "
                          "against a ring of --size x --size weight matrices, one launch each (HBM-bandwidth-bound); "
                          "attn: one decode step of attention per layer over a ring of paged KV caches; server: a "
                          "whole decode layer per ring layer (QKV projection, RoPE and KV append, attention, output "
-                         "projection) over caches that grow")
+                         "projection) over caches that grow; layer: a whole decoder layer per ring layer (the server "
+                         "workload's with a residual stream, two RMSNorms and the SwiGLU MLP)")
     ap.add_argument("--batch", type=int, default=8, metavar="N",
-                    help="--workload decode and server: the activation rows (M), 1..16; --workload attn: the sequences, "
-                         "1..256")
+                    help="--workload decode, server and layer: the activation rows (M), 1..16; --workload attn: the "
+                         "sequences, 1..256")
     add_attn_arguments(ap)
     ap.add_argument("--weights-gib", type=float, default=None,
-                    help="--workload decode and server: size of the weight ring (default 4, or a quarter of the share "
-                         "if that is smaller; never fewer than two matrices or layers)")
+                    help="--workload decode, server and layer: size of the weight ring (default 4, or a quarter of the "
+                         "share if that is smaller; never fewer than two matrices or layers)")
+    ap.add_argument("--ffn", type=int, default=None,
+                    help="--workload layer: width of the MLP (default 3.5 x hidden, rounded to a multiple of 64)")
     ap.add_argument("--seconds", type=float, default=0.0, help="0 = run forever (like the reference sample)")
     ap.add_argument("--iters", type=int, default=0)
     ap.add_argument("--touch", action="store_true")
@@ -709,7 +853,7 @@ def main(argv=None) -> int:
     res = run(a.total, a.allocated, kernel=a.kernel, size=a.size, seconds=a.seconds, iters=a.iters, touch=a.touch,
               quiet=a.json, probe_limit=a.probe_limit, dtype=a.dtype, workload=a.workload, batch=a.batch,
               weights_gib=a.weights_gib, context=a.context, heads=a.heads, kv_heads=a.kv_heads, kv_dtype=a.kv_dtype,
-              kv_gib=a.kv_gib, page=a.page)
+              kv_gib=a.kv_gib, page=a.page, ffn=a.ffn)
     print(json.dumps(res) if a.json else res, flush=True)
     return 0
 

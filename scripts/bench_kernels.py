@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the HIP kernels on one MI355X: bf16, fp8 and mxfp4 GEMM (ours vs torch/hipBLASLt), the decode
 GEMM (every configuration vs torch and a read-bandwidth yardstick), the decode attention over a paged KV cache (every
-configuration and split count vs torch SDPA and the same yardstick), RoPE + KV append (vs a read-and-rewrite
-yardstick), HBM fill, stamp/verify."""
+configuration and split count vs torch SDPA and the same yardstick), RoPE + KV append and the fused add + RMSNorm and
+SwiGLU (vs a read-and-rewrite yardstick), HBM fill, stamp/verify."""
 import json
 import os
 import statistics
@@ -564,6 +564,108 @@ def kv_append(shapes=KV_APPEND_SHAPES, heads=ATTN_HEADS, kinds=("bf16", "fp8"), 
     return out
 
 
+NORM_ACT_PREFILL = [("add_rmsnorm", 4096, 8192), ("add_rmsnorm", 16384, 8192), ("silu_mul", 4096, 28672)]
+NORM_ACT_DECODE = (1, 4, 16)  # rows of a decode step, at the same widths
+
+
+def norm_act(shapes=NORM_ACT_PREFILL, kinds=("bf16", "fp8"), ring_bytes=(512 << 20) + 1, reps=3, rounds=3,
+             decode=NORM_ACT_DECODE, decode_iters=200):
+    """Fused add + RMSNorm (X, R_in, R_out in place, Y) and SwiGLU, to bf16 and to e4m3 with a scale per row.
+    Prefill-sized: thousands of rows over a ring of operand sets of more than 512 MiB, twice the Infinity Cache; one
+    timing is ``reps`` passes over the ring between two events, reported as the median TB/s of ``rounds`` repeats (and
+    their spread) of the bytes read plus the bytes written.  ``memtest_rewrite_TBps`` is the yardstick as in
+    :func:`kv_append`: ``gsx_memtest_check`` with ``rewrite`` over half the pass's byte total, ONE call timed by the
+    host's clock, so it reads low by the fixed host cost of a call.  Decode-sized (M = 1, 4, 16): microseconds per call
+    over ``decode_iters`` back-to-back calls."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    widths = sorted({(op, n) for op, _, n in shapes})
+    for kind in kinds:
+        esz = 2 if kind == "bf16" else 1
+        for op, m, n in [*shapes, *((op, m, n) for op, n in widths for m in decode)]:
+            small = m <= max(decode)
+            if op == "add_rmsnorm":
+                moved = m * n * (2 + 2 + 2 + esz) + n * 2  # X, R_in, R_out, Y and W
+            else:
+                moved = m * n * (4 + esz)  # gate and up, Y
+            moved += m * 4 if esz == 1 else 0
+            slots = 2 if small else max(2, -(-ring_bytes // moved))
+            src = torch.randn(slots, m, 2 * n if op == "silu_mul" else n, device="cuda", dtype=torch.bfloat16)
+            res = torch.randn(slots, m, n, device="cuda", dtype=torch.bfloat16) if op == "add_rmsnorm" else None
+            w = torch.ones(n, device="cuda", dtype=torch.bfloat16)
+            y = torch.empty(slots, m, n * esz, device="cuda", dtype=torch.uint8)
+            sc = torch.empty(slots, m, device="cuda", dtype=torch.float32)
+            torch.cuda.synchronize()
+
+            def args(i):
+                scale = sc[i].data_ptr() if esz == 1 else 0
+                if op == "add_rmsnorm":
+                    return (s, kind, src[i].data_ptr(), n, res[i].data_ptr(), res[i].data_ptr(), n, w.data_ptr(),
+                            y[i].data_ptr(), n, scale, m, n, 1e-5)
+                return (s, kind, src[i].data_ptr(), 2 * n, y[i].data_ptr(), n, scale, m, n)
+
+            call, timer = ((hip.add_rmsnorm, hip.time_add_rmsnorm) if op == "add_rmsnorm"
+                           else (hip.silu_mul, hip.time_silu_mul))
+            row = {"op": op, "kind": kind, "m": m, "n": n, "slots": slots, "bytes_per_call": moved}
+            if small:
+                us = []
+                for r in range(rounds + 1):
+                    ms = timer(*args(r % slots), decode_iters)
+                    if r:
+                        us.append(ms * 1e3 / decode_iters)
+                row["gsx_us_per_call"] = round(statistics.median(us), 2)
+                row["gsx_spread"] = round((max(us) - min(us)) / statistics.median(us), 3)
+            else:
+                yard = hip.DeviceBuffer(0, (slots * moved // 2) & ~255)
+                hip.memtest_write(s, yard.addr(), yard.nbytes, 0, MEMTEST_RANDOM, 1)
+                s.sync()
+                flipped = [False]
+
+                def ours():
+                    for i in range(slots):
+                        call(*args(i))
+
+                def timed(fn):
+                    torch.cuda.synchronize()
+                    with torch.cuda.stream(ts):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(ts)
+                        for _ in range(reps):
+                            fn()
+                        e1.record(ts)
+                    e1.synchronize()
+                    return reps * slots * moved / (e0.elapsed_time(e1) * 1e-3) / 1e12
+
+                def yardstick():  # every call leaves the complement of what it found
+                    s.sync()
+                    t0 = time.perf_counter()
+                    rep = hip.memtest_check(s, yard.addr(), yard.nbytes, 0, MEMTEST_RANDOM, 1, flipped[0], True)
+                    dt = time.perf_counter() - t0
+                    flipped[0] = not flipped[0]
+                    assert rep.bad_dwords == 0
+                    return 2 * yard.nbytes / dt / 1e12
+
+                runs = {"gsx": [], "memtest_rewrite": []}
+                for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                    for name, fn in (("gsx", lambda: timed(ours)), ("memtest_rewrite", yardstick)):
+                        v = fn()
+                        if r:
+                            runs[name].append(v)
+                for name, v in runs.items():
+                    med = statistics.median(v)
+                    row[f"{name}_TBps"] = round(med, 3)
+                    row[f"{name}_spread"] = round((max(v) - min(v)) / med, 3)
+                row["gsx_over_memtest_rewrite"] = round(row["gsx_TBps"] / row["memtest_rewrite_TBps"], 3)
+                yard.free()
+            out.append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+            del src, res, y, sc
+            torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 def hbm(nbytes=16 << 30, reps=5):
     s = hip.Stream(0)
     buf = hip.DeviceBuffer(0, nbytes)
@@ -595,7 +697,7 @@ if __name__ == "__main__":
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
                 "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "attn_decode": attn_decode,
-                "kv_append": kv_append,
+                "kv_append": kv_append, "norm_act": norm_act,
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
                 "hbm": hbm}
