@@ -117,6 +117,9 @@ def lib():
         # stream, kind, QKV, qkv_stride, Q_out, K_cache, V_cache, block_table, seq_lens, lens_out, rope_cos, rope_sin;
         # rope_len, B, T, Hq, Hkv, D, page, num_pages, table_stride, max_seq_len; k_inv_scale, v_inv_scale
         _kv_append_sig = [vp, i32, vp, ctypes.c_int64] + [vp] * 8 + [i32] * 10 + [ctypes.c_float] * 2
+        # stream, kind, Q, K_cache, V_cache, block_table, seq_lens, O; B, T, Hq, Hkv, D, page, num_pages, table_stride,
+        # max_seq_len; scale, k_scale, v_scale
+        _prefill_sig = [vp, i32] + [vp] * 6 + [i32] * 9 + [ctypes.c_float] * 3
         # stream, out_kind, X, x_stride, R_in, R_out, r_stride, W, Y, y_stride, scale_out; M, H; eps
         _norm_sig = [vp, i32, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, i32, i32,
                      ctypes.c_float]
@@ -173,6 +176,11 @@ def lib():
             "gsx_event_time_decode_attn": ([*_attn_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_kv_append": (_kv_append_sig, i32),
             "gsx_event_time_kv_append": ([*_kv_append_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_prefill_attn": (_prefill_sig, i32),
+            "gsx_prefill_attn_launch_cfg": ([*_prefill_sig, i32], i32),
+            "gsx_prefill_attn_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_prefill_attn_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
+            "gsx_event_time_prefill_attn": ([*_prefill_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_add_rmsnorm": (_norm_sig, i32),
             "gsx_event_time_add_rmsnorm": ([*_norm_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_silu_mul": (_silu_sig, i32),
@@ -723,6 +731,65 @@ def time_kv_append(stream: Stream, kind: str, qkv: int, qkv_stride: int, q_out: 
                                                         b, t, hq, hkv, d, page, num_pages, table_stride, max_seq_len,
                                                         k_inv_scale, v_inv_scale), iters, ctypes.byref(ms)),
         "time_kv_append")
+    return ms.value
+
+
+def _prefill_args(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int, seq_lens: int,
+                  o: int, b: int, t: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int,
+                  max_seq_len: int, scale: float, k_scale: float, v_scale: float) -> tuple:
+    if kind not in ATTN_KV_KINDS:
+        raise ValueError(f"attention cache kind {kind!r}: one of {', '.join(ATTN_KV_KINDS)}")
+    return (stream.handle, ATTN_KV_KINDS[kind], *(ctypes.c_void_p(x) for x in (q, k_cache, v_cache, block_table,
+                                                                               seq_lens, o)),
+            b, t, hq, hkv, d, page, num_pages, table_stride, max_seq_len, scale, k_scale, v_scale)
+
+
+def prefill_attn(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int, seq_lens: int,
+                 o: int, b: int, t: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int,
+                 max_seq_len: int, scale: float, k_scale: float = 1.0, v_scale: float = 1.0):
+    """Causal grouped-query attention of a prefill chunk over the paged KV cache: ``o[b * t][hq][d]`` (bf16) from
+    ``q[b * t][hq][d]`` (bf16, the ``q_out`` of :func:`kv_append`) and the caches ``[num_pages][hkv][page][d]`` of
+    ``kind`` ``"bf16"`` or ``"fp8"``.  ``seq_lens[b]`` is the length BEFORE the chunk, the buffer :func:`kv_append`
+    took: row ``n`` is at position ``seq_lens[n // t] + n % t`` and attends to the tokens up to and including its
+    own.  All addresses are device addresses.  Not synchronised."""
+    _ck(lib().gsx_prefill_attn(*_prefill_args(stream, kind, q, k_cache, v_cache, block_table, seq_lens, o, b, t, hq,
+                                              hkv, d, page, num_pages, table_stride, max_seq_len, scale, k_scale,
+                                              v_scale)), "prefill_attn")
+
+
+def prefill_attn_cfg_name(cfg: int) -> str | None:
+    """The name of prefill attention configuration ``cfg``, or None outside the library's table."""
+    name = lib().gsx_prefill_attn_cfg_name(cfg)
+    return None if name is None else name.decode()
+
+
+def prefill_attn_cfg_shape(cfg: int) -> tuple[int, int, int]:
+    """``(q_rows, kv_tile, waves)`` of prefill attention configuration ``cfg`` (native/kernels/attn_prefill.hip):
+    query rows per workgroup, tokens per KV tile, waves per workgroup.  An unknown config raises HipError."""
+    v = [ctypes.c_int(0) for _ in range(3)]
+    if lib().gsx_prefill_attn_cfg_shape(cfg, *map(ctypes.byref, v)) != 0:
+        raise HipError(f"prefill attn cfg {cfg}: unknown config")
+    return tuple(x.value for x in v)
+
+
+def prefill_attn_launch_cfg(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int,
+                            seq_lens: int, o: int, b: int, t: int, hq: int, hkv: int, d: int, page: int,
+                            num_pages: int, table_stride: int, max_seq_len: int, scale: float, cfg: int,
+                            k_scale: float = 1.0, v_scale: float = 1.0):
+    """Launch one configuration of the prefill attention.  An unknown config raises HipError."""
+    _ck(lib().gsx_prefill_attn_launch_cfg(*_prefill_args(stream, kind, q, k_cache, v_cache, block_table, seq_lens, o,
+                                                         b, t, hq, hkv, d, page, num_pages, table_stride, max_seq_len,
+                                                         scale, k_scale, v_scale), cfg), f"prefill attn cfg {cfg}")
+
+
+def time_prefill_attn(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int, seq_lens: int,
+                      o: int, b: int, t: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int,
+                      max_seq_len: int, scale: float, iters: int, k_scale: float = 1.0, v_scale: float = 1.0) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_prefill_attn(*_prefill_args(stream, kind, q, k_cache, v_cache, block_table, seq_lens, o,
+                                                         b, t, hq, hkv, d, page, num_pages, table_stride, max_seq_len,
+                                                         scale, k_scale, v_scale), iters, ctypes.byref(ms)),
+        "time_prefill_attn")
     return ms.value
 
 

@@ -23,12 +23,19 @@ exact environment the device plugin's Allocate produces, in four scenarios:
 * ``attn-noisy`` / ``attn-noisy-partitioned``  pod 0 runs the attention workload
                     (``--batch`` sequences of ``--context`` tokens over a ring of paged KV
                     caches: a gather over pages, bound by HBM bandwidth too) next to 3 pods
-                    running large GEMMs.
+                    running large GEMMs;
+* ``prefill-noisy`` / ``prefill-noisy-partitioned``  pod 0 runs the decode ``layer`` workload
+                    (``--batch`` rows, bound by HBM bandwidth) next to ONE prefill pod
+                    (``--prefill-batch`` sequences of ``--chunk`` new tokens: compute-bound), the
+                    standard interference pair of an inference server.  Each pod also runs alone
+                    under the same mask; the summary has ``solo_tflops`` and
+                    ``ratio_to_solo`` per pod.
 
 ``--workload decode`` or ``--workload attn`` makes every pod of the other scenarios such a pod.  ``--workload server``
 (a whole decode layer per ring layer: projections, RoPE and KV append, attention) does so for ``solo``, ``solo64``,
 ``shared`` and ``partitioned``; it runs on the library's kernels only.  ``--workload layer`` (the same with a residual
-stream, two RMSNorms and the SwiGLU MLP of ``--ffn`` columns: a whole decoder layer) takes the same scenarios.
+stream, two RMSNorms and the SwiGLU MLP of ``--ffn`` columns: a whole decoder layer) takes the same scenarios, and so
+does ``--workload prefill`` (that layer on ``--batch`` sequences of ``--chunk`` new tokens each).
 Reported per scenario: per-pod TFLOP/s, aggregate, and fairness (min/max); for
 decode and attention pods also the TB/s of weight or KV bytes they streamed.
 Run: ``python -m gsxtools.isolation --seconds 8``.
@@ -67,13 +74,15 @@ def pod_envs(n_pods: int, cus_each: int, gpu_total_gib: int, pod_gib: int, with_
 
 def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str,
              dtype: str = "bf16", workload="gemm", batch: int = 8, attn_args: list[str] | None = None) -> list[dict]:
-    """``size`` and ``workload`` are one value for every pod or a list with one per pod; ``attn_args`` are the
-    command-line options an attention pod gets."""
+    """``size``, ``workload`` and ``batch`` are one value for every pod or a list with one per pod; ``attn_args`` are
+    the command-line options an attention pod gets (a list of lists: one per pod)."""
     start_at = time.time() + 20.0  # time for every process to import torch and warm up
     procs = []
     sizes = size if isinstance(size, list) else [size] * len(envs)
     workloads = workload if isinstance(workload, list) else [workload] * len(envs)
-    for e, sz, wl in zip(envs, sizes, workloads):
+    batches = batch if isinstance(batch, list) else [batch] * len(envs)
+    per_pod = attn_args if attn_args and isinstance(attn_args[0], list) else [attn_args] * len(envs)
+    for e, sz, wl, batch, attn_args in zip(envs, sizes, workloads, batches, per_pod):
         env = dict(os.environ)
         env.update({k: v for k, v in e.items() if k not in ("GSX_CU_MASK", "HSA_CU_MASK")})
         if mask_mode in ("stream", "both") and "GSX_CU_MASK" in e:
@@ -89,7 +98,7 @@ def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str
                "--size", str(sz), "--seconds", str(seconds), "--dtype", dtype, "--json"]
         if wl != "gemm":  # the default is left off the command line
             cmd += ["--workload", wl, "--batch", str(batch)]
-        if wl in ("attn", "server", "layer"):
+        if wl in ("attn", "server", "layer", "prefill"):
             cmd += attn_args or []
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                                       cwd=str(ROOT)))
@@ -115,8 +124,9 @@ def summarize(name: str, res: list[dict]) -> dict:
 
 SCENARIOS_DECODE_NOISY = ("decode-noisy", "decode-noisy-partitioned")
 SCENARIOS_ATTN_NOISY = ("attn-noisy", "attn-noisy-partitioned")
+SCENARIOS_PREFILL_NOISY = ("prefill-noisy", "prefill-noisy-partitioned")
 SCENARIOS = ("solo", "shared", "partitioned", "env", "env-gsx", "solo-small", "solo64", "noisy", "noisy-partitioned",
-             *SCENARIOS_DECODE_NOISY, *SCENARIOS_ATTN_NOISY)
+             *SCENARIOS_DECODE_NOISY, *SCENARIOS_ATTN_NOISY, *SCENARIOS_PREFILL_NOISY)
 
 
 def attn_cmdline(a: argparse.Namespace) -> list[str]:
@@ -142,6 +152,19 @@ def layer_cmdline(a: argparse.Namespace) -> list[str]:
     return server_cmdline(a) + (["--ffn", str(a.ffn)] if a.ffn is not None else [])
 
 
+def prefill_cmdline(a: argparse.Namespace) -> list[str]:
+    """The prefill pods' options: the layer pods', and the chunk."""
+    return layer_cmdline(a) + ["--chunk", str(a.chunk)]
+
+
+def with_solo(summary: dict, solo: list[dict]) -> dict:
+    """``summary`` of pods that ran together, with what each did alone and the ratio of the two."""
+    alone = [r["tflops"] for r in solo]
+    summary["solo_tflops"] = [round(x, 1) for x in alone]
+    summary["ratio_to_solo"] = [round(t / x, 3) if x else None for t, x in zip(summary["per_pod_tflops"], alone)]
+    return summary
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = pod_workload.BatchRangeParser()
     ap.add_argument("--pods", type=int, default=4)
@@ -153,11 +176,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"],
                     help="the pods' GEMM operand type (mxfp4: with --kernel gsx only)")
     ap.add_argument("--size", type=int, default=8192)
-    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server", "layer"],
+    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server", "layer", "prefill"],
                     help="what the pods run: the large GEMM, the decode workload (--batch rows against a ring of "
                          "--size x --size weights), the attention workload (--batch sequences of --context tokens), "
-                         "the server workload (a decode layer per ring layer; solo, solo64, shared, partitioned), or the "
-                         "layer workload (a whole decoder layer per ring layer; the same scenarios)")
+                         "the server workload (a decode layer per ring layer; solo, solo64, shared, partitioned), the "
+                         "layer workload (a whole decoder layer per ring layer; the same scenarios), or the prefill "
+                         "workload (that layer on --batch sequences of --chunk new tokens; the same scenarios)")
     ap.add_argument("--batch", type=int, default=8, metavar="N",
                     help="the decode pods' activation rows (1..16), or the attention pods' sequences (1..256, with "
                          "--workload attn)")
@@ -166,6 +190,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="--workload server and layer: size of the pods' weight ring (default: the workload's)")
     ap.add_argument("--ffn", type=int, default=None,
                     help="--workload layer: width of the pods' MLP (default: the workload's)")
+    ap.add_argument("--prefill-batch", type=int, default=1,
+                    help="prefill-noisy scenarios: the prefill pod's sequences (of --chunk new tokens each)")
     ap.add_argument("--small-size", type=int, default=2048)
     ap.add_argument("--scenarios",
                     default="solo,shared,partitioned,env,env-gsx,solo-small,solo64,noisy,noisy-partitioned")
@@ -176,8 +202,9 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     results = []
-    own_size = a.workload in ("decode", "attn", "server", "layer")  # pods whose work --size does not scale
-    pod_args = {"server": server_cmdline, "layer": layer_cmdline}.get(a.workload, attn_cmdline)(a)
+    own_size = a.workload in ("decode", "attn", "server", "layer", "prefill")  # pods whose work --size does not scale
+    pod_args = {"server": server_cmdline, "layer": layer_cmdline,
+                "prefill": prefill_cmdline}.get(a.workload, attn_cmdline)(a)
 
     def run(*args):  # every scenario's pods get the attention options: only attention, server and layer pods use them
         return run_pods(*args, attn_args=pod_args)
@@ -185,7 +212,7 @@ def main(argv=None) -> int:
     for sc in a.scenarios.split(","):
         if sc not in SCENARIOS:
             raise SystemExit(f"unknown scenario {sc}")
-        if a.workload in ("server", "layer") and sc not in SCENARIOS_SERVER:
+        if a.workload in ("server", "layer", "prefill") and sc not in SCENARIOS_SERVER:
             raise SystemExit(f"--workload {a.workload}: scenario {sc} is not one of {', '.join(SCENARIOS_SERVER)}")
         if sc == "solo":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, False)
@@ -220,6 +247,23 @@ def main(argv=None) -> int:
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, masked)
             res = run(envs, a.seconds, a.kernel, a.size, "stream" if masked else "none", a.dtype,
                       ["attn"] + ["gemm"] * (a.pods - 1), a.batch)
+        elif sc in SCENARIOS_PREFILL_NOISY:
+            masked = sc == "prefill-noisy-partitioned"
+            if why := pod_workload.prefill_refusal(a.prefill_batch, a.chunk, a.context):
+                raise SystemExit(f"{sc}: {why}")
+            if not 1 <= a.batch <= 16:
+                raise SystemExit(f"{sc}: --batch {a.batch}: the layer pod takes 1..16 rows")
+            envs = pod_envs(2, a.cus, a.gpu_gib, a.pod_gib, masked)
+            wls, batches = ["layer", "prefill"], [a.batch, a.prefill_batch]
+            args = [layer_cmdline(a), prefill_cmdline(a)]
+            mode = "stream" if masked else "none"
+            solo = [run_pods([envs[i]], a.seconds, a.kernel, a.size, mode, a.dtype, wls[i], batches[i],
+                             attn_args=args[i])[0] for i in range(2)]
+            res = run_pods(envs, a.seconds, a.kernel, a.size, mode, a.dtype, wls, batches, attn_args=args)
+            s = with_solo(summarize(sc, res), solo)
+            print(json.dumps(s), flush=True)
+            results.append(s)
+            continue
         elif sc == "env":
             envs = pod_envs(a.pods, a.cus, a.gpu_gib, a.pod_gib, True)
             res = run(envs, a.seconds, "torch" if a.kernel == "gsx" else a.kernel, a.size, "env", a.dtype,

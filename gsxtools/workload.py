@@ -32,6 +32,8 @@ server_layer_weight_bytes = _mod.server_layer_weight_bytes
 server_window = _mod.server_window
 default_ffn = _mod.default_ffn
 layer_weight_bytes = _mod.layer_weight_bytes
+prefill_refusal = _mod.prefill_refusal
+prefill_visible_pairs = _mod.prefill_visible_pairs
 BatchRangeParser = _mod._Parser
 
 if __name__ == "__main__":

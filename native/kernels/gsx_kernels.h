@@ -30,6 +30,9 @@
 //  * RoPE + KV append    — rotates Q and K and writes the new tokens' K and V into
 //                          their page slots, quantised for an e4m3 cache: what makes
 //                          the cache the attention reads (kv_append.hip);
+//  * prefill attention   — causal attention of a chunk of new tokens over the same paged
+//                          cache, the compute-bound half of an inference server
+//                          (attn_prefill.hip);
 //  * add + RMSNorm, SwiGLU — the residual stream, the normalisation and the MLP's activation of
 //                          a decoder layer, to bf16 or to e4m3 with a scale per row
 //                          (norm_act.hip);
@@ -313,6 +316,55 @@ int gsx_event_time_kv_append(void* stream, int kind, const void* QKV, int64_t qk
                              const float* rope_cos, const float* rope_sin, int rope_len, int B, int T, int Hq, int Hkv,
                              int D, int page, int num_pages, int table_stride, int max_seq_len, float k_inv_scale,
                              float v_inv_scale, int iters, float* ms);
+
+// Causal prefill attention over the paged KV cache (attn_prefill.hip): T new tokens per sequence attend over the cache
+// that gsx_kv_append(T) has just extended; kinds, cache layout, block_table and seq_lens as gsx_decode_attn takes them.
+//   Q[B * T][Hq][D], O[B * T][Hq][D]      bf16, D == 128; Q is exactly the Q_out of gsx_kv_append
+//   seq_lens[B]                           the lengths BEFORE the chunk: the buffer gsx_kv_append took, not its lens_out
+// base = clamp(seq_lens[b], 0, max_seq_len).  Row n = b * T + t is at pos = base + t and is LIVE when pos <
+// max_seq_len, the rule of gsx_kv_append.  A live row attends to tokens 0 .. pos of its sequence (causal, its own token
+// included); a row that is not live gives a row of zeros.  With T == 1 this is gsx_decode_attn on lengths base + 1.
+// Requirements: a known kind; D == 128; 1 <= Hq <= 4096, Hq % Hkv == 0 and Hq / Hkv <= 16; page % 16 == 0 and 16 <=
+// page <= 256; B, T >= 1, B * T below 2^31 and ceil(T / 256) * B * Hq below 2^31 (the grid); num_pages >= 1; 1 <=
+// max_seq_len <= table_stride * page; every pointer non-NULL, Q, the caches and O 16-B aligned, the int32 arrays 4-B
+// aligned; O does not overlap Q; scale, k_scale and v_scale finite and > 0, the latter two exactly 1.0f for a bf16
+// cache.  Everything is validated before the first device call; launches on `stream` and returns without synchronising.
+// Safety: a page index is clamped into [0, num_pages) by an unsigned min; block-table entries past the page of the
+// last live row of a block of 256 query rows are never read by that block; offsets into the caches are 64-bit.  No
+// content of block_table, seq_lens or the caches makes the kernel read outside the caches or write outside O.
+// Numerics, the contract of gsx_decode_attn per query row, over the tokens j <= pos:
+//   x[j] = (q . k_j) * (scale * k_scale * log2 e)        fp32; bf16 products accumulated in fp32 on
+//                                                        v_mfma_f32_32x32x16_bf16; e4m3 K and V are converted to
+//                                                        bf16 on the way into LDS, which is exact
+//   p = exp2(x - m)                                      fp32, m a running maximum (plain online softmax: the
+//                                                        accumulator is rescaled at every tile, nothing is deferred)
+//   l = sum of p                                         fp32, of the unrounded p
+//   P = bf16(p), round to nearest even                   the operand of the PV MFMA, accumulated in fp32
+//   O = bf16((acc / l) * v_scale)                        rounded once
+// One workgroup takes the sequence's KV tiles of 64 tokens front to back, from token 0: no split-KV, no workspace,
+// nothing passes between workgroups, and the result is deterministic.  A row's bytes depend only on its own query,
+// its pos and its sequence's cache: not on B, T, or which rows share the launch.  A token a row may not see has its x
+// replaced by -inf by a select, so it contributes nothing whatever its K holds; V of tokens past the last live row
+// of the row's block of 256 is replaced by zeros.  Between a row's pos and that last row (tokens the same launch's
+// later rows do see) V must be finite: 0 * NaN in the PV product would reach the row.
+int gsx_prefill_attn(void* stream, int kind, const void* Q, const void* K_cache, const void* V_cache,
+                     const void* block_table, const void* seq_lens, void* O, int B, int T, int Hq, int Hkv, int D,
+                     int page, int num_pages, int table_stride, int max_seq_len, float scale, float k_scale,
+                     float v_scale);
+// The prefill configurations, one table for both cache types: 0 "8w-q256-k64": waves per workgroup - query rows per
+// workgroup - tokens per KV tile.  _cfg_name returns NULL and _cfg_shape nonzero outside the table; _launch_cfg takes
+// what gsx_prefill_attn takes.
+const char* gsx_prefill_attn_cfg_name(int cfg);
+int gsx_prefill_attn_cfg_shape(int cfg, int* q_rows, int* kv_tile, int* waves);
+int gsx_prefill_attn_launch_cfg(void* stream, int kind, const void* Q, const void* K_cache, const void* V_cache,
+                                const void* block_table, const void* seq_lens, void* O, int B, int T, int Hq, int Hkv,
+                                int D, int page, int num_pages, int table_stride, int max_seq_len, float scale,
+                                float k_scale, float v_scale, int cfg);
+// elapsed milliseconds of `iters` back-to-back gsx_prefill_attn on `stream`, by hip events (for benches)
+int gsx_event_time_prefill_attn(void* stream, int kind, const void* Q, const void* K_cache, const void* V_cache,
+                                const void* block_table, const void* seq_lens, void* O, int B, int T, int Hq, int Hkv,
+                                int D, int page, int num_pages, int table_stride, int max_seq_len, float scale,
+                                float k_scale, float v_scale, int iters, float* ms);
 
 // Fused residual add + RMSNorm, and SwiGLU (norm_act.hip): what a decoder layer has between its projections.  Both
 // write bf16, or OCP e4m3 with one fp32 scale per row, which is exactly the A and scale_a that

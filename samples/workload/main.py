@@ -45,7 +45,15 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   projection to ``2 x --ffn`` columns, ``gsx_silu_mul`` and the down projection.  ``--ffn`` is the MLP's width (default
   3.5 x hidden, rounded to a multiple of 64).  Layer 0 of every step starts the residual stream afresh from a constant
   input, so an endless run stays finite.  The weights are bf16; it takes the server workload's other options and
-  reports the same fields and ``ffn``.
+  reports the same fields and ``ffn``;
+* ``--workload prefill`` is the same decoder layer in the prefill phase, the compute-bound half of a server:
+  ``--batch`` sequences (1..256) of ``--chunk`` new tokens each (default 2048; ``batch * chunk`` a multiple of 128),
+  which land at positions ``[--context - chunk, --context)``: ``--context`` is the length after the chunk, and has
+  to be given (the other workloads' default means something else).  The
+  projections run on the large bf16 GEMM, ``gsx_kv_append`` writes the whole chunk and ``gsx_prefill_attn``, causal
+  over the paged cache, attends over it.  The lengths are a constant device buffer, so an endless run rewrites the same
+  slots.  It reports ``tokens_per_s`` (prompt tokens), ``tflops`` (the projections, and the attention over visible
+  pairs only), ``tbps``, ``chunk`` and the layer workload's fields.
 """
 from __future__ import annotations
 
@@ -146,6 +154,25 @@ def layer_weight_bytes(heads: int, kv_heads: int, ffn: int) -> int:
     return server_layer_weight_bytes(heads, kv_heads) + 3 * ffn * heads * ATTN_D * 2
 
 
+def prefill_refusal(batch: int, chunk: int, context: int) -> str | None:
+    """Why ``--workload prefill`` cannot run these sizes, or None: known before anything touches the device."""
+    if chunk < 1:
+        return f"--chunk {chunk}: at least 1"
+    if not 1 <= batch <= 256:
+        return f"--batch {batch}: 1..256 sequences"
+    if (batch * chunk) % 128:
+        return f"--batch {batch} x --chunk {chunk} = {batch * chunk} rows: the GEMM takes a multiple of 128"
+    if chunk > context:
+        return f"--chunk {chunk} is more than --context {context}: the context is the length after the chunk"
+    return None
+
+
+def prefill_visible_pairs(batch: int, chunk: int, context: int) -> int:
+    """(query row, token) pairs a causal chunk at positions ``[context - chunk, context)`` sees, the row's own token
+    included: the sum over rows of ``pos + 1``."""
+    return batch * (chunk * (context - chunk) + chunk * (chunk + 1) // 2)
+
+
 def ring_layers(weights_bytes: int, one_matrix_bytes: int) -> int:
     """Matrices in the weight ring: enough to cover ``weights_bytes``, and never fewer than two, so that no launch
     finds its matrix where the last launch left it."""
@@ -181,6 +208,9 @@ class Kernels:
             L.gsx_kv_append.argtypes = ([vp, i32, vp, ctypes.c_int64] + [vp] * 8 + [i32] * 10
                                         + [ctypes.c_float] * 2)
             L.gsx_kv_append.restype = i32
+        if hasattr(L, "gsx_prefill_attn"):  # likewise: an image built before the prefill attention
+            L.gsx_prefill_attn.argtypes = [vp, i32] + [vp] * 6 + [i32] * 9 + [ctypes.c_float] * 3
+            L.gsx_prefill_attn.restype = i32
         if hasattr(L, "gsx_add_rmsnorm"):  # likewise: an image built before the norm and activation kernels
             i64 = ctypes.c_int64
             L.gsx_add_rmsnorm.argtypes = [vp, i32, vp, i64, vp, vp, i64, vp, vp, i64, vp, i32, i32, ctypes.c_float]
@@ -261,6 +291,17 @@ class Kernels:
                                       *(ctypes.c_void_p(x) for x in (q_out, kc, vc, table, lens, lens_out, cos, sin)),
                                       rope_len, b, t, hq, hkv, ATTN_D, page, num_pages, table_stride, max_seq_len,
                                       1.0, 1.0), "kv_append")
+
+    def prefill_attn(self, s, kv_dtype: str, q: int, kc: int, vc: int, table: int, lens: int, o: int, b: int, t: int,
+                     hq: int, hkv: int, page: int, num_pages: int, table_stride: int, max_seq_len: int, scale: float):
+        """Causal attention of ``t`` new tokens per sequence over the paged cache (unit cache scales); ``lens`` are the
+        lengths before the chunk."""
+        if not hasattr(self.L, "gsx_prefill_attn"):
+            raise RuntimeError(f"{self.path} has no gsx_prefill_attn: rebuild it")
+        self._ck(self.L.gsx_prefill_attn(s, ATTN_KV_KINDS[kv_dtype], *(ctypes.c_void_p(x) for x in
+                                                                       (q, kc, vc, table, lens, o)),
+                                         b, t, hq, hkv, ATTN_D, page, num_pages, table_stride, max_seq_len, scale, 1.0,
+                                         1.0), "prefill_attn")
 
     def add_rmsnorm(self, s, x: int, r_in: int, r_out: int, w: int, y: int, m: int, h: int, eps: float):
         """``hid = bf16(x + r_in)`` (``x`` with ``r_in`` 0) to ``r_out``, and its RMSNorm times ``w`` to ``y``: bf16,
@@ -571,11 +612,90 @@ def layer_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, hea
     return step, sync, finite
 
 
+def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, context: int, heads: int, kv_heads: int,
+                  page: int, ffn: int, w_layers: int, kv_layers: int):
+    """``(step, sync, finite)`` of the prefill workload: :func:`layer_steps` on ``batch * chunk`` rows.  The
+    projections go through the large GEMM, the append writes ``chunk`` tokens per sequence at positions
+    ``[context - chunk, context)`` and the causal attention reads the lengths the append read: one constant buffer."""
+    hidden, nqkv = heads * ATTN_D, (heads + 2 * kv_heads) * ATTN_D
+    rows = batch * chunk
+    per_seq, pages = kv_pages(batch, context, page)
+    layers = max(w_layers, kv_layers)
+    bf = torch.bfloat16
+    wqkv = torch.empty(w_layers, nqkv, hidden, device=dev, dtype=bf)
+    wo = torch.empty(w_layers, hidden, hidden, device=dev, dtype=bf)
+    wgu = torch.empty(w_layers, 2 * ffn, hidden, device=dev, dtype=bf)
+    wdown = torch.empty(w_layers, hidden, ffn, device=dev, dtype=bf)
+    for i in range(w_layers):  # one matrix at a time: nothing larger is ever held in fp32
+        for w, k in ((wqkv, hidden), (wo, hidden), (wgu, hidden), (wdown, ffn)):
+            w[i].copy_(torch.randn(w.shape[1], k, device=dev) / math.sqrt(k))
+    ln = torch.ones(w_layers, 2, hidden, device=dev, dtype=bf)
+    kdt = bf if kv_dtype == "bf16" else torch.float8_e4m3fn
+    kc = torch.empty(kv_layers, pages, kv_heads, page, ATTN_D, device=dev, dtype=kdt)
+    vc = torch.empty_like(kc)
+    for i in range(kv_layers):
+        for c in (kc, vc):
+            c[i].copy_(torch.randn(pages, kv_heads, page, ATTN_D, device=dev, dtype=bf).to(kdt))
+    table = torch.randperm(pages, device=dev).to(torch.int32).view(batch, per_seq).contiguous()
+    lens = torch.full((batch,), context - chunk, device=dev, dtype=torch.int32)  # before the chunk; never written
+    ang = (torch.arange(context, device=dev, dtype=torch.float64)[:, None]
+           * 10000.0 ** (-torch.arange(ATTN_D // 2, device=dev, dtype=torch.float64) / (ATTN_D // 2))[None])
+    cos, sin = ang.cos().float().contiguous(), ang.sin().float().contiguous()
+    x0 = torch.randn(rows, hidden, device=dev, dtype=bf)  # layer 0's input, constant
+    resid, xn, sub = (torch.zeros(rows, hidden, device=dev, dtype=bf) for _ in range(3))
+    qkv = torch.empty(rows, nqkv, device=dev, dtype=bf)
+    q = torch.empty(rows, heads, ATTN_D, device=dev, dtype=bf)
+    o = torch.empty_like(q)
+    gu = torch.empty(rows, 2 * ffn, device=dev, dtype=bf)
+    act = torch.empty(rows, ffn, device=dev, dtype=bf)
+    wqkv_b, wo_b, wgu_b, wdown_b = (w[0].numel() * 2 for w in (wqkv, wo, wgu, wdown))
+    cache_bytes = kc[0].numel() * kc.element_size()
+    scale = 1.0 / math.sqrt(ATTN_D)
+    torch.cuda.synchronize()
+
+    def step():
+        for i in range(layers):
+            wi = i % w_layers
+            kci, vci = kc.data_ptr() + (i % kv_layers) * cache_bytes, vc.data_ptr() + (i % kv_layers) * cache_bytes
+            ln1 = ln.data_ptr() + wi * 2 * hidden * 2
+            if i == 0:  # the residual stream starts afresh
+                kl.add_rmsnorm(gs, x0.data_ptr(), 0, resid.data_ptr(), ln1, xn.data_ptr(), rows, hidden, LAYER_EPS)
+            else:
+                kl.add_rmsnorm(gs, sub.data_ptr(), resid.data_ptr(), resid.data_ptr(), ln1, xn.data_ptr(), rows,
+                               hidden, LAYER_EPS)
+            kl.gemm(gs, xn.data_ptr(), wqkv.data_ptr() + wi * wqkv_b, qkv.data_ptr(), rows, nqkv, hidden)
+            kl.kv_append(gs, kv_dtype, qkv.data_ptr(), nqkv, q.data_ptr(), kci, vci, table.data_ptr(),
+                         lens.data_ptr(), 0, cos.data_ptr(), sin.data_ptr(), context, batch, chunk, heads, kv_heads,
+                         page, pages, per_seq, context)
+            kl.prefill_attn(gs, kv_dtype, q.data_ptr(), kci, vci, table.data_ptr(), lens.data_ptr(), o.data_ptr(),
+                            batch, chunk, heads, kv_heads, page, pages, per_seq, context, scale)
+            kl.gemm(gs, o.data_ptr(), wo.data_ptr() + wi * wo_b, sub.data_ptr(), rows, hidden, hidden)
+            kl.add_rmsnorm(gs, sub.data_ptr(), resid.data_ptr(), resid.data_ptr(), ln1 + hidden * 2, xn.data_ptr(),
+                           rows, hidden, LAYER_EPS)
+            kl.gemm(gs, xn.data_ptr(), wgu.data_ptr() + wi * wgu_b, gu.data_ptr(), rows, 2 * ffn, hidden)
+            kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), rows, ffn)
+            kl.gemm(gs, act.data_ptr(), wdown.data_ptr() + wi * wdown_b, sub.data_ptr(), rows, hidden, ffn)
+
+    def sync():
+        kl.sync(gs)
+
+    def finite():
+        kl.sync(gs)
+        return all(bool(torch.isfinite(t.float()).all()) for t in (resid, xn, sub, qkv, q, o, gu, act))
+
+    # the closures hold addresses, not tensors
+    step.keep = (wqkv, wo, wgu, wdown, ln, kc, vc, table, lens, cos, sin, x0, resid, xn, sub, qkv, q, o, gu, act)
+    return step, sync, finite
+
+
 def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 8192, seconds: float = 0.0,
         iters: int = 0, report_every: float = 5.0, touch: bool = False, quiet: bool = False,
         probe_limit: bool = False, dtype: str = "bf16", workload: str = "gemm", batch: int = 8,
         weights_gib: float | None = None, context: int = 8192, heads: int = 64, kv_heads: int = 8,
-        kv_dtype: str = "bf16", kv_gib: float | None = None, page: int = 16, ffn: int | None = None) -> dict:
+        kv_dtype: str = "bf16", kv_gib: float | None = None, page: int = 16, ffn: int | None = None,
+        chunk: int = 2048) -> dict:
+    if workload == "prefill" and (why := prefill_refusal(batch, chunk, context)):
+        raise SystemExit(f"--workload prefill: {why}")
     import torch
 
     lib_path = kernels_lib_path()
@@ -607,20 +727,21 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     m = n = k = size
     if dtype not in ("bf16", "fp8", "mxfp4"):
         raise SystemExit(f"--dtype {dtype}: bf16, fp8 or mxfp4")
-    if workload not in ("gemm", "decode", "attn", "server", "layer"):
-        raise SystemExit(f"--workload {workload}: gemm, decode, attn, server or layer")
+    if workload not in ("gemm", "decode", "attn", "server", "layer", "prefill"):
+        raise SystemExit(f"--workload {workload}: gemm, decode, attn, server, layer or prefill")
     decode = workload == "decode"
+    prefill = workload == "prefill"
     layer = workload == "layer"
     server = workload == "server" or layer  # the layer workload is the server workload with more in a layer
-    attn = workload == "attn" or server  # the server workload has the attention's shape options
-    if server:
+    attn = workload == "attn" or server or prefill  # these have the attention's shape options
+    if server or prefill:
         if kernel != "gsx":
             raise SystemExit(f"--workload {workload} runs on the library's kernels only (--kernel gsx)")
         if dtype != "bf16":
             raise SystemExit(f"--workload {workload}: the weights are bf16 only (the KV cache: --kv-dtype)")
-        if not 1 <= batch <= 16:
+        if server and not 1 <= batch <= 16:
             raise SystemExit(f"--batch {batch}: 1..16")
-    if layer:
+    if layer or prefill:
         ffn = default_ffn(heads * ATTN_D) if ffn is None else ffn
         if ffn < 64 or ffn % 64:
             raise SystemExit(f"--ffn {ffn}: a multiple of 64, at least 64")
@@ -658,7 +779,19 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         own = None if hip_stream is not None else gs
     layers = 1
     finite = None
-    if server:
+    if prefill:
+        weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
+        one_layer_bytes = layer_weight_bytes(heads, kv_heads, ffn)
+        w_layers = ring_layers(weights_bytes, one_layer_bytes)
+        kv_layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB),
+                                   kv_layer_bytes(kv_dtype, batch, context, kv_heads))
+        layers = max(w_layers, kv_layers)
+        step, sync, finite = prefill_steps(torch, kl, gs, dev, kv_dtype, batch, chunk, context, heads, kv_heads, page,
+                                           ffn, w_layers, kv_layers)
+        # the projections (2 flops per weight and row: a weight is 2 bytes), and QK^T and PV over the visible pairs
+        flops_attn = layers * (batch * chunk * one_layer_bytes
+                               + 4.0 * ATTN_D * heads * prefill_visible_pairs(batch, chunk, context))
+    elif server:
         weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
         one_layer_bytes = (layer_weight_bytes(heads, kv_heads, ffn) if layer
                            else server_layer_weight_bytes(heads, kv_heads))
@@ -756,7 +889,13 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     if decode:
         out.update({"workload": workload, "batch": m, "layers": layers,
                     "tbps": done * layers * matrix_bytes(dtype, n, k) / el / 1e12})
-    if server:
+    if prefill:
+        step_bytes = layers * (one_layer_bytes + kv_layer_bytes(kv_dtype, batch, context, kv_heads))
+        out.update({"workload": workload, "batch": batch, "chunk": chunk, "layers": layers, "weight_layers": w_layers,
+                    "kv_layers": kv_layers, "context": context, "heads": heads, "kv_heads": kv_heads,
+                    "kv_dtype": kv_dtype, "page": page, "ffn": ffn, "tbps": done * step_bytes / el / 1e12,
+                    "tokens_per_s": done * batch * chunk / el, "activations_finite": finite()})
+    elif server:
         step_bytes = layers * (one_layer_bytes + kv_layer_bytes(kv_dtype, batch, context, kv_heads))
         out.update({"workload": workload, "batch": batch, "layers": layers, "weight_layers": w_layers,
                     "kv_layers": kv_layers, "context": context, "heads": heads, "kv_heads": kv_heads,
@@ -786,15 +925,26 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
 
 
 class _Parser(argparse.ArgumentParser):
-    """``--batch`` has a range per workload: 1..16 rows (gemm ignores it, decode uses it), 1..256 sequences for attn,
-    also where only an ``attn-*`` scenario of the isolation harness (its ``--scenarios``) runs an attention pod."""
+    """``--batch`` has a range per workload: 1..16 rows (gemm ignores it, decode uses it), 1..256 sequences for attn
+    and prefill, also where only an ``attn-*`` scenario of the isolation harness (its ``--scenarios``) runs an
+    attention pod.  The sizes ``--workload prefill`` cannot run are refused here too, before anything loads torch."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
         scenarios = getattr(ns, "scenarios", "").split(",")
-        top = 256 if ns.workload == "attn" or any(sc.startswith("attn-") for sc in scenarios) else 16
+        wide = ns.workload in ("attn", "prefill") or any(sc.startswith("attn-") for sc in scenarios)
+        top = 256 if wide else 16
         if not 1 <= ns.batch <= top:
             self.error(f"argument --batch: {ns.batch} is not in 1..{top} (--workload {ns.workload})")
+        if ns.workload == "prefill":
+            # --context means something else here, the length AFTER the chunk, and the chunk's place follows from it:
+            # the other workloads' default is not taken over silently
+            given = sys.argv[1:] if args is None else args
+            if not any(len(a.split("=")[0]) >= 5 and "--context".startswith(a.split("=")[0]) for a in given):
+                self.error("--workload prefill: give --context, the length after the chunk (the chunk lands at "
+                           "[context - chunk, context))")
+            if why := prefill_refusal(ns.batch, ns.chunk, ns.context):
+                self.error(f"--workload prefill: {why}")
         return ns
 
 
@@ -810,6 +960,9 @@ def add_attn_arguments(ap: argparse.ArgumentParser) -> None:
                          "share if that is smaller; never fewer than two layers)")
     ap.add_argument("--page", type=int, default=16,
                     help="--workload attn: tokens of a KV page (a multiple of 16 in 16..256)")
+    ap.add_argument("--chunk", type=int, default=2048,
+                    help="--workload prefill: new tokens per sequence, at most --context (which this workload wants "
+                         "given: the length after the chunk); batch x chunk a multiple of 128")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -824,22 +977,24 @@ def build_parser() -> argparse.ArgumentParser:
                     help="operand type of the GEMM: bf16, fp8 (OCP e4m3) or mxfp4 (e2m1 with e8m0 block scales, "
                          "quantised from bf16 by the library; --kernel gsx only); the output stays bf16")
     ap.add_argument("--size", type=int, default=8192)
-    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server", "layer"],
+    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server", "layer", "prefill"],
                     help="gemm: one large square GEMM per step (compute-bound); decode: --batch activation rows "
                          "against a ring of --size x --size weight matrices, one launch each (HBM-bandwidth-bound); "
                          "attn: one decode step of attention per layer over a ring of paged KV caches; server: a "
                          "whole decode layer per ring layer (QKV projection, RoPE and KV append, attention, output "
                          "projection) over caches that grow; layer: a whole decoder layer per ring layer (the server "
-                         "workload's with a residual stream, two RMSNorms and the SwiGLU MLP)")
+                         "workload's with a residual stream, two RMSNorms and the SwiGLU MLP); prefill: the same layer on "
+                         "--batch sequences of --chunk new tokens each, causal attention over the paged cache "
+                         "(compute-bound)")
     ap.add_argument("--batch", type=int, default=8, metavar="N",
-                    help="--workload decode, server and layer: the activation rows (M), 1..16; --workload attn: the "
-                         "sequences, 1..256")
+                    help="--workload decode, server and layer: the activation rows (M), 1..16; --workload attn and "
+                         "prefill: the sequences, 1..256")
     add_attn_arguments(ap)
     ap.add_argument("--weights-gib", type=float, default=None,
-                    help="--workload decode, server and layer: size of the weight ring (default 4, or a quarter of the "
+                    help="--workload decode, server, layer and prefill: size of the weight ring (default 4, or a quarter of the "
                          "share if that is smaller; never fewer than two matrices or layers)")
     ap.add_argument("--ffn", type=int, default=None,
-                    help="--workload layer: width of the MLP (default 3.5 x hidden, rounded to a multiple of 64)")
+                    help="--workload layer and prefill: width of the MLP (default 3.5 x hidden, rounded to a multiple of 64)")
     ap.add_argument("--seconds", type=float, default=0.0, help="0 = run forever (like the reference sample)")
     ap.add_argument("--iters", type=int, default=0)
     ap.add_argument("--touch", action="store_true")
@@ -853,7 +1008,7 @@ def main(argv=None) -> int:
     res = run(a.total, a.allocated, kernel=a.kernel, size=a.size, seconds=a.seconds, iters=a.iters, touch=a.touch,
               quiet=a.json, probe_limit=a.probe_limit, dtype=a.dtype, workload=a.workload, batch=a.batch,
               weights_gib=a.weights_gib, context=a.context, heads=a.heads, kv_heads=a.kv_heads, kv_dtype=a.kv_dtype,
-              kv_gib=a.kv_gib, page=a.page, ffn=a.ffn)
+              kv_gib=a.kv_gib, page=a.page, ffn=a.ffn, chunk=a.chunk)
     print(json.dumps(res) if a.json else res, flush=True)
     return 0
 

@@ -2,7 +2,8 @@
 """Micro-benchmarks of the HIP kernels on one MI355X: bf16, fp8 and mxfp4 GEMM (ours vs torch/hipBLASLt), the decode
 GEMM (every configuration vs torch and a read-bandwidth yardstick), the decode attention over a paged KV cache (every
 configuration and split count vs torch SDPA and the same yardstick), RoPE + KV append and the fused add + RMSNorm and
-SwiGLU (vs a read-and-rewrite yardstick), HBM fill, stamp/verify."""
+SwiGLU (vs a read-and-rewrite yardstick), the causal prefill attention over the paged cache (vs torch SDPA on a
+contiguous copy), HBM fill, stamp/verify."""
 import json
 import os
 import statistics
@@ -666,6 +667,81 @@ def norm_act(shapes=NORM_ACT_PREFILL, kinds=("bf16", "fp8"), ring_bytes=(512 << 
     return out
 
 
+ATTN_PREFILL_SHAPES = [(16, 2048, 0), (4, 8192, 0), (8, 2048, 6144)]  # (sequences, new tokens each, tokens before them)
+
+
+def attn_prefill(shapes=ATTN_PREFILL_SHAPES, heads=((64, 8),), kinds=("bf16", "fp8"), iters=5, rounds=3, page=16):
+    """The causal prefill attention: ``b`` sequences of ``t`` new tokens behind ``base`` tokens, random normal Q, K and
+    V, pages of 16 tokens handed out through a random permutation.  TFLOP/s over visible pairs only
+    (``4 * D * Hq * sum of (pos + 1)``), the median of ``rounds`` timings of ``iters`` back-to-back calls (and their
+    spread).  The yardstick, for the bf16 cache and ``base == 0``: ``scaled_dot_product_attention(is_causal=True,
+    enable_gqa=True)`` on a contiguous bf16 copy of the same data, in the same run, counted with the same FLOPs."""
+    out = []
+    s = hip.Stream(0)
+    d = 128
+    sdpa = torch.nn.functional.scaled_dot_product_attention
+    for kind in kinds:
+        kdt = torch.bfloat16 if kind == "bf16" else torch.float8_e4m3fn
+        for hq, hkv in heads:
+            for b, t, base in shapes:
+                n = base + t
+                per_seq = -(-n // page)
+                pages = b * per_seq
+                flops = 4.0 * d * hq * b * (t * base + t * (t + 1) // 2)
+                k = torch.randn(b, hkv, per_seq * page, d, device="cuda", dtype=torch.bfloat16)
+                v = torch.randn(b, hkv, per_seq * page, d, device="cuda", dtype=torch.bfloat16)
+                q = torch.randn(b * t, hq, d, device="cuda", dtype=torch.bfloat16)
+                o = torch.empty_like(q)
+                table = torch.randperm(pages, device="cuda").to(torch.int32).view(b, per_seq).contiguous()
+                kc = torch.empty(pages, hkv, page, d, device="cuda", dtype=kdt)
+                vc = torch.empty_like(kc)
+                for src, dst in ((k, kc), (v, vc)):  # token j of sequence i lies at page table[i][j / page]
+                    paged = src.view(b, hkv, per_seq, page, d).permute(0, 2, 1, 3, 4).reshape(pages, hkv, page, d)
+                    dst[table.view(-1).long()] = paged.to(kdt)
+                lens = torch.full((b,), base, device="cuda", dtype=torch.int32)
+                torch.cuda.synchronize()
+                args = (s, kind, q.data_ptr(), kc.data_ptr(), vc.data_ptr(), table.data_ptr(), lens.data_ptr(),
+                        o.data_ptr(), b, t, hq, hkv, d, page, pages, per_seq, n, d ** -0.5)
+                row = {"kind": kind, "b": b, "t": t, "base": base, "heads": hq, "kv_heads": hkv, "page": page,
+                       "flops_per_call": flops}
+                runs = {"gsx": []}
+                for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                    ms = hip.time_prefill_attn(*args, iters)
+                    if r:
+                        runs["gsx"].append(iters * flops / (ms * 1e-3) / 1e12)
+                if kind == "bf16" and base == 0:
+                    q4 = q.view(b, t, hq, d).transpose(1, 2)  # [B][Hq][T][D], a view
+                    kk, vv = k[:, :, :n], v[:, :, :n]
+                    ref = sdpa(q4, kk, vv, is_causal=True, enable_gqa=True, scale=d ** -0.5)
+                    s.sync()
+                    row["max_abs_diff_vs_sdpa"] = float((ref.transpose(1, 2).reshape(b * t, hq, d).float()
+                                                         - o.float()).abs().max())
+                    runs["sdpa"] = []
+                    for r in range(rounds + 1):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        torch.cuda.synchronize()
+                        e0.record()
+                        for _ in range(iters):
+                            sdpa(q4, kk, vv, is_causal=True, enable_gqa=True, scale=d ** -0.5)
+                        e1.record()
+                        e1.synchronize()
+                        if r:
+                            runs["sdpa"].append(iters * flops / (e0.elapsed_time(e1) * 1e-3) / 1e12)
+                    del ref
+                for name, vals in runs.items():
+                    med = statistics.median(vals)
+                    row[f"{name}_TFLOPs"] = round(med, 1)
+                    row[f"{name}_spread"] = round((max(vals) - min(vals)) / med, 3)
+                if "sdpa" in runs:
+                    row["gsx_over_sdpa"] = round(row["gsx_TFLOPs"] / row["sdpa_TFLOPs"], 3)
+                out.append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                del k, v, q, o, kc, vc, table, lens
+                torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 def hbm(nbytes=16 << 30, reps=5):
     s = hip.Stream(0)
     buf = hip.DeviceBuffer(0, nbytes)
@@ -697,7 +773,7 @@ if __name__ == "__main__":
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
                 "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "attn_decode": attn_decode,
-                "kv_append": kv_append, "norm_act": norm_act,
+                "kv_append": kv_append, "norm_act": norm_act, "attn_prefill": attn_prefill,
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
                 "hbm": hbm}
