@@ -125,6 +125,10 @@ def lib():
                      ctypes.c_float]
         # stream, out_kind, GU, gu_stride, Y, y_stride, scale_out; M, I
         _silu_sig = [vp, i32, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, i32, i32]
+        # stream, logits, logits_stride, temperature, top_k, top_p, seeds, counter, tokens_out; M, V
+        _sample_sig = [vp, vp, ctypes.c_int64, vp, vp, vp, vp, u64, vp, i32, i32]
+        # stream, table, table_stride, tokens, out, out_stride; M, H, V
+        _embed_sig = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i32, i32, i32]
         sig = {
             "gsx_last_error": ([], ctypes.c_char_p),
             "gsx_device_count": ([ctypes.POINTER(i32)], i32),
@@ -185,6 +189,10 @@ def lib():
             "gsx_event_time_add_rmsnorm": ([*_norm_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_silu_mul": (_silu_sig, i32),
             "gsx_event_time_silu_mul": ([*_silu_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_sample": (_sample_sig, i32),
+            "gsx_event_time_sample": ([*_sample_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_embed_gather": (_embed_sig, i32),
+            "gsx_event_time_embed_gather": ([*_embed_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
             "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
                                   i32),
@@ -850,4 +858,54 @@ def time_silu_mul(stream: Stream, out_kind: str, gu: int, gu_stride: int, y: int
     ms = ctypes.c_float(0)
     _ck(lib().gsx_event_time_silu_mul(*_silu_mul_args(stream, out_kind, gu, gu_stride, y, y_stride, scale_out, m, i),
                                       iters, ctypes.byref(ms)), "time_silu_mul")
+    return ms.value
+
+
+def _sample_args(stream: Stream, logits: int, logits_stride: int, temperature: int, top_k: int, top_p: int,
+                 seeds: int, counter: int, tokens_out: int, m: int, v: int) -> tuple:
+    return (stream.handle, ctypes.c_void_p(logits), logits_stride, ctypes.c_void_p(temperature),
+            ctypes.c_void_p(top_k), ctypes.c_void_p(top_p), ctypes.c_void_p(seeds), counter & 0xFFFFFFFFFFFFFFFF,
+            ctypes.c_void_p(tokens_out), m, v)
+
+
+def sample(stream: Stream, logits: int, logits_stride: int, temperature: int, top_k: int, top_p: int, seeds: int,
+           counter: int, tokens_out: int, m: int, v: int):
+    """One token id (int32, ``tokens_out[m]``) from each of ``m`` rows of ``v`` bf16 logits, what ``decode_gemm_nt``
+    writes as an LM head; a ``logits_stride`` of 0 makes every row read the same logits.  ``temperature`` (fp32),
+    ``top_k`` (int32), ``top_p`` (fp32) and ``seeds`` (uint64) are per-row arrays in device memory; ``temperature`` 0
+    (NULL) makes every row greedy, ``top_k`` 0 and ``top_p`` 0 mean no limit.  A row whose temperature is NaN or <= 0
+    is greedy: the lowest index of the largest logit.  ``counter`` is the step number, a host value.  The result is
+    exact (tests/sample_cases.py is its twin).  All addresses are device addresses; 0 means NULL.  Not synchronised."""
+    _ck(lib().gsx_sample(*_sample_args(stream, logits, logits_stride, temperature, top_k, top_p, seeds, counter,
+                                       tokens_out, m, v)), "sample")
+
+
+def time_sample(stream: Stream, logits: int, logits_stride: int, temperature: int, top_k: int, top_p: int, seeds: int,
+                counter: int, tokens_out: int, m: int, v: int, iters: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_sample(*_sample_args(stream, logits, logits_stride, temperature, top_k, top_p, seeds,
+                                                  counter, tokens_out, m, v), iters, ctypes.byref(ms)), "time_sample")
+    return ms.value
+
+
+def _embed_gather_args(stream: Stream, table: int, table_stride: int, tokens: int, out: int, out_stride: int, m: int,
+                       h: int, v: int) -> tuple:
+    return (stream.handle, ctypes.c_void_p(table), table_stride, ctypes.c_void_p(tokens), ctypes.c_void_p(out),
+            out_stride, m, h, v)
+
+
+def embed_gather(stream: Stream, table: int, table_stride: int, tokens: int, out: int, out_stride: int, m: int, h: int,
+                 v: int):
+    """``out[r][0..h)`` is a raw 16-bit copy of ``table[tokens[r]][0..h)`` for ``m`` int32 token ids in device memory; a
+    token outside ``[0, v)`` gives a row of zeros.  Strides are in elements.  All addresses are device addresses.  Not
+    synchronised."""
+    _ck(lib().gsx_embed_gather(*_embed_gather_args(stream, table, table_stride, tokens, out, out_stride, m, h, v)),
+        "embed_gather")
+
+
+def time_embed_gather(stream: Stream, table: int, table_stride: int, tokens: int, out: int, out_stride: int, m: int,
+                      h: int, v: int, iters: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_embed_gather(*_embed_gather_args(stream, table, table_stride, tokens, out, out_stride, m,
+                                                              h, v), iters, ctypes.byref(ms)), "time_embed_gather")
     return ms.value

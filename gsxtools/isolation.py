@@ -98,7 +98,7 @@ def run_pods(envs: list[dict], seconds: float, kernel: str, size, mask_mode: str
                "--size", str(sz), "--seconds", str(seconds), "--dtype", dtype, "--json"]
         if wl != "gemm":  # the default is left off the command line
             cmd += ["--workload", wl, "--batch", str(batch)]
-        if wl in ("attn", "server", "layer", "prefill"):
+        if wl in ("attn", "server", "layer", "prefill", "generate"):
             cmd += attn_args or []
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                                       cwd=str(ROOT)))
@@ -152,6 +152,12 @@ def layer_cmdline(a: argparse.Namespace) -> list[str]:
     return server_cmdline(a) + (["--ffn", str(a.ffn)] if a.ffn is not None else [])
 
 
+def generate_cmdline(a: argparse.Namespace) -> list[str]:
+    """The generate pods' options: the layer pods', the vocabulary and the sampling parameters."""
+    return layer_cmdline(a) + ["--vocab", str(a.vocab), "--temperature", str(a.temperature), "--top-k", str(a.top_k),
+                               "--top-p", str(a.top_p), "--seed", str(a.seed)]
+
+
 def prefill_cmdline(a: argparse.Namespace) -> list[str]:
     """The prefill pods' options: the layer pods', and the chunk."""
     return layer_cmdline(a) + ["--chunk", str(a.chunk)]
@@ -176,16 +182,20 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"],
                     help="the pods' GEMM operand type (mxfp4: with --kernel gsx only)")
     ap.add_argument("--size", type=int, default=8192)
-    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server", "layer", "prefill"],
+    ap.add_argument("--workload", default="gemm",
+                    choices=["gemm", "decode", "attn", "server", "layer", "prefill", "generate"],
                     help="what the pods run: the large GEMM, the decode workload (--batch rows against a ring of "
                          "--size x --size weights), the attention workload (--batch sequences of --context tokens), "
                          "the server workload (a decode layer per ring layer; solo, solo64, shared, partitioned), the "
                          "layer workload (a whole decoder layer per ring layer; the same scenarios), or the prefill "
-                         "workload (that layer on --batch sequences of --chunk new tokens; the same scenarios)")
+                         "workload (that layer on --batch sequences of --chunk new tokens; the same scenarios), or the generate "
+                         "workload (the layer workload with the embedding lookup, the LM head and the sampler: the "
+                         "latency-sensitive decode pod; the same scenarios)")
     ap.add_argument("--batch", type=int, default=8, metavar="N",
                     help="the decode pods' activation rows (1..16), or the attention pods' sequences (1..256, with "
                          "--workload attn)")
     pod_workload.add_attn_arguments(ap)
+    pod_workload.add_generate_arguments(ap)
     ap.add_argument("--weights-gib", type=float, default=None,
                     help="--workload server and layer: size of the pods' weight ring (default: the workload's)")
     ap.add_argument("--ffn", type=int, default=None,
@@ -202,9 +212,9 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     results = []
-    own_size = a.workload in ("decode", "attn", "server", "layer", "prefill")  # pods whose work --size does not scale
-    pod_args = {"server": server_cmdline, "layer": layer_cmdline,
-                "prefill": prefill_cmdline}.get(a.workload, attn_cmdline)(a)
+    own_size = a.workload in ("decode", "attn", "server", "layer", "prefill", "generate")  # pods whose work --size does not scale
+    pod_args = {"server": server_cmdline, "layer": layer_cmdline, "prefill": prefill_cmdline,
+                "generate": generate_cmdline}.get(a.workload, attn_cmdline)(a)
 
     def run(*args):  # every scenario's pods get the attention options: only attention, server and layer pods use them
         return run_pods(*args, attn_args=pod_args)
@@ -212,7 +222,7 @@ def main(argv=None) -> int:
     for sc in a.scenarios.split(","):
         if sc not in SCENARIOS:
             raise SystemExit(f"unknown scenario {sc}")
-        if a.workload in ("server", "layer", "prefill") and sc not in SCENARIOS_SERVER:
+        if a.workload in ("server", "layer", "prefill", "generate") and sc not in SCENARIOS_SERVER:
             raise SystemExit(f"--workload {a.workload}: scenario {sc} is not one of {', '.join(SCENARIOS_SERVER)}")
         if sc == "solo":
             envs = pod_envs(1, a.cus, a.gpu_gib, a.pod_gib, False)

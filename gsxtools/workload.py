@@ -34,6 +34,9 @@ default_ffn = _mod.default_ffn
 layer_weight_bytes = _mod.layer_weight_bytes
 prefill_refusal = _mod.prefill_refusal
 prefill_visible_pairs = _mod.prefill_visible_pairs
+add_generate_arguments = _mod.add_generate_arguments
+generate_refusal = _mod.generate_refusal
+generate_step_bytes = _mod.generate_step_bytes
 BatchRangeParser = _mod._Parser
 
 if __name__ == "__main__":

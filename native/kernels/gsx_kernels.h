@@ -420,6 +420,56 @@ int gsx_event_time_add_rmsnorm(void* stream, int out_kind, const void* X, int64_
 int gsx_event_time_silu_mul(void* stream, int out_kind, const void* GU, int64_t gu_stride, void* Y, int64_t y_stride,
                             float* scale_out, int M, int I, int iters, float* ms);
 
+// Token sampler and embedding gather (sample.hip): what closes a decode step.  The LM head is gsx_decode_gemm_nt with
+// N = vocabulary; gsx_sample turns its bf16 logits into token ids and gsx_embed_gather turns token ids into the next
+// step's input rows, both through device memory, so generation needs no host synchronisation.
+// gsx_sample: logits[M][logits_stride] bf16; a stride of 0 makes every row read the same logits.  temperature[M]
+// (fp32), top_k[M] (int32), top_p[M] (fp32) and seeds[M] (uint64) are per-row arrays in device memory;
+// temperature == NULL makes every row greedy, top_k == NULL and top_p == NULL mean no limit, seeds may be NULL only
+// when temperature is.  counter is the step number.  tokens_out[M] int32.  The result is exact: a NumPy twin
+// (tests/sample_cases.py) reproduces every token.  No parameter value and no logit content makes the kernel write
+// outside tokens_out[m] or write a value outside [0, V).  Per row:
+//   key      a 16-bit integer that orders bf16 codes; -0 is +0; every NaN has one key, below -inf.  `first` is the
+//            lowest index that holds the largest key.
+//   greedy   the token is `first` when temperature[m] is NaN or <= 0, or the logit at `first` is not finite; top_k,
+//            top_p and seeds are not read for such a row.
+//   c        otherwise T = clamp(temperature, 2^-16, 2^16) and c = fl(fl32(log2 e) / T), one correctly rounded
+//            fp32 division.
+//   S        k = top_k (k <= 0 or k >= V: V); the k tokens of the largest keys, ties at the k-th key to the lowest
+//            indices.
+//   w        an integer.  d = fl(l - l_first), x = fl(d c); w = 0 when x < -32 and for a -inf or NaN logit.
+//            Otherwise n = floor(x), f = fl(x - n), g = ((((c5 f + c4) f + c3) f + c2) f + c1) f + 1 with every
+//            multiply and add rounded to fp32 on its own (no FMA), and w = trunc(g 2^(32 + n)) as a uint64.  `first`
+//            has w = 2^32.  c1 = 0x1.62e4bcp-1, c2 = 0x1.ebdb30p-3, c3 = 0x1.c91e04p-5, c4 = 0x1.277576p-7,
+//            c5 = 0x1.e97886p-10: g is within 2^-20 of 2^f on [0, 1).
+//   N        p = top_p (NaN or p >= 1: no cut; p < 0: 0) and Z = sum of w over S.  S is walked by descending key,
+//            every group of equal keys whole (of the group that top-k cuts, its members in S), up to and including
+//            the first group at which (double)mass >= (double)p * (double)Z.  N holds `first`.
+//   draw     a = mix64(seeds[m] + kGolden), r = mix64(a + (counter + 1) kGolden), wrapping (mix64.h);
+//            target = the high 64 bits of r * Z_N, Z_N the sum of w over N.  The token is the lowest index of N whose
+//            inclusive prefix sum of w, over N in index order, exceeds target.  A token of weight 0 is never drawn.
+// Every sum is a sum of integers, so the result does not depend on the order of addition, on M, on a row's index or
+// on where workgroups run; a workgroup owns a row and nothing passes between workgroups.
+// gsx_embed_gather: out[m][0..H) is a raw 16-bit copy of table[tokens[m]][0..H); a token outside [0, V) gives a row
+// of zeros (dropped, not clamped).  Nothing is written past element H of a row.
+// Requirements: M >= 1.  gsx_sample: 8 <= V <= 262144 and V % 8 == 0; logits_stride 0, or >= V and a multiple of 8;
+// logits and tokens_out non-NULL; logits 16-B aligned; temperature, top_k, top_p and tokens_out 4-B aligned, seeds
+// 8-B aligned; tokens_out overlaps nothing.  gsx_embed_gather: V >= 1; H >= 8 and H % 8 == 0; each stride >= H and a
+// multiple of 8; table, tokens and out non-NULL; table and out 16-B aligned, tokens 4-B aligned; out overlaps
+// nothing.  Row offsets are 64-bit: the table may exceed 4 GiB.  Everything is validated before the first device
+// call; launches on `stream` and returns without synchronising.
+int gsx_sample(void* stream, const void* logits, int64_t logits_stride, const float* temperature,
+               const int32_t* top_k, const float* top_p, const uint64_t* seeds, uint64_t counter,
+               int32_t* tokens_out, int M, int V);
+int gsx_embed_gather(void* stream, const void* table, int64_t table_stride, const int32_t* tokens, void* out,
+                     int64_t out_stride, int M, int H, int V);
+// elapsed milliseconds of `iters` back-to-back calls on `stream`, by hip events (for benches)
+int gsx_event_time_sample(void* stream, const void* logits, int64_t logits_stride, const float* temperature,
+                          const int32_t* top_k, const float* top_p, const uint64_t* seeds, uint64_t counter,
+                          int32_t* tokens_out, int M, int V, int iters, float* ms);
+int gsx_event_time_embed_gather(void* stream, const void* table, int64_t table_stride, const int32_t* tokens,
+                                void* out, int64_t out_stride, int M, int H, int V, int iters, float* ms);
+
 // HBM pre-flight memory test (memtest.hip).  The expected content of 16-byte word W = origin/16 + word index is
 // generated from (pattern, seed, invert, W) and never stored; `origin` is the byte offset of `base` in the whole
 // tested range, so a range tested chunk by chunk keeps globally unique content.

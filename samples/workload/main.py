@@ -46,6 +46,14 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   3.5 x hidden, rounded to a multiple of 64).  Layer 0 of every step starts the residual stream afresh from a constant
   input, so an endless run stays finite.  The weights are bf16; it takes the server workload's other options and
   reports the same fields and ``ffn``;
+* ``--workload generate`` closes the layer workload into generation, as a server runs it.  Per step:
+  ``gsx_embed_gather`` of the previous step's token ids (the input of layer 0), the layers, a final ``gsx_add_rmsnorm``,
+  the LM head, which is the bf16 decode GEMM with N = ``--vocab`` (default 128256), and ``gsx_sample`` with
+  ``--temperature`` (0.8), ``--top-k`` (50), ``--top-p`` (0.95) and ``--seed`` into the other of two token buffers.  A
+  step's token feeds the next step through device memory: nothing waits for the host, which passes only the step
+  number.  ``--batch`` is 1..16.  It reports the layer workload's fields, ``vocab``, ``tokens_per_s``,
+  ``bytes_per_step`` (LM head and embedding rows included), ``tbps`` from it, and ``tokens_in_range``: every id of the
+  last step lies in ``[0, vocab)``;
 * ``--workload prefill`` is the same decoder layer in the prefill phase, the compute-bound half of a server:
   ``--batch`` sequences (1..256) of ``--chunk`` new tokens each (default 2048; ``batch * chunk`` a multiple of 128),
   which land at positions ``[--context - chunk, --context)``: ``--context`` is the length after the chunk, and has
@@ -216,6 +224,14 @@ class Kernels:
             L.gsx_add_rmsnorm.argtypes = [vp, i32, vp, i64, vp, vp, i64, vp, vp, i64, vp, i32, i32, ctypes.c_float]
             L.gsx_silu_mul.argtypes = [vp, i32, vp, i64, vp, i64, vp, i32, i32]
             L.gsx_add_rmsnorm.restype = L.gsx_silu_mul.restype = i32
+        if hasattr(L, "gsx_sample"):  # likewise: an image built before the sampler and the embedding gather
+            i64, u64, fp = ctypes.c_int64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_float)
+            L.gsx_sample.argtypes = [vp, vp, i64, vp, vp, vp, vp, u64, vp, i32, i32]
+            L.gsx_embed_gather.argtypes = [vp, vp, i64, vp, vp, i64, i32, i32, i32]
+            L.gsx_event_time_sample.argtypes = [*L.gsx_sample.argtypes, i32, fp]
+            L.gsx_event_time_embed_gather.argtypes = [*L.gsx_embed_gather.argtypes, i32, fp]
+            L.gsx_sample.restype = L.gsx_embed_gather.restype = i32
+            L.gsx_event_time_sample.restype = L.gsx_event_time_embed_gather.restype = i32
         L.gsx_last_error.argtypes, L.gsx_last_error.restype = [], ctypes.c_char_p
         self.L, self.path = L, path
 
@@ -314,6 +330,43 @@ class Kernels:
     def silu_mul(self, s, gu: int, y: int, m: int, i: int):
         """``y[m][i] = silu(gu[:, :i]) * gu[:, i:]``: bf16, contiguous rows."""
         self._ck(self.L.gsx_silu_mul(s, 0, ctypes.c_void_p(gu), 2 * i, ctypes.c_void_p(y), i, None, m, i), "silu_mul")
+
+    def _sample_args(self, s, logits: int, temperature: int, top_k: int, top_p: int, seeds: int, counter: int,
+                     tokens_out: int, m: int, v: int) -> tuple:
+        if not hasattr(self.L, "gsx_sample"):
+            raise RuntimeError(f"{self.path} has no gsx_sample: rebuild it")
+        return (s, ctypes.c_void_p(logits), v, *(ctypes.c_void_p(x) for x in (temperature, top_k, top_p, seeds)),
+                counter & 0xFFFFFFFFFFFFFFFF, ctypes.c_void_p(tokens_out), m, v)
+
+    def sample(self, s, logits: int, temperature: int, top_k: int, top_p: int, seeds: int, counter: int,
+               tokens_out: int, m: int, v: int):
+        """One int32 token id per row of ``logits[m][v]`` (bf16, contiguous rows); the per-row parameter arrays are
+        device addresses (0: NULL), ``counter`` is the step number."""
+        self._ck(self.L.gsx_sample(*self._sample_args(s, logits, temperature, top_k, top_p, seeds, counter, tokens_out,
+                                                      m, v)), "sample")
+
+    def time_sample(self, s, logits: int, temperature: int, top_k: int, top_p: int, seeds: int, counter: int,
+                    tokens_out: int, m: int, v: int, iters: int) -> float:
+        ms = ctypes.c_float(0)
+        self._ck(self.L.gsx_event_time_sample(*self._sample_args(s, logits, temperature, top_k, top_p, seeds, counter,
+                                                                 tokens_out, m, v), iters, ctypes.byref(ms)),
+                 "time_sample")
+        return ms.value
+
+    def _embed_args(self, s, table: int, tokens: int, out: int, m: int, h: int, v: int) -> tuple:
+        if not hasattr(self.L, "gsx_embed_gather"):
+            raise RuntimeError(f"{self.path} has no gsx_embed_gather: rebuild it")
+        return (s, ctypes.c_void_p(table), h, ctypes.c_void_p(tokens), ctypes.c_void_p(out), h, m, h, v)
+
+    def embed_gather(self, s, table: int, tokens: int, out: int, m: int, h: int, v: int):
+        """``out[m][h]`` = rows ``tokens[m]`` (int32, device memory) of ``table[v][h]``: bf16, contiguous rows."""
+        self._ck(self.L.gsx_embed_gather(*self._embed_args(s, table, tokens, out, m, h, v)), "embed_gather")
+
+    def time_embed_gather(self, s, table: int, tokens: int, out: int, m: int, h: int, v: int, iters: int) -> float:
+        ms = ctypes.c_float(0)
+        self._ck(self.L.gsx_event_time_embed_gather(*self._embed_args(s, table, tokens, out, m, h, v), iters,
+                                                    ctypes.byref(ms)), "time_embed_gather")
+        return ms.value
 
     def sync(self, s):
         self._ck(self.L.gsx_stream_sync(s), "stream_sync")
@@ -609,7 +662,74 @@ def layer_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, hea
     # the closures hold addresses, not tensors
     step.keep = (wqkv, wo, wgu, wdown, ln, kc, vc, table, start, lens, cos, sin, x0, resid, xn, sub, qkv, q, o, gu, act,
                  ws)
+    step.io = {"x0": x0, "resid": resid, "sub": sub, "xn": xn}  # what the generate workload puts around the layers
     return step, sync, finite
+
+
+GENERATE_MAX_VOCAB = 262144
+
+
+def generate_refusal(batch: int, vocab: int) -> str | None:
+    """Why ``--workload generate`` cannot run these sizes, or None: known before anything touches the device."""
+    if not 1 <= batch <= 16:
+        return f"--batch {batch}: 1..16 rows (the LM head is the decode GEMM)"
+    if not 16 <= vocab <= GENERATE_MAX_VOCAB or vocab % 16:
+        return f"--vocab {vocab}: a multiple of 16 in 16..{GENERATE_MAX_VOCAB}"
+    return None
+
+
+def generate_step_bytes(layers: int, one_layer_bytes: int, kv_bytes: int, batch: int, hidden: int, vocab: int) -> int:
+    """Bytes one generation step reads: the layers' weights and KV, the LM head ``[vocab][hidden]`` and the ``batch``
+    embedding rows (bf16)."""
+    return layers * (one_layer_bytes + kv_bytes) + vocab * hidden * 2 + batch * hidden * 2
+
+
+def generate_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, heads: int, kv_heads: int, page: int,
+                   ffn: int, w_layers: int, kv_layers: int, vocab: int, temperature: float, top_k: int, top_p: float,
+                   seed: int):
+    """``(step, sync, finite, tokens)`` of the generate workload: a step of :func:`layer_steps` between the embedding
+    lookup of the previous step's tokens and the final norm, the LM head (the decode GEMM with N = ``vocab``) and the
+    sampler, which writes the other of two token buffers.  The tokens go from step to step through device memory;
+    the host passes only the step number.  ``tokens()`` synchronises and returns the last step's token ids."""
+    hidden = heads * ATTN_D
+    bf = torch.bfloat16
+    layers, sync, layers_finite = layer_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, kv_heads, page, ffn,
+                                              w_layers, kv_layers)
+    io = layers.io
+    embed = torch.randn(vocab, hidden, device=dev, dtype=bf)
+    head = torch.empty(vocab, hidden, device=dev, dtype=bf)
+    for lo in range(0, vocab, 16384):  # in slices: nothing large is ever held in fp32
+        head[lo:lo + 16384].copy_(torch.randn(min(16384, vocab - lo), hidden, device=dev) / math.sqrt(hidden))
+    lnf = torch.ones(hidden, device=dev, dtype=bf)
+    logits = torch.empty(batch, vocab, device=dev, dtype=bf)
+    tokens = [torch.randint(0, vocab, (batch,), device=dev, dtype=torch.int32) for _ in range(2)]
+    temp = torch.full((batch,), temperature, device=dev, dtype=torch.float32)
+    topk = torch.full((batch,), top_k, device=dev, dtype=torch.int32)
+    topp = torch.full((batch,), top_p, device=dev, dtype=torch.float32)
+    seeds = (torch.arange(batch, device=dev, dtype=torch.int64) + (seed & 0x7FFFFFFFFFFFFFFF)).contiguous()
+    torch.cuda.synchronize()
+    count = [0]
+
+    def step():
+        n = count[0]
+        count[0] += 1
+        kl.embed_gather(gs, embed.data_ptr(), tokens[n % 2].data_ptr(), io["x0"].data_ptr(), batch, hidden, vocab)
+        layers()
+        kl.add_rmsnorm(gs, io["sub"].data_ptr(), io["resid"].data_ptr(), 0, lnf.data_ptr(), io["xn"].data_ptr(), batch,
+                       hidden, LAYER_EPS)
+        kl.decode_gemm(gs, "bf16", io["xn"].data_ptr(), head.data_ptr(), logits.data_ptr(), batch, vocab, hidden)
+        kl.sample(gs, logits.data_ptr(), temp.data_ptr(), topk.data_ptr(), topp.data_ptr(), seeds.data_ptr(), n,
+                  tokens[(n + 1) % 2].data_ptr(), batch, vocab)
+
+    def finite():
+        return layers_finite() and bool(torch.isfinite(logits.float()).all())
+
+    def last_tokens():
+        kl.sync(gs)
+        return tokens[count[0] % 2].tolist()
+
+    step.keep = (layers, embed, head, lnf, logits, tokens, temp, topk, topp, seeds)
+    return step, sync, finite, last_tokens
 
 
 def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, context: int, heads: int, kv_heads: int,
@@ -693,9 +813,12 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         probe_limit: bool = False, dtype: str = "bf16", workload: str = "gemm", batch: int = 8,
         weights_gib: float | None = None, context: int = 8192, heads: int = 64, kv_heads: int = 8,
         kv_dtype: str = "bf16", kv_gib: float | None = None, page: int = 16, ffn: int | None = None,
-        chunk: int = 2048) -> dict:
+        chunk: int = 2048, vocab: int = 128256, temperature: float = 0.8, top_k: int = 50, top_p: float = 0.95,
+        seed: int = 0) -> dict:
     if workload == "prefill" and (why := prefill_refusal(batch, chunk, context)):
         raise SystemExit(f"--workload prefill: {why}")
+    if workload == "generate" and (why := generate_refusal(batch, vocab)):
+        raise SystemExit(f"--workload generate: {why}")
     import torch
 
     lib_path = kernels_lib_path()
@@ -727,11 +850,12 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     m = n = k = size
     if dtype not in ("bf16", "fp8", "mxfp4"):
         raise SystemExit(f"--dtype {dtype}: bf16, fp8 or mxfp4")
-    if workload not in ("gemm", "decode", "attn", "server", "layer", "prefill"):
-        raise SystemExit(f"--workload {workload}: gemm, decode, attn, server, layer or prefill")
+    if workload not in ("gemm", "decode", "attn", "server", "layer", "prefill", "generate"):
+        raise SystemExit(f"--workload {workload}: gemm, decode, attn, server, layer, prefill or generate")
     decode = workload == "decode"
     prefill = workload == "prefill"
-    layer = workload == "layer"
+    generate = workload == "generate"
+    layer = workload == "layer" or generate  # the generate workload is the layer workload between tokens
     server = workload == "server" or layer  # the layer workload is the server workload with more in a layer
     attn = workload == "attn" or server or prefill  # these have the attention's shape options
     if server or prefill:
@@ -799,7 +923,11 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         kv_layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB),
                                    kv_layer_bytes(kv_dtype, batch, context, kv_heads))
         layers = max(w_layers, kv_layers)
-        if layer:
+        if generate:
+            step, sync, finite, last_tokens = generate_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads,
+                                                             kv_heads, page, ffn, w_layers, kv_layers, vocab,
+                                                             temperature, top_k, top_p, seed)
+        elif layer:
             step, sync, finite = layer_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, kv_heads, page, ffn,
                                              w_layers, kv_layers)
         else:
@@ -807,6 +935,8 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
                                               w_layers, kv_layers)
         # the projections (2 flops per weight and row: a weight is 2 bytes), and QK^T and PV over the context
         flops_attn = layers * (batch * one_layer_bytes + 4.0 * batch * heads * context * ATTN_D)
+        if generate:  # the LM head
+            flops_attn += 2.0 * batch * vocab * heads * ATTN_D
     elif attn:
         layer_bytes = kv_layer_bytes(kv_dtype, batch, context, kv_heads)
         layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB), layer_bytes)
@@ -904,6 +1034,12 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
                     "activations_finite": finite()})
         if layer:
             out["ffn"] = ffn
+        if generate:
+            step_bytes = generate_step_bytes(layers, one_layer_bytes, kv_layer_bytes(kv_dtype, batch, context, kv_heads),
+                                             batch, heads * ATTN_D, vocab)
+            out.update({"vocab": vocab, "temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed,
+                        "bytes_per_step": step_bytes, "tbps": done * step_bytes / el / 1e12,
+                        "tokens_in_range": all(0 <= t < vocab for t in last_tokens())})
     elif attn:
         out.update({"workload": workload, "batch": batch, "layers": layers, "context": context, "heads": heads,
                     "kv_heads": kv_heads, "kv_dtype": kv_dtype, "page": page,
@@ -936,6 +1072,8 @@ class _Parser(argparse.ArgumentParser):
         top = 256 if wide else 16
         if not 1 <= ns.batch <= top:
             self.error(f"argument --batch: {ns.batch} is not in 1..{top} (--workload {ns.workload})")
+        if ns.workload == "generate" and (why := generate_refusal(ns.batch, ns.vocab)):
+            self.error(f"--workload generate: {why}")
         if ns.workload == "prefill":
             # --context means something else here, the length AFTER the chunk, and the chunk's place follows from it:
             # the other workloads' default is not taken over silently
@@ -965,6 +1103,17 @@ def add_attn_arguments(ap: argparse.ArgumentParser) -> None:
                          "given: the length after the chunk); batch x chunk a multiple of 128")
 
 
+def add_generate_arguments(ap: argparse.ArgumentParser) -> None:
+    """The options of ``--workload generate`` (shared with the isolation harness)."""
+    ap.add_argument("--vocab", type=int, default=128256,
+                    help="--workload generate: the vocabulary, a multiple of 16 up to 262144")
+    ap.add_argument("--temperature", type=float, default=0.8,
+                    help="--workload generate: the sampling temperature of every row (<= 0: greedy)")
+    ap.add_argument("--top-k", type=int, default=50, help="--workload generate: top-k of every row (<= 0: no limit)")
+    ap.add_argument("--top-p", type=float, default=0.95, help="--workload generate: top-p of every row (>= 1: no cut)")
+    ap.add_argument("--seed", type=int, default=0, help="--workload generate: row r draws with seed + r")
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = os.environ.get("GSX_ENV_PREFIX", "SHARED_GPU_MEM")
     ap = _Parser(description="GEMM loop inside the pod's GPU share (the gpushare sample workload)")
@@ -977,7 +1126,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="operand type of the GEMM: bf16, fp8 (OCP e4m3) or mxfp4 (e2m1 with e8m0 block scales, "
                          "quantised from bf16 by the library; --kernel gsx only); the output stays bf16")
     ap.add_argument("--size", type=int, default=8192)
-    ap.add_argument("--workload", default="gemm", choices=["gemm", "decode", "attn", "server", "layer", "prefill"],
+    ap.add_argument("--workload", default="gemm",
+                    choices=["gemm", "decode", "attn", "server", "layer", "prefill", "generate"],
                     help="gemm: one large square GEMM per step (compute-bound); decode: --batch activation rows "
                          "against a ring of --size x --size weight matrices, one launch each (HBM-bandwidth-bound); "
                          "attn: one decode step of attention per layer over a ring of paged KV caches; server: a "
@@ -985,9 +1135,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "projection) over caches that grow; layer: a whole decoder layer per ring layer (the server "
                          "workload's with a residual stream, two RMSNorms and the SwiGLU MLP); prefill: the same layer on "
                          "--batch sequences of --chunk new tokens each, causal attention over the paged cache "
-                         "(compute-bound)")
+                         "(compute-bound); generate: the layer workload closed into generation: the embedding lookup of "
+                         "the last step's tokens, the layers, a final RMSNorm, the LM head (--vocab columns) and the "
+                         "sampler, token to token through device memory")
     ap.add_argument("--batch", type=int, default=8, metavar="N",
-                    help="--workload decode, server and layer: the activation rows (M), 1..16; --workload attn and "
+                    help="--workload decode, server, layer and generate: the activation rows (M), 1..16; --workload attn and "
                          "prefill: the sequences, 1..256")
     add_attn_arguments(ap)
     ap.add_argument("--weights-gib", type=float, default=None,
@@ -995,6 +1147,7 @@ def build_parser() -> argparse.ArgumentParser:
                          "share if that is smaller; never fewer than two matrices or layers)")
     ap.add_argument("--ffn", type=int, default=None,
                     help="--workload layer and prefill: width of the MLP (default 3.5 x hidden, rounded to a multiple of 64)")
+    add_generate_arguments(ap)
     ap.add_argument("--seconds", type=float, default=0.0, help="0 = run forever (like the reference sample)")
     ap.add_argument("--iters", type=int, default=0)
     ap.add_argument("--touch", action="store_true")
@@ -1008,7 +1161,8 @@ def main(argv=None) -> int:
     res = run(a.total, a.allocated, kernel=a.kernel, size=a.size, seconds=a.seconds, iters=a.iters, touch=a.touch,
               quiet=a.json, probe_limit=a.probe_limit, dtype=a.dtype, workload=a.workload, batch=a.batch,
               weights_gib=a.weights_gib, context=a.context, heads=a.heads, kv_heads=a.kv_heads, kv_dtype=a.kv_dtype,
-              kv_gib=a.kv_gib, page=a.page, ffn=a.ffn, chunk=a.chunk)
+              kv_gib=a.kv_gib, page=a.page, ffn=a.ffn, chunk=a.chunk, vocab=a.vocab, temperature=a.temperature,
+              top_k=a.top_k, top_p=a.top_p, seed=a.seed)
     print(json.dumps(res) if a.json else res, flush=True)
     return 0
 

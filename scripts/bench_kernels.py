@@ -742,6 +742,124 @@ def attn_prefill(shapes=ATTN_PREFILL_SHAPES, heads=((64, 8),), kinds=("bf16", "f
     return out
 
 
+SAMPLE_VOCABS = (128256, 262144)
+SAMPLE_ROWS = (1, 8, 16, 256)
+
+
+def sample(vocabs=SAMPLE_VOCABS, rows=SAMPLE_ROWS, hidden=8192, iters=50, gemm_iters=5, rounds=3, gather_rows=65536):
+    """The sampler against torch on the same logits, interleaved, the median of ``rounds`` timings (the first round
+    warms up) of ``iters`` back-to-back calls, in microseconds per call.  Greedy: ``torch.argmax``.  Sampling at
+    T 0.8, k 50, p 0.95: ``topk`` -> softmax -> cumulative-sum cut -> ``multinomial`` -> gather, which is what a server
+    in eager torch runs.  With M <= 16 the logits are what ``gsx_decode_gemm_nt`` (N = V, K = ``hidden``) wrote from
+    random normal operands, and that call is timed too: ``sampler_share`` is the sampler's part of LM head plus
+    sampler.  With M = 256 they are random normal.  The logits of one case (at most 134 MB) stay in the Infinity Cache
+    between calls, as they are after the LM head has written them.  Then ``gsx_embed_gather`` of ``gather_rows``
+    random rows of a [V][hidden] table (bytes read plus written) against ``gsx_hbm_fill`` over the bytes written."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+
+    def torch_us(fn):
+        torch.cuda.synchronize()
+        with torch.cuda.stream(ts):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            for _ in range(iters):
+                fn()
+            e1.record(ts)
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / iters
+
+    for v in vocabs:
+        w = torch.empty(v, hidden, device="cuda", dtype=torch.bfloat16)
+        for lo in range(0, v, 16384):
+            w[lo:lo + 16384].copy_(torch.randn(min(16384, v - lo), hidden, device="cuda") / hidden ** 0.5)
+        for m in rows:
+            row = {"v": v, "m": m}
+            if m <= 16:
+                x = torch.randn(m, hidden, device="cuda", dtype=torch.bfloat16)
+                logits = torch.empty(m, v, device="cuda", dtype=torch.bfloat16)
+                torch.cuda.synchronize()
+                gargs = (s, "bf16", x.data_ptr(), w.data_ptr(), logits.data_ptr(), m, v, hidden)
+                hip.decode_gemm_nt(*gargs)
+                s.sync()
+            else:
+                logits = torch.randn(m, v, device="cuda", dtype=torch.bfloat16)
+            temp = torch.full((m,), 0.8, device="cuda")
+            topk = torch.full((m,), 50, device="cuda", dtype=torch.int32)
+            topp = torch.full((m,), 0.95, device="cuda")
+            seeds = torch.arange(m, device="cuda", dtype=torch.int64) + 1
+            tok = torch.empty(m, device="cuda", dtype=torch.int32)
+            torch.cuda.synchronize()
+
+            def torch_sample():
+                vals, idx = torch.topk(logits.float() / 0.8, 50, dim=-1)
+                probs = torch.softmax(vals, -1)
+                before = torch.cumsum(probs, -1) - probs
+                probs = probs.masked_fill(before >= 0.95, 0.0)
+                return idx.gather(-1, torch.multinomial(probs, 1))
+
+            modes = {"greedy": ((s, logits.data_ptr(), v, 0, 0, 0, 0, 0, tok.data_ptr(), m, v),
+                                lambda: torch.argmax(logits, -1)),
+                     "k50_p95": ((s, logits.data_ptr(), v, temp.data_ptr(), topk.data_ptr(), topp.data_ptr(),
+                                  seeds.data_ptr(), 0, tok.data_ptr(), m, v), torch_sample)}
+            runs = {f"{mode}_{who}": [] for mode in modes for who in ("gsx", "torch")}
+            if m <= 16:
+                runs["lm_head"] = []
+            for r in range(rounds + 1):
+                for mode, (args, ref) in modes.items():
+                    a, b = hip.time_sample(*args, iters) * 1e3 / iters, torch_us(ref)
+                    if r:
+                        runs[f"{mode}_gsx"].append(a)
+                        runs[f"{mode}_torch"].append(b)
+                if m <= 16:
+                    g = hip.time_decode_gemm(*gargs, gemm_iters) * 1e3 / gemm_iters
+                    if r:
+                        runs["lm_head"].append(g)
+            for name, vals in runs.items():
+                med = statistics.median(vals)
+                row[f"{name}_us"] = round(med, 2)
+                row[f"{name}_spread"] = round((max(vals) - min(vals)) / med, 3)
+            for mode in modes:
+                row[f"{mode}_torch_over_gsx"] = round(row[f"{mode}_torch_us"] / row[f"{mode}_gsx_us"], 2)
+                if m <= 16:
+                    row[f"{mode}_sampler_share"] = round(row[f"{mode}_gsx_us"]
+                                                         / (row[f"{mode}_gsx_us"] + row["lm_head_us"]), 4)
+            out.append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+            del logits, temp, topk, topp, seeds, tok
+        # the gather, with the table of this vocabulary
+        ids = torch.randint(0, v, (gather_rows,), device="cuda", dtype=torch.int32)
+        dst = torch.empty(gather_rows, hidden, device="cuda", dtype=torch.bfloat16)
+        nbytes = gather_rows * hidden * 2
+        torch.cuda.synchronize()
+        eargs = (s, w.data_ptr(), hidden, ids.data_ptr(), dst.data_ptr(), hidden)
+        runs = {"gather": [], "fill": [], "gather_16_us": []}
+        for r in range(rounds + 1):
+            ms = hip.time_embed_gather(*eargs, gather_rows, hidden, v, 5)
+            s.sync()
+            t0 = time.perf_counter()
+            for _ in range(5):
+                hip.hbm_fill(s, dst.data_ptr(), nbytes, r)
+            s.sync()
+            dt = time.perf_counter() - t0
+            small = hip.time_embed_gather(*eargs, 16, hidden, v, iters)
+            if r:
+                runs["gather"].append(5 * 2 * nbytes / (ms * 1e-3) / 1e12)
+                runs["fill"].append(5 * nbytes / dt / 1e12)
+                runs["gather_16_us"].append(small * 1e3 / iters)
+        row = {"v": v, "op": "embed_gather", "rows": gather_rows, "h": hidden, "bytes_written": nbytes,
+               "gather_TBps_read_plus_written": round(statistics.median(runs["gather"]), 3),
+               "hbm_fill_TBps_written": round(statistics.median(runs["fill"]), 3),
+               "gather_16_rows_us": round(statistics.median(runs["gather_16_us"]), 2)}
+        out.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+        del w, ids, dst
+        torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 def hbm(nbytes=16 << 30, reps=5):
     s = hip.Stream(0)
     buf = hip.DeviceBuffer(0, nbytes)
@@ -773,7 +891,7 @@ if __name__ == "__main__":
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
                 "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "attn_decode": attn_decode,
-                "kv_append": kv_append, "norm_act": norm_act, "attn_prefill": attn_prefill,
+                "kv_append": kv_append, "norm_act": norm_act, "attn_prefill": attn_prefill, "sample": sample,
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
                 "hbm": hbm}
