@@ -129,6 +129,12 @@ def lib():
         _sample_sig = [vp, vp, ctypes.c_int64, vp, vp, vp, vp, u64, vp, i32, i32]
         # stream, table, table_stride, tokens, out, out_stride; M, H, V
         _embed_sig = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i32, i32, i32]
+        # stream, logits, logits_stride, topk_ids, topk_w, plan; M, E, topk
+        _moe_route_sig = [vp, vp, ctypes.c_int64, vp, vp, vp, i32, i32, i32]
+        # stream, kind, A, a_div, B, C, plan; M, topk, E, N, K; scale_a, scale_b, scale_mode
+        _moe_gemm_sig = [vp, i32, vp, i32, vp, vp, vp] + [i32] * 5 + [vp, vp, i32]
+        # stream, Y, y_stride, topk_w, out, out_stride; M, topk, H
+        _moe_combine_sig = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i32, i32, i32]
         sig = {
             "gsx_last_error": ([], ctypes.c_char_p),
             "gsx_device_count": ([ctypes.POINTER(i32)], i32),
@@ -193,6 +199,15 @@ def lib():
             "gsx_event_time_sample": ([*_sample_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_embed_gather": (_embed_sig, i32),
             "gsx_event_time_embed_gather": ([*_embed_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_moe_route": (_moe_route_sig, i32),
+            "gsx_event_time_moe_route": ([*_moe_route_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_moe_gemm_nt": (_moe_gemm_sig, i32),
+            "gsx_moe_gemm_nt_launch_cfg": ([*_moe_gemm_sig, i32], i32),
+            "gsx_moe_gemm_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_moe_gemm_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 4, i32),
+            "gsx_event_time_moe_gemm": ([*_moe_gemm_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_moe_combine": (_moe_combine_sig, i32),
+            "gsx_event_time_moe_combine": ([*_moe_combine_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
             "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
                                   i32),
@@ -908,4 +923,104 @@ def time_embed_gather(stream: Stream, table: int, table_stride: int, tokens: int
     ms = ctypes.c_float(0)
     _ck(lib().gsx_event_time_embed_gather(*_embed_gather_args(stream, table, table_stride, tokens, out, out_stride, m,
                                                               h, v), iters, ctypes.byref(ms)), "time_embed_gather")
+    return ms.value
+
+
+# Mixture-of-experts decode (gsx_kernels.h): at most 16 tokens x 8 experts = 128 (token, expert) pairs, and a plan of
+# 516 int32 in device memory that groups them by expert
+MOE_MAX_PAIRS = 128
+MOE_PLAN_INTS = 4 + 4 * MOE_MAX_PAIRS
+
+
+def _moe_route_args(stream: Stream, logits: int, logits_stride: int, topk_ids: int, topk_w: int, plan: int, m: int,
+                    e: int, topk: int) -> tuple:
+    return (stream.handle, ctypes.c_void_p(logits), logits_stride, ctypes.c_void_p(topk_ids), ctypes.c_void_p(topk_w),
+            ctypes.c_void_p(plan), m, e, topk)
+
+
+def moe_route(stream: Stream, logits: int, logits_stride: int, topk_ids: int, topk_w: int, plan: int, m: int, e: int,
+              topk: int):
+    """The MoE router: from ``m <= 16`` rows of ``e`` bf16 router logits, ``topk_ids[m][topk]`` (int32, descending
+    logit, ties to the lowest index), ``topk_w[m][topk]`` (fp32, a softmax over the selected logits) and ``plan``
+    (``MOE_PLAN_INTS`` int32: the pairs grouped by expert, what :func:`moe_gemm_nt` reads).  Ids and plan are exact
+    (tests/moe_cases.py is their twin).  All addresses are device addresses.  Not synchronised."""
+    _ck(lib().gsx_moe_route(*_moe_route_args(stream, logits, logits_stride, topk_ids, topk_w, plan, m, e, topk)),
+        "moe_route")
+
+
+def time_moe_route(stream: Stream, logits: int, logits_stride: int, topk_ids: int, topk_w: int, plan: int, m: int,
+                   e: int, topk: int, iters: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_moe_route(*_moe_route_args(stream, logits, logits_stride, topk_ids, topk_w, plan, m, e,
+                                                        topk), iters, ctypes.byref(ms)), "time_moe_route")
+    return ms.value
+
+
+def _moe_gemm_args(stream: Stream, kind: str, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                   n: int, k: int, scale_a: int, scale_b: int, scale_mode: int) -> tuple:
+    return (stream.handle, _decode_kind(kind), ctypes.c_void_p(a), a_div, ctypes.c_void_p(b), ctypes.c_void_p(c),
+            ctypes.c_void_p(plan), m, topk, e, n, k, ctypes.c_void_p(scale_a), ctypes.c_void_p(scale_b), scale_mode)
+
+
+def moe_gemm_nt(stream: Stream, kind: str, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                n: int, k: int, scale_a: int = 0, scale_b: int = 0, scale_mode: int = SCALE_NONE):
+    """The grouped expert GEMM: for every pair ``p`` of ``plan`` with expert ``x``, ``C[p][n]`` (bf16) ``=
+    A[p // a_div][k] * B[x][n][k]^T``.  ``a_div = topk`` is the up projection (a pair reads its token's row),
+    ``a_div = 1`` the down projection (a pair reads its own row).  ``kind`` and operand formats as
+    :func:`decode_gemm_nt`; fp8 takes ``SCALE_NONE`` or ``SCALE_ROW`` (``scale_a`` per row of A, ``scale_b[e][n]``),
+    mxfp4 ``scale_a[rows of A][k / 32]`` and ``scale_b[e][n][k / 32]``.  Only the experts the plan names are read.
+    Not synchronised."""
+    _ck(lib().gsx_moe_gemm_nt(*_moe_gemm_args(stream, kind, a, a_div, b, c, plan, m, topk, e, n, k, scale_a, scale_b,
+                                              scale_mode)), "moe_gemm_nt")
+
+
+def moe_gemm_cfgs() -> dict[int, tuple[str, int, int, int, int]]:
+    """``{index: (name, bn, waves, inflight, decode_cfg)}`` of the grouped GEMM's configurations, read from the
+    library's table: the four shapes the decode GEMM dispatches to, each with the index of the decode configuration
+    (:func:`decode_gemm_cfgs`) it equals."""
+    out: dict[int, tuple[str, int, int, int, int]] = {}
+    while (name := lib().gsx_moe_gemm_cfg_name(len(out))) is not None:
+        v = [ctypes.c_int(0) for _ in range(4)]
+        if lib().gsx_moe_gemm_cfg_shape(len(out), *map(ctypes.byref, v)) != 0:
+            raise HipError(f"moe gemm cfg {len(out)} has a name and no shape")
+        out[len(out)] = (name.decode(), *(x.value for x in v))
+    return out
+
+
+def moe_gemm_nt_cfg(stream: Stream, kind: str, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int,
+                    e: int, n: int, k: int, cfg: int, scale_a: int = 0, scale_b: int = 0,
+                    scale_mode: int = SCALE_NONE):
+    """Launch one configuration of the grouped GEMM; an unknown config or a shape it cannot take raises HipError."""
+    _ck(lib().gsx_moe_gemm_nt_launch_cfg(*_moe_gemm_args(stream, kind, a, a_div, b, c, plan, m, topk, e, n, k,
+                                                         scale_a, scale_b, scale_mode), cfg), f"moe gemm cfg {cfg}")
+
+
+def time_moe_gemm(stream: Stream, kind: str, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                  n: int, k: int, iters: int, scale_a: int = 0, scale_b: int = 0,
+                  scale_mode: int = SCALE_NONE) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_moe_gemm(*_moe_gemm_args(stream, kind, a, a_div, b, c, plan, m, topk, e, n, k, scale_a,
+                                                      scale_b, scale_mode), iters, ctypes.byref(ms)), "time_moe_gemm")
+    return ms.value
+
+
+def _moe_combine_args(stream: Stream, y: int, y_stride: int, topk_w: int, out: int, out_stride: int, m: int, topk: int,
+                      h: int) -> tuple:
+    return (stream.handle, ctypes.c_void_p(y), y_stride, ctypes.c_void_p(topk_w), ctypes.c_void_p(out), out_stride, m,
+            topk, h)
+
+
+def moe_combine(stream: Stream, y: int, y_stride: int, topk_w: int, out: int, out_stride: int, m: int, topk: int,
+                h: int):
+    """``out[r][0..h)`` (bf16) is the sum over ``j`` of ``topk_w[r][j] * Y[r * topk + j][0..h)``, in fp32, in the order
+    of ``j``, every multiply and add rounded on its own: bit-exact.  Strides are in elements.  Not synchronised."""
+    _ck(lib().gsx_moe_combine(*_moe_combine_args(stream, y, y_stride, topk_w, out, out_stride, m, topk, h)),
+        "moe_combine")
+
+
+def time_moe_combine(stream: Stream, y: int, y_stride: int, topk_w: int, out: int, out_stride: int, m: int, topk: int,
+                     h: int, iters: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_moe_combine(*_moe_combine_args(stream, y, y_stride, topk_w, out, out_stride, m, topk, h),
+                                         iters, ctypes.byref(ms)), "time_moe_combine")
     return ms.value

@@ -147,9 +147,17 @@ def server_cmdline(a: argparse.Namespace) -> list[str]:
 SCENARIOS_LAYER = SCENARIOS_SERVER
 
 
-def layer_cmdline(a: argparse.Namespace) -> list[str]:
-    """The layer pods' options: the server pods', and the MLP's width."""
+def dense_layer_cmdline(a: argparse.Namespace) -> list[str]:
+    """The server pods' options, and the MLP's width."""
     return server_cmdline(a) + (["--ffn", str(a.ffn)] if a.ffn is not None else [])
+
+
+def layer_cmdline(a: argparse.Namespace) -> list[str]:
+    """The layer pods' options: the server pods', the MLP's width, and its experts where ``--experts`` is set (a
+    dense layer's command line is what it was)."""
+    experts = getattr(a, "experts", 0)
+    moe = ["--experts", str(experts), "--experts-active", str(a.experts_active)] if experts else []
+    return dense_layer_cmdline(a) + moe
 
 
 def generate_cmdline(a: argparse.Namespace) -> list[str]:
@@ -159,8 +167,8 @@ def generate_cmdline(a: argparse.Namespace) -> list[str]:
 
 
 def prefill_cmdline(a: argparse.Namespace) -> list[str]:
-    """The prefill pods' options: the layer pods', and the chunk."""
-    return layer_cmdline(a) + ["--chunk", str(a.chunk)]
+    """The prefill pods' options: the dense layer pods' (a prefill pod takes no experts), and the chunk."""
+    return dense_layer_cmdline(a) + ["--chunk", str(a.chunk)]
 
 
 def with_solo(summary: dict, solo: list[dict]) -> dict:
@@ -196,6 +204,7 @@ def build_parser() -> argparse.ArgumentParser:
                          "--workload attn)")
     pod_workload.add_attn_arguments(ap)
     pod_workload.add_generate_arguments(ap)
+    pod_workload.add_moe_arguments(ap)
     ap.add_argument("--weights-gib", type=float, default=None,
                     help="--workload server and layer: size of the pods' weight ring (default: the workload's)")
     ap.add_argument("--ffn", type=int, default=None,

@@ -37,6 +37,12 @@ prefill_visible_pairs = _mod.prefill_visible_pairs
 add_generate_arguments = _mod.add_generate_arguments
 generate_refusal = _mod.generate_refusal
 generate_step_bytes = _mod.generate_step_bytes
+add_moe_arguments = _mod.add_moe_arguments
+moe_refusal = _mod.moe_refusal
+moe_active = _mod.moe_active
+moe_expert_bytes = _mod.moe_expert_bytes
+moe_layer_weight_bytes = _mod.moe_layer_weight_bytes
+moe_layer_read_bytes = _mod.moe_layer_read_bytes
 BatchRangeParser = _mod._Parser
 
 if __name__ == "__main__":

@@ -15,7 +15,8 @@ Targets (outputs land in ``gpushare_scheduler_extender_amd/_native/``):
                 workload with the MXFP4 quantiser, the decode GEMM (M <= 16) on the same operands, decode attention over a
                 paged KV cache (attn_decode.hip), RoPE + KV-cache append (kv_append.hip), fused residual add + RMSNorm
                 and SwiGLU (norm_act.hip), causal prefill attention over the same cache (attn_prefill.hip), the token
-                sampler and the embedding gather (sample.hip), CU-masked streams.
+                sampler and the embedding gather (sample.hip), the MoE router and combine (moe.hip; the grouped expert
+                GEMM is a form of the decode kernel in gemm_decode.hip), CU-masked streams.
 * ``tools``   – standalone HIP executables (``gsx-cuprobe``, ``gsx-memprobe``, ``gsx-memtest``, ``gsx-cutest``).
 * ``isolate`` – ``libgsx_isolate.so``, the HSA tools library that enforces a pod's CU partition and HBM share
                 inside every HIP/HSA process of the pod, plus its host-only test driver (fake HSA runtime).

@@ -32,6 +32,13 @@
 //
 // The configurations (one table for the three kinds) vary W, F, BN and the cache policy of the loads of B; the
 // dispatch rule and the measurements behind it are at decode_pick() below and in profiles/gemm_decode/README.md.
+//
+// The grouped form (gsx_moe_gemm_nt, for a mixture of experts) is the same kernel with GRP = MoePlan: a workgroup is
+// (strip, slot of a plan in device memory), its fragment rows are the slot's (token, expert) pairs, A's rows are
+// gathered by the offset of the same buffer load, B is the slot's expert, and stores go to the pairs' rows of C.  The
+// K loop, the ring, the waves' split of K and the reduction are shared, so a row has the bits the plain kernel gives
+// it; with GRP = NoGroup every `if constexpr (GROUPED)` falls away and the plain instantiations have the registers,
+// LDS and scratch they had (profiles/gemm_decode/README.md; profiles/moe/README.md has the grouped ones).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -56,11 +63,55 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_buffer(const void* base, 
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, static_cast<int>(bytes), 0x00020000);
 }
 
+// What the grouped form (gsx_moe_gemm_nt) passes instead of NoGroup: a plan in device memory, which gsx_moe_route
+// wrote, or anyone.  Workgroup (strip, slot); grid.y is min(E, P) <= 128.
+struct MoePlan {
+  const int32_t* plan;
+  int P, E, a_div, a_rows;
+};
+struct NoGroup {};
+// A workgroup's slot of the plan.  Fragment row r < M (the slot's clamped count) is pair rows[begin + r]; the pair
+// reads row pair / a_div of A's a_rows rows, meets expert `expert` of B and of scale_b, and is stored to row `pair`
+// of C.
+struct MoeGroup {
+  const int32_t* rows;  // the plan's rows[GSX_MOE_MAX_PAIRS]
+  int begin, P, a_div, a_rows;
+  size_t expert;
+};
+
+// The pair of fragment row r, or -1: an index into rows outside [0, 128) and a pair outside [0, P) are dropped.
+__device__ __forceinline__ int moe_pair(const MoeGroup& g, int r, int M) {
+  const uint32_t idx = static_cast<uint32_t>(g.begin) + static_cast<uint32_t>(r);
+  if (r >= M || idx >= static_cast<uint32_t>(GSX_MOE_MAX_PAIRS)) return -1;
+  const int p = g.rows[idx];
+  return p >= 0 && p < g.P ? p : -1;
+}
+
 // MASKED: the loads of A and scale_a are plain loads inside `if (row < M)` instead of buffer loads.
-template <class OP, int NF, int W, int F, bool NT, bool MASKED, typename... EP>
+// GRP = MoePlan (never MASKED) is the grouped form: M is not passed but read, the slot's count; rows of A and C and the
+// expert of B come from the plan; the buffer over A covers all its a_rows rows, and a lane without a pair gets an
+// offset at its end.  A slot at or past n_active, one whose expert is outside [0, E) and one without a row return
+// before any barrier and read nothing of B; the count is clamped to 16, and moe_pair() drops what the rows of the plan
+// must not name.
+template <class OP, int NF, int W, int F, bool NT, bool MASKED, class GRP, typename... EP>
 __global__ __launch_bounds__(W * 64) void decode_kernel(const typename OP::elem* __restrict__ A,
                                                        const typename OP::elem* __restrict__ B,
-                                                       uint16_t* __restrict__ C, int M, int N, int K, EP... ep) {
+                                                       uint16_t* __restrict__ C, int M, int N, int K, GRP gp,
+                                                       EP... ep) {
+  constexpr bool GROUPED = std::is_same_v<GRP, MoePlan>;
+  static_assert(!(GROUPED && MASKED), "the grouped form has no masked form");
+  [[maybe_unused]] MoeGroup grp{};
+  if constexpr (GROUPED) {
+    constexpr int S = GSX_MOE_MAX_PAIRS;
+    const int slot = blockIdx.y;
+    if (slot >= gp.plan[0] || slot >= S) return;
+    const int e = gp.plan[4 + slot];
+    if (e < 0 || e >= gp.E) return;
+    const int count = gp.plan[4 + 2 * S + slot];
+    if (count <= 0) return;
+    M = count > 16 ? 16 : count;
+    grp = MoeGroup{gp.plan + 4 + 3 * S, gp.plan[4 + S + slot], gp.P, gp.a_div, gp.a_rows, static_cast<size_t>(e)};
+  }
   using T = typename OP::elem;
   using frag = typename OP::frag;
   constexpr int CH = OP::CH;
@@ -81,8 +132,16 @@ __global__ __launch_bounds__(W * 64) void decode_kernel(const typename OP::elem*
   // otherwise as a byte offset into the buffer of A's M rows, which is past its end for a row >= M
   [[maybe_unused]] const T* ap = A + (arow ? static_cast<size_t>(fr) * ld : 0) + fq * CU;
   const uint32_t arow_bytes = static_cast<uint32_t>(ld) * sizeof(T);
-  const __amdgpu_buffer_rsrc_t abuf = rows_buffer(A, M * arow_bytes);
-  const int aoff = static_cast<int>(fr * arow_bytes + fq * CHUNK);
+  // grouped: the pair's row of A's a_rows rows, or a_rows (the end of the buffer) for a lane without a pair
+  [[maybe_unused]] uint32_t ar = 0, an = 0;
+  if constexpr (GROUPED) {
+    const int p = moe_pair(grp, fr, M);
+    an = static_cast<uint32_t>(grp.a_rows);
+    ar = p >= 0 ? static_cast<uint32_t>(p / grp.a_div) : an;
+    B += grp.expert * static_cast<size_t>(N) * ld;
+  }
+  const __amdgpu_buffer_rsrc_t abuf = rows_buffer(A, GROUPED ? an * arow_bytes : M * arow_bytes);
+  const int aoff = static_cast<int>((GROUPED ? ar * arow_bytes : fr * arow_bytes) + fq * CHUNK);
   const T* bp[NF];
 #pragma unroll
   for (int f = 0; f < NF; ++f) bp[f] = B + (col0 + f * 16 + fr) * ld + fq * CU;
@@ -92,9 +151,12 @@ __global__ __launch_bounds__(W * 64) void decode_kernel(const typename OP::elem*
   if constexpr (MX) {
     const auto mx = from_args<MxArgs, MX>(ep...);
     sap = mx.sa + (arow ? static_cast<size_t>(fr) * (K / 32) : 0);
-    sabuf = rows_buffer(mx.sa, static_cast<uint32_t>(M) * (K / 32));  // 1 / 16 of A's bytes
+    // 1 / 16 of A's bytes
+    sabuf = rows_buffer(mx.sa, (GROUPED ? an : static_cast<uint32_t>(M)) * (K / 32));
+    const uint8_t* sb = mx.sb;
+    if constexpr (GROUPED) sb += grp.expert * static_cast<size_t>(N) * (K / 32);
 #pragma unroll
-    for (int f = 0; f < NF; ++f) sbp[f] = mx.sb + (col0 + f * 16 + fr) * (K / 32);
+    for (int f = 0; f < NF; ++f) sbp[f] = sb + (col0 + f * 16 + fr) * (K / 32);
   }
 
   // the ring: slot i holds one K-tile's fragments of A and of B, and for MX the 8 codes of the lane's rows
@@ -127,7 +189,9 @@ __global__ __launch_bounds__(W * 64) void decode_kernel(const typename OP::elem*
         ra[i][c] = __builtin_bit_cast(
             frag, __builtin_amdgcn_raw_buffer_load_b128(abuf, aoff + c * 4 * CHUNK, kt * ROW_BYTES, 0));
       if constexpr (MX)
-        rsa[i] = __builtin_bit_cast(i32x2, __builtin_amdgcn_raw_buffer_load_b64(sabuf, fr * (K / 32), kt * MX_ROW, 0));
+        rsa[i] = __builtin_bit_cast(
+            i32x2, __builtin_amdgcn_raw_buffer_load_b64(
+                       sabuf, GROUPED ? static_cast<int>(ar * (K / 32)) : fr * (K / 32), kt * MX_ROW, 0));
     }
   };
 
@@ -208,11 +272,21 @@ __global__ __launch_bounds__(W * 64) void decode_kernel(const typename OP::elem*
       const int row = fq * 4 + j;
       if (row >= M) continue;
       float v = s[j];
-      if constexpr (!MX && sizeof...(EP) != 0) {
-        const auto sc = from_args<Scaled, true>(ep...);
-        if (sc.sa != nullptr) v = (v * sc.sa[static_cast<size_t>(row) * sc.stride]) * sc.sb[col * sc.stride];
+      if constexpr (GROUPED) {
+        const int p = moe_pair(grp, row, M);
+        if (p < 0) continue;
+        if constexpr (!MX && sizeof...(EP) != 0) {  // a scale per row of A and per (expert, column), or none
+          const auto sc = from_args<Scaled, true>(ep...);
+          if (sc.sa != nullptr) v = (v * sc.sa[p / grp.a_div]) * sc.sb[grp.expert * static_cast<size_t>(N) + col];
+        }
+        C[static_cast<size_t>(p) * N + col] = f2bf(v);
+      } else {
+        if constexpr (!MX && sizeof...(EP) != 0) {
+          const auto sc = from_args<Scaled, true>(ep...);
+          if (sc.sa != nullptr) v = (v * sc.sa[static_cast<size_t>(row) * sc.stride]) * sc.sb[col * sc.stride];
+        }
+        C[static_cast<size_t>(row) * N + col] = f2bf(v);
       }
-      C[static_cast<size_t>(row) * N + col] = f2bf(v);
     }
   }
 }
@@ -274,18 +348,18 @@ int decode_launch_as(const char* who, hipStream_t s, const void* A, const void* 
   const dim3 grid(N / (NF * 16)), block(W * 64);
   uint16_t* c = static_cast<uint16_t*>(C);
   if constexpr (KIND == GSX_DECODE_BF16) {
-    hipLaunchKernelGGL((decode_kernel<Bf16, NF, W, F, NT, MASKED>), grid, block, 0, s,
-                       static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), c, M, N, K);
+    hipLaunchKernelGGL((decode_kernel<Bf16, NF, W, F, NT, MASKED, NoGroup>), grid, block, 0, s,
+                       static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), c, M, N, K, NoGroup{});
   } else if constexpr (KIND == GSX_DECODE_FP8) {
     const bool scaled = mode != GSX_GEMM_SCALE_NONE;  // the kernel gets (nullptr, nullptr, 0) for no scales
-    hipLaunchKernelGGL((decode_kernel<Fp8K128, NF, W, F, NT, MASKED, const float*, const float*, int>), grid, block,
-                       0, s, static_cast<const uint8_t*>(A), static_cast<const uint8_t*>(B), c, M, N, K,
-                       scaled ? static_cast<const float*>(sa) : nullptr,
+    hipLaunchKernelGGL((decode_kernel<Fp8K128, NF, W, F, NT, MASKED, NoGroup, const float*, const float*, int>), grid,
+                       block, 0, s, static_cast<const uint8_t*>(A), static_cast<const uint8_t*>(B), c, M, N, K,
+                       NoGroup{}, scaled ? static_cast<const float*>(sa) : nullptr,
                        scaled ? static_cast<const float*>(sb) : nullptr, mode == GSX_GEMM_SCALE_ROW ? 1 : 0);
   } else {
-    hipLaunchKernelGGL((decode_kernel<Mxfp4, NF, W, F, NT, MASKED, const uint8_t*, const uint8_t*>), grid, block, 0,
-                       s, static_cast<const uint8_t*>(A), static_cast<const uint8_t*>(B), c, M, N, K,
-                       static_cast<const uint8_t*>(sa), static_cast<const uint8_t*>(sb));
+    hipLaunchKernelGGL((decode_kernel<Mxfp4, NF, W, F, NT, MASKED, NoGroup, const uint8_t*, const uint8_t*>), grid,
+                       block, 0, s, static_cast<const uint8_t*>(A), static_cast<const uint8_t*>(B), c, M, N, K,
+                       NoGroup{}, static_cast<const uint8_t*>(sa), static_cast<const uint8_t*>(sb));
   }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail(e, who);
@@ -354,6 +428,145 @@ static int decode_pick(int N, int nk) {
   return nk >= 128 ? 3 : nk >= 64 ? 1 : 0;
 }
 
+// ---------------------------------------------------------------------------
+// The grouped form (gsx_moe_gemm_nt): host side
+// ---------------------------------------------------------------------------
+
+struct MoeGemmArgs {
+  int kind;
+  const void* A;
+  int a_div;
+  const void* B;
+  void* C;
+  const int32_t* plan;
+  int M, topk, E, N, K;
+  const void* sa;
+  const void* sb;
+  int mode;
+};
+
+static uint64_t moe_row_bytes(int kind, int K) {
+  return static_cast<uint64_t>(K) * (kind == GSX_DECODE_BF16 ? 16 : kind == GSX_DECODE_FP8 ? 8 : 4) / 8;
+}
+
+// Everything gsx_moe_gemm_nt and its _launch_cfg refuse, before the first device call.  `bn`: the columns of a strip.
+static int moe_gemm_validate(const char* who, int bn, const MoeGemmArgs& a) {
+  char msg[200];
+  auto refuse = [&](const char* rule) {
+    std::snprintf(msg, sizeof(msg), "%s: %s", who, rule);
+    return fail_arg(msg);
+  };
+  if (a.kind < 0 || a.kind >= kDecodeKinds) {
+    std::snprintf(msg, sizeof(msg), "%s: unknown kind %d", who, a.kind);
+    return fail_arg(msg);
+  }
+  if (a.M < 1 || a.M > 16) return refuse("need 1 <= M <= 16");
+  if (a.E < 1) return refuse("need E >= 1");
+  if (a.topk < 1 || a.topk > 8 || a.topk > a.E) return refuse("need 1 <= topk <= min(8, E)");
+  if (a.a_div < 1) return refuse("need a_div >= 1");
+  if (a.N <= 0 || a.N % bn || a.K <= 0 || a.K % kDecodeKTile[a.kind]) {
+    std::snprintf(msg, sizeof(msg), "%s: need N%%%d==0, K%%%d==0", who, bn, kDecodeKTile[a.kind]);
+    return fail_arg(msg);
+  }
+  if (!a.A || !a.B || !a.C || !a.plan) return refuse("A, B, C and plan must not be NULL");
+  if ((reinterpret_cast<uintptr_t>(a.A) | reinterpret_cast<uintptr_t>(a.B) | reinterpret_cast<uintptr_t>(a.C)) % 16)
+    return refuse("operands must be 16-B aligned");
+  if (reinterpret_cast<uintptr_t>(a.plan) % 4) return refuse("plan must be 4-B aligned");
+  const uintptr_t sbits = reinterpret_cast<uintptr_t>(a.sa) | reinterpret_cast<uintptr_t>(a.sb);
+  if (a.kind == GSX_DECODE_BF16) {
+    if (a.sa || a.sb || a.mode != GSX_GEMM_SCALE_NONE)
+      return refuse("bf16 takes no scales: scale_a and scale_b must be NULL and scale_mode NONE");
+  } else if (a.kind == GSX_DECODE_FP8) {
+    if (a.mode != GSX_GEMM_SCALE_NONE && a.mode != GSX_GEMM_SCALE_ROW)
+      return refuse("fp8 takes scale_mode NONE or ROW");
+    if (a.mode == GSX_GEMM_SCALE_ROW) {
+      if (!a.sa || !a.sb) return refuse("scale_a and scale_b must not be NULL in this scale_mode");
+      if (sbits % 4) return refuse("scale_a and scale_b must be 4-B aligned");
+    }
+  } else {
+    if (a.mode != GSX_GEMM_SCALE_NONE) return refuse("mxfp4 takes scale_mode NONE: its scales are the e8m0 blocks");
+    if (!a.sa || !a.sb) return refuse("scale_a and scale_b must not be NULL");
+    if (sbits % 16) return refuse("scale_a and scale_b must be 16-B aligned");
+  }
+  // A lane without a row reads at the end of the buffer over A, plus its place in the row: one row more than A has
+  // must fit the 32-bit range too.  scale_a's rows are 1 / 16 of A's.
+  const uint64_t P = static_cast<uint64_t>(a.M) * a.topk, a_rows = (P + a.a_div - 1) / a.a_div;
+  const uint64_t row = moe_row_bytes(a.kind, a.K);
+  if ((a_rows + 1) * row > UINT32_MAX) return refuse("A (and one row more) must fit a 32-bit buffer range");
+  struct Span {
+    const void* p;
+    uint64_t bytes;
+  };
+  const bool scaled = a.kind == GSX_DECODE_MXFP4 || a.mode == GSX_GEMM_SCALE_ROW;
+  const uint64_t en = static_cast<uint64_t>(a.E) * a.N, blocks = a.K / 32;
+  const Span c{a.C, P * a.N * 2};
+  const Span in[] = {{a.A, a_rows * row},
+                     {a.B, en * row},
+                     {a.plan, GSX_MOE_PLAN_INTS * 4ull},
+                     {scaled ? a.sa : nullptr, a.kind == GSX_DECODE_MXFP4 ? a_rows * blocks : a_rows * 4},
+                     {scaled ? a.sb : nullptr, a.kind == GSX_DECODE_MXFP4 ? en * blocks : en * 4}};
+  for (const Span& s : in) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(c.p), y = reinterpret_cast<uintptr_t>(s.p);
+    if (s.p && x < y + s.bytes && y < x + c.bytes) return refuse("C must not overlap A, B, plan, scale_a or scale_b");
+  }
+  return 0;
+}
+
+using moe_launch_t = int (*)(const char* who, hipStream_t s, const MoeGemmArgs& a);
+
+template <int KIND, int NF, int W, int F>
+int moe_launch(const char* who, hipStream_t s, const MoeGemmArgs& a) {
+  const int P = a.M * a.topk, a_rows = (P + a.a_div - 1) / a.a_div;
+  const dim3 grid(a.N / (NF * 16), a.E < P ? a.E : P), block(W * 64);
+  uint16_t* c = static_cast<uint16_t*>(a.C);
+  const MoePlan gp{a.plan, P, a.E, a.a_div, a_rows};
+  if constexpr (KIND == GSX_DECODE_BF16) {
+    hipLaunchKernelGGL((decode_kernel<Bf16, NF, W, F, false, false, MoePlan>), grid, block, 0, s,
+                       static_cast<const uint16_t*>(a.A), static_cast<const uint16_t*>(a.B), c, 0, a.N, a.K, gp);
+  } else if constexpr (KIND == GSX_DECODE_FP8) {
+    const bool scaled = a.mode != GSX_GEMM_SCALE_NONE;  // the kernel gets (nullptr, nullptr, 0) for no scales
+    hipLaunchKernelGGL((decode_kernel<Fp8K128, NF, W, F, false, false, MoePlan, const float*, const float*, int>),
+                       grid, block, 0, s, static_cast<const uint8_t*>(a.A), static_cast<const uint8_t*>(a.B), c, 0,
+                       a.N, a.K, gp, scaled ? static_cast<const float*>(a.sa) : nullptr,
+                       scaled ? static_cast<const float*>(a.sb) : nullptr, scaled ? 1 : 0);
+  } else {
+    hipLaunchKernelGGL((decode_kernel<Mxfp4, NF, W, F, false, false, MoePlan, const uint8_t*, const uint8_t*>),
+                       grid, block, 0, s, static_cast<const uint8_t*>(a.A), static_cast<const uint8_t*>(a.B), c, 0,
+                       a.N, a.K, gp, static_cast<const uint8_t*>(a.sa), static_cast<const uint8_t*>(a.sb));
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(e, who);
+}
+
+struct MoeCfg {
+  int decode;  // the row of kDecodeCfgs it equals: same NF, W and F, and so the same summation order
+  moe_launch_t launch[kDecodeKinds];
+};
+template <int NF, int W, int F>
+constexpr MoeCfg moe_cfg(int decode) {
+  return {decode,
+          {&moe_launch<GSX_DECODE_BF16, NF, W, F>, &moe_launch<GSX_DECODE_FP8, NF, W, F>,
+           &moe_launch<GSX_DECODE_MXFP4, NF, W, F>}};
+}
+// the four shapes decode_pick() dispatches to, under their names in kDecodeCfgs
+constexpr MoeCfg kMoeCfgs[] = {moe_cfg<1, 4, 4>(0), moe_cfg<1, 8, 4>(1), moe_cfg<1, 16, 4>(3), moe_cfg<2, 8, 4>(4)};
+constexpr int kNumMoeCfgs = sizeof(kMoeCfgs) / sizeof(kMoeCfgs[0]);
+
+static const MoeCfg* moe_row(int cfg) { return cfg >= 0 && cfg < kNumMoeCfgs ? &kMoeCfgs[cfg] : nullptr; }
+
+// decode_pick()'s rule, as a row of kMoeCfgs.  It was measured on dense 8192-wide matrices; what it does on expert
+// shapes is in profiles/moe/README.md.
+static const MoeCfg& moe_pick(int N, int nk) {
+  const int d = decode_pick(N, nk);
+  for (const MoeCfg& c : kMoeCfgs)
+    if (c.decode == d) return c;
+  return kMoeCfgs[0];
+}
+
+static int moe_gemm_run(const char* who, void* stream, const MoeGemmArgs& a) {
+  return moe_pick(a.N, a.K / kDecodeKTile[a.kind]).launch[a.kind](who, S(stream), a);
+}
+
 }  // namespace gsxgemm
 
 using namespace gsxgemm;
@@ -396,6 +609,42 @@ int gsx_event_time_decode_gemm(void* stream, int kind, const void* A, const void
   return event_time(stream, iters, ms, [&] {
     return gsx_decode_gemm_nt(stream, kind, A, B, C, M, N, K, scale_a, scale_b, scale_mode);
   });
+}
+
+const char* gsx_moe_gemm_cfg_name(int cfg) { return moe_row(cfg) ? kDecodeCfgs[moe_row(cfg)->decode].name : nullptr; }
+
+int gsx_moe_gemm_cfg_shape(int cfg, int* bn, int* waves, int* inflight, int* decode_cfg) {
+  const MoeCfg* c = moe_row(cfg);
+  if (!c) return -1;
+  *decode_cfg = c->decode;
+  return gsx_decode_gemm_cfg_shape(c->decode, bn, waves, inflight);
+}
+
+int gsx_moe_gemm_nt_launch_cfg(void* stream, int kind, const void* A, int a_div, const void* B, void* C,
+                               const int32_t* plan, int M, int topk, int E, int N, int K, const void* scale_a,
+                               const void* scale_b, int scale_mode, int cfg) {
+  const char* who = "gsx_moe_gemm_nt_launch_cfg";
+  const MoeCfg* c = moe_row(cfg);
+  if (!c) return fail_arg("gsx_moe_gemm_nt_launch_cfg: unknown config");
+  const MoeGemmArgs a{kind, A, a_div, B, C, plan, M, topk, E, N, K, scale_a, scale_b, scale_mode};
+  if (int rc = moe_gemm_validate(who, kDecodeCfgs[c->decode].bn, a)) return rc;
+  return c->launch[kind](who, S(stream), a);
+}
+
+int gsx_moe_gemm_nt(void* stream, int kind, const void* A, int a_div, const void* B, void* C, const int32_t* plan,
+                    int M, int topk, int E, int N, int K, const void* scale_a, const void* scale_b, int scale_mode) {
+  const MoeGemmArgs a{kind, A, a_div, B, C, plan, M, topk, E, N, K, scale_a, scale_b, scale_mode};
+  if (int rc = moe_gemm_validate("gsx_moe_gemm_nt", 16, a)) return rc;
+  return moe_gemm_run("gsx_moe_gemm_nt", stream, a);
+}
+
+int gsx_event_time_moe_gemm(void* stream, int kind, const void* A, int a_div, const void* B, void* C,
+                            const int32_t* plan, int M, int topk, int E, int N, int K, const void* scale_a,
+                            const void* scale_b, int scale_mode, int iters, float* ms) {
+  const MoeGemmArgs a{kind, A, a_div, B, C, plan, M, topk, E, N, K, scale_a, scale_b, scale_mode};
+  // refused before the events are made, under the name of the entry point that is timed
+  if (int rc = moe_gemm_validate("gsx_moe_gemm_nt", 16, a)) return rc;
+  return event_time(stream, iters, ms, [&] { return moe_gemm_run("gsx_moe_gemm_nt", stream, a); });
 }
 
 }  // extern "C"

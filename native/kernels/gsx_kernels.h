@@ -470,6 +470,94 @@ int gsx_event_time_sample(void* stream, const void* logits, int64_t logits_strid
 int gsx_event_time_embed_gather(void* stream, const void* table, int64_t table_stride, const int32_t* tokens,
                                 void* out, int64_t out_stride, int M, int H, int V, int iters, float* ms);
 
+// Mixture-of-experts decode (moe.hip, gemm_decode.hip): a router that picks topk of E experts per token, a grouped
+// GEMM that streams only the chosen experts' weights, and the weighted sum of a token's expert outputs.  Decode-sized:
+// 1 <= M <= 16 tokens and 1 <= topk <= 8, so at most P = M topk <= GSX_MOE_MAX_PAIRS (token, expert) pairs; pair
+// p = m topk + j is token m's j-th choice.  A token never picks an expert twice, so an expert has at most 16 rows: one
+// MFMA fragment of the decode kernel.  Ids, weights and the plan are device memory, written by one kernel and read by
+// the next: an MoE layer needs no host synchronisation.
+//
+// gsx_moe_route: logits[M][logits_stride] bf16, what gsx_decode_gemm_nt writes with N = E against the router matrix.
+// topk_ids[M][topk] int32, topk_w[M][topk] fp32, plan[GSX_MOE_PLAN_INTS] int32.  One launch of one workgroup.  Per row:
+//   selection  by the sampler's key (gsx_sample): the topk largest keys, ties to the lowest index; -0 is +0 and every
+//              NaN has one key below -inf.
+//   ids        topk_ids[m][j] in descending key order, the lowest index first among equal keys; j = 0 is `first`.
+//   weights    a softmax over the selected logits only (Mixtral, gpt-oss, Qwen3 with norm_topk_prob).  With l0 the
+//              logit at `first`: if l0 is not finite, w_0 = 1 and the others 0.  Otherwise
+//              p_j = exp2(fl(fl(l_j - l0) * fl32(log2 e))), p_j = 0 for a -inf or NaN l_j, and
+//              w_j = p_j / (p_0 + ... + p_{topk-1}), summed in the order of j.
+// Selection, ids and plan are exact (tests/moe_cases.py is their twin).  The weights have a bound, not bit-exactness,
+// as gsx_silu_mul: with x_j = l_j - l0 <= 0 and u = 2^-24 per correctly rounded fp32 operation, w_j lies within a
+// relative delta(x_j) = (3 |x_j| + 3.2 (topk - 1) + 4) u of the exact softmax weight wherever that is >= 2^-100, and
+// within 2^-99 absolute below.  Operation by operation:
+//   p_j    d = fl(l_j - l0): u.  fl32(log2 e) is within u of log2 e, and the multiply adds u: the argument t of the
+//          exponential is off by 3 u |t|, |t| = |x_j| log2 e, which 2^t turns into 3 u |x_j| ln 2 log2 e = 3 |x_j| u
+//          relative.  v_exp_f32: the ISA's documented 1 ulp, 2 u.  In all (3 |x_j| + 2) u; p_0 = 2^0 = 1 is exact, and
+//          so is every p_j with l_j = l0.
+//   sum    the exact sum of the computed p is off by sum_j p_j delta_j / sum_j p_j.  p_j <= e^x_j (1 + delta_j) and
+//          e^-|x| (3 |x| + 2) <= 2.15 (at |x| = 1 / 3), the sum is >= p_0 = 1, and p_0 carries no error: at most
+//          2.2 (topk - 1) u.  Its topk - 1 additions of positive terms: (topk - 1) u.  Together 3.2 (topk - 1) u.
+//   w_j    the division: u.  One more u covers the second-order terms of the products above.
+// A weight that these rules make exactly 0 or 1 is exactly that (topk = 1; a -inf or NaN logit; a non-finite l0).
+// The plan: a header {n_active, P, E, 0}, then slot_expert, slot_begin, slot_count and rows, GSX_MOE_MAX_PAIRS int32
+// each.  Slots 0 .. n_active - 1 are the experts that have at least one pair, in ascending expert index;
+// rows[slot_begin[s] .. + slot_count[s]) are that expert's pairs in ascending order, and the slots' runs tile
+// rows[0, P) in slot order.  Every unused slot is {-1, 0, 0} and every unused row -1: the whole buffer is defined, the
+// same size for every M.  No logit content makes the kernel write outside its three outputs, and every id it writes
+// lies in [0, E).
+// Requirements: 1 <= M <= 16; 8 <= E <= 1024 and E % 8 == 0; 1 <= topk <= min(8, E); logits_stride >= E and a
+// multiple of 8; every pointer non-NULL, logits 16-B aligned, the others 4-B aligned; the outputs overlap nothing.
+//
+// gsx_moe_gemm_nt: for every pair p of the plan, with e its slot's expert, C[p][0..N) = A[p / a_div][0..K) *
+// B[e][N][K]^T.  a_div = topk is the up projection (a pair reads its token's row of xn[M][K]), a_div = 1 the down
+// projection (a pair reads its own row of act[P][K]).  A has ceil(P / a_div) contiguous rows, C[P][N] is bf16 and
+// contiguous, B[E][N][K] are the experts' matrices back to back.  `kind` and the operand formats are those of
+// gsx_decode_gemm_nt.  GSX_DECODE_FP8 takes GSX_GEMM_SCALE_NONE, or GSX_GEMM_SCALE_ROW with scale_a one fp32 per row
+// of A (what GSX_ACT_OUT_FP8_ROW writes) and scale_b[E][N]; GSX_DECODE_MXFP4 takes scale_a[rows of A][K / 32] and
+// scale_b[E][N][K / 32].  The kernel is decode_kernel's body: workgroup (strip, slot), grid.y = min(E, P); a workgroup
+// whose slot is not active returns at once, so the host never learns n_active.  The summation order of a (row,
+// column) is that of the decode configuration of the same shape, so a pair's row of C has the bits that
+// gsx_decode_gemm_nt_launch_cfg gives for that row against that expert.  Inactive experts' weights are never read.
+// The plan is device memory anyone may have written, and no content of it makes the kernel read outside A, B or the
+// scales or write outside C: a slot whose expert is outside [0, E) is skipped, slot_count is clamped to [0, 16], an
+// index into rows outside [0, GSX_MOE_MAX_PAIRS) and a pair outside [0, P) are dropped (no load, no store).  The
+// same pair listed twice is a race between equal or unequal values: the caller's business.
+// Requirements: 1 <= M <= 16; E >= 1; 1 <= topk <= min(8, E); a_div >= 1; the K multiples of gsx_decode_gemm_nt and
+// N % 16 == 0; A, B, C and plan non-NULL, A, B and C 16-B aligned, plan 4-B aligned; the scales as above; A's rows and
+// one row more (where a lane without a pair points) fit a 32-bit buffer range, which is refused otherwise: there is no
+// masked form; C overlaps nothing.  Offsets into B, scale_b and C are 64-bit: B may exceed 4 GiB.
+// The configurations are a table of its own, the four shapes gsx_decode_gemm_nt dispatches to: 0 "16/4w-f4",
+// 1 "16/8w-f4", 2 "16/16w-f4", 3 "32/8w-f4"; _cfg_shape also gives the decode configuration each equals.
+// gsx_moe_gemm_nt picks by the decode GEMM's rule on (N, K).
+//
+// gsx_moe_combine: Y[P][y_stride] bf16 (the down projection's C), out[M][out_stride] bf16.  out[m][h] = bf16(acc),
+// acc = fl(w_0 y_0), then acc = fl(acc + fl(w_j y_j)) for j = 1 .. topk - 1, with y_j = Y[m topk + j][h] and
+// w_j = topk_w[m][j]: every fp32 operation rounded on its own, nothing contracted, one rounding to bf16.  Bit-exact
+// and fixed in order.  Requirements: 1 <= M <= 16; 1 <= topk <= 8; H >= 8 and H % 8 == 0; each stride >= H and a
+// multiple of 8; pointers non-NULL, Y and out 16-B aligned, topk_w 4-B aligned; out overlaps nothing.
+// Everything is validated before the first device call; every launch is on `stream` and returns without synchronising.
+#define GSX_MOE_MAX_PAIRS 128
+#define GSX_MOE_PLAN_INTS (4 + 4 * GSX_MOE_MAX_PAIRS)  // 516
+int gsx_moe_route(void* stream, const void* logits, int64_t logits_stride, int32_t* topk_ids, float* topk_w,
+                  int32_t* plan, int M, int E, int topk);
+int gsx_moe_gemm_nt(void* stream, int kind, const void* A, int a_div, const void* B, void* C, const int32_t* plan,
+                    int M, int topk, int E, int N, int K, const void* scale_a, const void* scale_b, int scale_mode);
+const char* gsx_moe_gemm_cfg_name(int cfg);
+int gsx_moe_gemm_cfg_shape(int cfg, int* bn, int* waves, int* inflight, int* decode_cfg);
+int gsx_moe_gemm_nt_launch_cfg(void* stream, int kind, const void* A, int a_div, const void* B, void* C,
+                               const int32_t* plan, int M, int topk, int E, int N, int K, const void* scale_a,
+                               const void* scale_b, int scale_mode, int cfg);
+int gsx_moe_combine(void* stream, const void* Y, int64_t y_stride, const float* topk_w, void* out, int64_t out_stride,
+                    int M, int topk, int H);
+// elapsed milliseconds of `iters` back-to-back calls on `stream`, by hip events (for benches)
+int gsx_event_time_moe_route(void* stream, const void* logits, int64_t logits_stride, int32_t* topk_ids, float* topk_w,
+                             int32_t* plan, int M, int E, int topk, int iters, float* ms);
+int gsx_event_time_moe_gemm(void* stream, int kind, const void* A, int a_div, const void* B, void* C,
+                            const int32_t* plan, int M, int topk, int E, int N, int K, const void* scale_a,
+                            const void* scale_b, int scale_mode, int iters, float* ms);
+int gsx_event_time_moe_combine(void* stream, const void* Y, int64_t y_stride, const float* topk_w, void* out,
+                               int64_t out_stride, int M, int topk, int H, int iters, float* ms);
+
 // HBM pre-flight memory test (memtest.hip).  The expected content of 16-byte word W = origin/16 + word index is
 // generated from (pattern, seed, invert, W) and never stored; `origin` is the byte offset of `base` in the whole
 // tested range, so a range tested chunk by chunk keeps globally unique content.

@@ -28,6 +28,7 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "bf16_key.h"
 #include "gemm_tile.h"
 #include "gsx_internal.h"
 #include "gsx_kernels.h"
@@ -57,13 +58,6 @@ struct SmShared {
   int found;
   uint32_t n;
 };
-
-// The 16-bit key that orders bf16 codes: -0 is +0, every NaN is 0, below -inf (0x007f).
-__device__ __forceinline__ uint32_t sm_key(uint32_t b) {
-  if ((b & 0x7fffu) > 0x7f80u) return 0u;
-  if (b == 0x8000u) return 0x8000u;
-  return (b & 0x8000u) ? (~b & 0xffffu) : (b | 0x8000u);
-}
 
 // The integer weight of a logit (its bf16 code) against the row's maximum lf: trunc(g(f) * 2^(32 + n)).
 __device__ __forceinline__ uint64_t sm_weight(uint32_t bits, float lf, float c) {

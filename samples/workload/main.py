@@ -162,6 +162,52 @@ def layer_weight_bytes(heads: int, kv_heads: int, ffn: int) -> int:
     return server_layer_weight_bytes(heads, kv_heads) + 3 * ffn * heads * ATTN_D * 2
 
 
+MOE_MAX_EXPERTS = 1024
+MOE_MAX_ACTIVE = 8
+MOE_PLAN_INTS = 516  # GSX_MOE_PLAN_INTS
+
+
+def moe_expert_bytes(heads: int, ffn: int) -> int:
+    """Bytes of one expert's bf16 weights: its gate / up projection ``[2 ffn][hidden]`` and its down projection
+    ``[hidden][ffn]``."""
+    return 3 * ffn * heads * ATTN_D * 2
+
+
+def moe_layer_weight_bytes(heads: int, kv_heads: int, ffn: int, experts: int) -> int:
+    """Bytes of one MoE decoder layer's bf16 weights as they are resident: the server layer's two projections, the
+    router ``[experts][hidden]`` and ``experts`` experts of width ``ffn``.  A step reads only the experts it hits
+    (:func:`moe_layer_read_bytes`)."""
+    return (server_layer_weight_bytes(heads, kv_heads) + experts * heads * ATTN_D * 2
+            + experts * moe_expert_bytes(heads, ffn))
+
+
+def moe_layer_read_bytes(heads: int, kv_heads: int, ffn: int, experts: int, hit: float) -> float:
+    """Bytes of weights one MoE layer reads in a step that hits ``hit`` of its experts: the dense part and the router
+    whole, and the hit experts."""
+    return (server_layer_weight_bytes(heads, kv_heads) + experts * heads * ATTN_D * 2
+            + hit * moe_expert_bytes(heads, ffn))
+
+
+def moe_active(experts: int, experts_active: int) -> int:
+    """The experts a token picks: ``--experts-active``, capped at ``--experts``."""
+    return min(experts_active, experts)
+
+
+def moe_refusal(workload: str, experts: int, experts_active: int) -> str | None:
+    """Why ``--experts`` cannot run with these options, or None: known before anything touches the device."""
+    if experts == 0:
+        return None
+    if workload == "prefill":
+        return "--workload prefill --experts: more than 16 rows needs a grouped large GEMM, which there is none of"
+    if workload not in ("layer", "generate"):
+        return f"--experts {experts}: --workload layer and generate only"
+    if not 16 <= experts <= MOE_MAX_EXPERTS or experts % 16:
+        return f"--experts {experts}: 0, or a multiple of 16 in 16..{MOE_MAX_EXPERTS} (the router is the decode GEMM)"
+    if not 1 <= experts_active <= MOE_MAX_ACTIVE:
+        return f"--experts-active {experts_active}: 1..{MOE_MAX_ACTIVE}"
+    return None
+
+
 def prefill_refusal(batch: int, chunk: int, context: int) -> str | None:
     """Why ``--workload prefill`` cannot run these sizes, or None: known before anything touches the device."""
     if chunk < 1:
@@ -232,6 +278,21 @@ class Kernels:
             L.gsx_event_time_embed_gather.argtypes = [*L.gsx_embed_gather.argtypes, i32, fp]
             L.gsx_sample.restype = L.gsx_embed_gather.restype = i32
             L.gsx_event_time_sample.restype = L.gsx_event_time_embed_gather.restype = i32
+        if hasattr(L, "gsx_moe_route"):  # likewise: an image built before the MoE kernels
+            i64, fp, ip = ctypes.c_int64, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i32)
+            L.gsx_moe_route.argtypes = [vp, vp, i64, vp, vp, vp, i32, i32, i32]
+            L.gsx_moe_gemm_nt.argtypes = [vp, i32, vp, i32, vp, vp, vp] + [i32] * 5 + [vp, vp, i32]
+            L.gsx_moe_gemm_nt_launch_cfg.argtypes = [*L.gsx_moe_gemm_nt.argtypes, i32]
+            L.gsx_moe_combine.argtypes = [vp, vp, i64, vp, vp, i64, i32, i32, i32]
+            L.gsx_moe_gemm_cfg_name.argtypes, L.gsx_moe_gemm_cfg_name.restype = [i32], ctypes.c_char_p
+            L.gsx_moe_gemm_cfg_shape.argtypes = [i32, ip, ip, ip, ip]
+            L.gsx_event_time_moe_route.argtypes = [*L.gsx_moe_route.argtypes, i32, fp]
+            L.gsx_event_time_moe_gemm.argtypes = [*L.gsx_moe_gemm_nt.argtypes, i32, fp]
+            L.gsx_event_time_moe_combine.argtypes = [*L.gsx_moe_combine.argtypes, i32, fp]
+            for f in (L.gsx_moe_route, L.gsx_moe_gemm_nt, L.gsx_moe_gemm_nt_launch_cfg, L.gsx_moe_combine,
+                      L.gsx_moe_gemm_cfg_shape, L.gsx_event_time_moe_route, L.gsx_event_time_moe_gemm,
+                      L.gsx_event_time_moe_combine):
+                f.restype = i32
         L.gsx_last_error.argtypes, L.gsx_last_error.restype = [], ctypes.c_char_p
         self.L, self.path = L, path
 
@@ -366,6 +427,73 @@ class Kernels:
         ms = ctypes.c_float(0)
         self._ck(self.L.gsx_event_time_embed_gather(*self._embed_args(s, table, tokens, out, m, h, v), iters,
                                                     ctypes.byref(ms)), "time_embed_gather")
+        return ms.value
+
+    def _moe_route_args(self, s, logits: int, ids: int, w: int, plan: int, m: int, e: int, topk: int) -> tuple:
+        if not hasattr(self.L, "gsx_moe_route"):
+            raise RuntimeError(f"{self.path} has no gsx_moe_route: rebuild it")
+        return (s, ctypes.c_void_p(logits), e, *(ctypes.c_void_p(x) for x in (ids, w, plan)), m, e, topk)
+
+    def moe_route(self, s, logits: int, ids: int, w: int, plan: int, m: int, e: int, topk: int):
+        """From ``logits[m][e]`` (bf16, contiguous rows): ``ids[m][topk]`` int32, ``w[m][topk]`` fp32 and the plan of
+        ``MOE_PLAN_INTS`` int32 that groups the pairs by expert, all in device memory."""
+        self._ck(self.L.gsx_moe_route(*self._moe_route_args(s, logits, ids, w, plan, m, e, topk)), "moe_route")
+
+    def time_moe_route(self, s, logits: int, ids: int, w: int, plan: int, m: int, e: int, topk: int,
+                       iters: int) -> float:
+        ms = ctypes.c_float(0)
+        self._ck(self.L.gsx_event_time_moe_route(*self._moe_route_args(s, logits, ids, w, plan, m, e, topk), iters,
+                                                 ctypes.byref(ms)), "time_moe_route")
+        return ms.value
+
+    def _moe_gemm_args(self, s, dtype: str, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                       n: int, k: int, sa: int, sb: int, mode: int) -> tuple:
+        if not hasattr(self.L, "gsx_moe_gemm_nt"):
+            raise RuntimeError(f"{self.path} has no gsx_moe_gemm_nt: rebuild it")
+        return (s, DECODE_KINDS[dtype], ctypes.c_void_p(a), a_div, ctypes.c_void_p(b), ctypes.c_void_p(c),
+                ctypes.c_void_p(plan), m, topk, e, n, k, ctypes.c_void_p(sa), ctypes.c_void_p(sb), mode)
+
+    def moe_gemm_nt(self, s, dtype: str, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                    n: int, k: int, sa: int = 0, sb: int = 0, mode: int = 0):
+        """``c[p][n] = a[p // a_div][k] * b[expert of p][n][k]^T`` for every pair ``p`` of the plan."""
+        self._ck(self.L.gsx_moe_gemm_nt(*self._moe_gemm_args(s, dtype, a, a_div, b, c, plan, m, topk, e, n, k, sa, sb,
+                                                             mode)), "moe_gemm_nt")
+
+    def moe_gemm_cfgs(self) -> dict[int, tuple[str, int, int, int, int]]:
+        """``{index: (name, bn, waves, inflight, decode_cfg)}`` of the grouped GEMM's table."""
+        out: dict[int, tuple[str, int, int, int, int]] = {}
+        while (name := self.L.gsx_moe_gemm_cfg_name(len(out))) is not None:
+            v = [ctypes.c_int(0) for _ in range(4)]
+            self._ck(self.L.gsx_moe_gemm_cfg_shape(len(out), *map(ctypes.byref, v)), "moe_gemm_cfg_shape")
+            out[len(out)] = (name.decode(), *(x.value for x in v))
+        return out
+
+    def moe_gemm_nt_cfg(self, s, dtype: str, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                        n: int, k: int, cfg: int, sa: int = 0, sb: int = 0, mode: int = 0):
+        self._ck(self.L.gsx_moe_gemm_nt_launch_cfg(*self._moe_gemm_args(s, dtype, a, a_div, b, c, plan, m, topk, e, n,
+                                                                        k, sa, sb, mode), cfg), f"moe gemm cfg {cfg}")
+
+    def time_moe_gemm(self, s, dtype: str, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                      n: int, k: int, iters: int, sa: int = 0, sb: int = 0, mode: int = 0) -> float:
+        ms = ctypes.c_float(0)
+        self._ck(self.L.gsx_event_time_moe_gemm(*self._moe_gemm_args(s, dtype, a, a_div, b, c, plan, m, topk, e, n, k,
+                                                                     sa, sb, mode), iters, ctypes.byref(ms)),
+                 "time_moe_gemm")
+        return ms.value
+
+    def _moe_combine_args(self, s, y: int, w: int, out: int, m: int, topk: int, h: int) -> tuple:
+        if not hasattr(self.L, "gsx_moe_combine"):
+            raise RuntimeError(f"{self.path} has no gsx_moe_combine: rebuild it")
+        return (s, ctypes.c_void_p(y), h, ctypes.c_void_p(w), ctypes.c_void_p(out), h, m, topk, h)
+
+    def moe_combine(self, s, y: int, w: int, out: int, m: int, topk: int, h: int):
+        """``out[m][h]`` = the sum over ``j`` of ``w[m][j] * y[m topk + j][h]``: bf16, contiguous rows."""
+        self._ck(self.L.gsx_moe_combine(*self._moe_combine_args(s, y, w, out, m, topk, h)), "moe_combine")
+
+    def time_moe_combine(self, s, y: int, w: int, out: int, m: int, topk: int, h: int, iters: int) -> float:
+        ms = ctypes.c_float(0)
+        self._ck(self.L.gsx_event_time_moe_combine(*self._moe_combine_args(s, y, w, out, m, topk, h), iters,
+                                                   ctypes.byref(ms)), "time_moe_combine")
         return ms.value
 
     def sync(self, s):
@@ -576,12 +704,18 @@ LAYER_EPS = 1e-5
 
 
 def layer_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, heads: int, kv_heads: int, page: int,
-                ffn: int, w_layers: int, kv_layers: int):
+                ffn: int, w_layers: int, kv_layers: int, experts: int = 0, active: int = 0):
     """``(step, sync, finite)`` of the layer workload: :func:`server_steps` with a residual stream, the two
     normalisations and the MLP.  A ring of ``w_layers`` decoder layers' bf16 weights (random normal over the square
     root of the input width; norm weights of 1), a ring of ``kv_layers`` paged KV caches, and a step that runs
     ``max(w_layers, kv_layers)`` layers back to back on the library's stream.  Layer 0 takes the constant input with
-    no residual and writes the residual buffer; every later add updates it in place."""
+    no residual and writes the residual buffer; every later add updates it in place.
+
+    With ``experts`` > 0 the MLP is a mixture of experts of width ``ffn``, of which a token picks ``active``: the
+    router (the decode GEMM with N = ``experts``), ``moe_route``, the grouped up projection, SwiGLU on the
+    ``batch * active`` pairs, the grouped down projection and ``moe_combine``, with ids, weights and plan in device
+    memory and one plan buffer per layer of the step.  ``step.hits()`` synchronises and returns every layer's
+    ``n_active`` of the last step."""
     hidden, nqkv = heads * ATTN_D, (heads + 2 * kv_heads) * ATTN_D
     per_seq, pages = kv_pages(batch, context, page)
     window = server_window(context)
@@ -589,11 +723,16 @@ def layer_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, hea
     bf = torch.bfloat16
     wqkv = torch.empty(w_layers, nqkv, hidden, device=dev, dtype=bf)
     wo = torch.empty(w_layers, hidden, hidden, device=dev, dtype=bf)
-    wgu = torch.empty(w_layers, 2 * ffn, hidden, device=dev, dtype=bf)
-    wdown = torch.empty(w_layers, hidden, ffn, device=dev, dtype=bf)
+    nexp, pairs = max(experts, 1), batch * max(active, 1)  # a dense MLP is one expert that every row takes once
+    wgu = torch.empty(w_layers, nexp * 2 * ffn, hidden, device=dev, dtype=bf)
+    wdown = torch.empty(w_layers, nexp * hidden, ffn, device=dev, dtype=bf)
+    router = torch.empty(w_layers, experts, hidden, device=dev, dtype=bf)
     for i in range(w_layers):  # one matrix at a time: nothing larger is ever held in fp32
-        for w, k in ((wqkv, hidden), (wo, hidden), (wgu, hidden), (wdown, ffn)):
+        for w, k in ((wqkv, hidden), (wo, hidden), (router, hidden)):
             w[i].copy_(torch.randn(w.shape[1], k, device=dev) / math.sqrt(k))
+        for w, rows, k in ((wgu, 2 * ffn, hidden), (wdown, hidden, ffn)):
+            for e in range(nexp):
+                w[i, e * rows:(e + 1) * rows].copy_(torch.randn(rows, k, device=dev) / math.sqrt(k))
     ln = torch.ones(w_layers, 2, hidden, device=dev, dtype=bf)
     kdt = bf if kv_dtype == "bf16" else torch.float8_e4m3fn
     kc = torch.empty(kv_layers, pages, kv_heads, page, ATTN_D, device=dev, dtype=kdt)
@@ -612,11 +751,16 @@ def layer_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, hea
     qkv = torch.empty(batch, nqkv, device=dev, dtype=bf)
     q = torch.empty(batch, heads, ATTN_D, device=dev, dtype=bf)
     o = torch.empty_like(q)
-    gu = torch.empty(batch, 2 * ffn, device=dev, dtype=bf)
-    act = torch.empty(batch, ffn, device=dev, dtype=bf)
+    gu = torch.empty(pairs, 2 * ffn, device=dev, dtype=bf)
+    act = torch.empty(pairs, ffn, device=dev, dtype=bf)
+    rlogits = torch.empty(batch, experts, device=dev, dtype=bf)
+    ids = torch.empty(pairs, device=dev, dtype=torch.int32)
+    tw = torch.empty(pairs, device=dev, dtype=torch.float32)
+    yexp = torch.empty(pairs, hidden, device=dev, dtype=bf)
+    plans = torch.zeros(layers if experts else 0, MOE_PLAN_INTS, device=dev, dtype=torch.int32)
     ws_bytes = kl.attn_workspace_bytes(batch, heads, page, context)
     ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
-    wqkv_b, wo_b, wgu_b, wdown_b = (w[0].numel() * 2 for w in (wqkv, wo, wgu, wdown))
+    wqkv_b, wo_b, wgu_b, wdown_b, router_b = (w[0].numel() * 2 for w in (wqkv, wo, wgu, wdown, router))
     cache_bytes = kc[0].numel() * kc.element_size()
     scale = 1.0 / math.sqrt(ATTN_D)
     torch.cuda.synchronize()
@@ -646,22 +790,40 @@ def layer_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, hea
             kl.decode_gemm(gs, "bf16", o.data_ptr(), wo.data_ptr() + wi * wo_b, sub.data_ptr(), batch, hidden, hidden)
             kl.add_rmsnorm(gs, sub.data_ptr(), resid.data_ptr(), resid.data_ptr(), ln1 + hidden * 2, xn.data_ptr(),
                            batch, hidden, LAYER_EPS)
-            kl.decode_gemm(gs, "bf16", xn.data_ptr(), wgu.data_ptr() + wi * wgu_b, gu.data_ptr(), batch, 2 * ffn,
-                           hidden)
-            kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), batch, ffn)
-            kl.decode_gemm(gs, "bf16", act.data_ptr(), wdown.data_ptr() + wi * wdown_b, sub.data_ptr(), batch, hidden,
-                           ffn)
+            if not experts:
+                kl.decode_gemm(gs, "bf16", xn.data_ptr(), wgu.data_ptr() + wi * wgu_b, gu.data_ptr(), batch, 2 * ffn,
+                               hidden)
+                kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), batch, ffn)
+                kl.decode_gemm(gs, "bf16", act.data_ptr(), wdown.data_ptr() + wi * wdown_b, sub.data_ptr(), batch,
+                               hidden, ffn)
+                continue
+            plan = plans.data_ptr() + i * MOE_PLAN_INTS * 4
+            kl.decode_gemm(gs, "bf16", xn.data_ptr(), router.data_ptr() + wi * router_b, rlogits.data_ptr(), batch,
+                           experts, hidden)
+            kl.moe_route(gs, rlogits.data_ptr(), ids.data_ptr(), tw.data_ptr(), plan, batch, experts, active)
+            kl.moe_gemm_nt(gs, "bf16", xn.data_ptr(), active, wgu.data_ptr() + wi * wgu_b, gu.data_ptr(), plan, batch,
+                           active, experts, 2 * ffn, hidden)
+            kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), pairs, ffn)
+            kl.moe_gemm_nt(gs, "bf16", act.data_ptr(), 1, wdown.data_ptr() + wi * wdown_b, yexp.data_ptr(), plan,
+                           batch, active, experts, hidden, ffn)
+            kl.moe_combine(gs, yexp.data_ptr(), tw.data_ptr(), sub.data_ptr(), batch, active, hidden)
 
     def sync():
         kl.sync(gs)
 
     def finite():
         kl.sync(gs)
-        return all(bool(torch.isfinite(t.float()).all()) for t in (resid, xn, sub, qkv, q, o, gu, act))
+        moe = (rlogits, tw, yexp) if experts else ()
+        return all(bool(torch.isfinite(t.float()).all()) for t in (resid, xn, sub, qkv, q, o, gu, act, *moe))
 
+    def hits():
+        kl.sync(gs)
+        return plans[:, 0].tolist()
+
+    step.hits = hits
     # the closures hold addresses, not tensors
-    step.keep = (wqkv, wo, wgu, wdown, ln, kc, vc, table, start, lens, cos, sin, x0, resid, xn, sub, qkv, q, o, gu, act,
-                 ws)
+    step.keep = (wqkv, wo, wgu, wdown, router, ln, kc, vc, table, start, lens, cos, sin, x0, resid, xn, sub, qkv, q, o,
+                 gu, act, ws, rlogits, ids, tw, yexp, plans)
     step.io = {"x0": x0, "resid": resid, "sub": sub, "xn": xn}  # what the generate workload puts around the layers
     return step, sync, finite
 
@@ -686,7 +848,7 @@ def generate_step_bytes(layers: int, one_layer_bytes: int, kv_bytes: int, batch:
 
 def generate_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, heads: int, kv_heads: int, page: int,
                    ffn: int, w_layers: int, kv_layers: int, vocab: int, temperature: float, top_k: int, top_p: float,
-                   seed: int):
+                   seed: int, experts: int = 0, active: int = 0):
     """``(step, sync, finite, tokens)`` of the generate workload: a step of :func:`layer_steps` between the embedding
     lookup of the previous step's tokens and the final norm, the LM head (the decode GEMM with N = ``vocab``) and the
     sampler, which writes the other of two token buffers.  The tokens go from step to step through device memory;
@@ -694,7 +856,7 @@ def generate_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, 
     hidden = heads * ATTN_D
     bf = torch.bfloat16
     layers, sync, layers_finite = layer_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, kv_heads, page, ffn,
-                                              w_layers, kv_layers)
+                                              w_layers, kv_layers, experts, active)
     io = layers.io
     embed = torch.randn(vocab, hidden, device=dev, dtype=bf)
     head = torch.empty(vocab, hidden, device=dev, dtype=bf)
@@ -728,6 +890,7 @@ def generate_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, 
         kl.sync(gs)
         return tokens[count[0] % 2].tolist()
 
+    step.hits = layers.hits
     step.keep = (layers, embed, head, lnf, logits, tokens, temp, topk, topp, seeds)
     return step, sync, finite, last_tokens
 
@@ -814,7 +977,9 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         weights_gib: float | None = None, context: int = 8192, heads: int = 64, kv_heads: int = 8,
         kv_dtype: str = "bf16", kv_gib: float | None = None, page: int = 16, ffn: int | None = None,
         chunk: int = 2048, vocab: int = 128256, temperature: float = 0.8, top_k: int = 50, top_p: float = 0.95,
-        seed: int = 0) -> dict:
+        seed: int = 0, experts: int = 0, experts_active: int = MOE_MAX_ACTIVE) -> dict:
+    if why := moe_refusal(workload, experts, experts_active):
+        raise SystemExit(why)
     if workload == "prefill" and (why := prefill_refusal(batch, chunk, context)):
         raise SystemExit(f"--workload prefill: {why}")
     if workload == "generate" and (why := generate_refusal(batch, vocab)):
@@ -917,7 +1082,9 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
                                + 4.0 * ATTN_D * heads * prefill_visible_pairs(batch, chunk, context))
     elif server:
         weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
-        one_layer_bytes = (layer_weight_bytes(heads, kv_heads, ffn) if layer
+        active = moe_active(experts, experts_active)
+        one_layer_bytes = (moe_layer_weight_bytes(heads, kv_heads, ffn, experts) if experts
+                           else layer_weight_bytes(heads, kv_heads, ffn) if layer
                            else server_layer_weight_bytes(heads, kv_heads))
         w_layers = ring_layers(weights_bytes, one_layer_bytes)
         kv_layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB),
@@ -926,15 +1093,18 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         if generate:
             step, sync, finite, last_tokens = generate_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads,
                                                              kv_heads, page, ffn, w_layers, kv_layers, vocab,
-                                                             temperature, top_k, top_p, seed)
+                                                             temperature, top_k, top_p, seed, experts, active)
         elif layer:
             step, sync, finite = layer_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, kv_heads, page, ffn,
-                                             w_layers, kv_layers)
+                                             w_layers, kv_layers, experts, active)
         else:
             step, sync, finite = server_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, kv_heads, page,
                                               w_layers, kv_layers)
         # the projections (2 flops per weight and row: a weight is 2 bytes), and QK^T and PV over the context
         flops_attn = layers * (batch * one_layer_bytes + 4.0 * batch * heads * context * ATTN_D)
+        if experts:  # a row meets the dense part, the router and its `active` experts
+            flops_attn = layers * (batch * moe_layer_read_bytes(heads, kv_heads, ffn, experts, active)
+                                   + 4.0 * batch * heads * context * ATTN_D)
         if generate:  # the LM head
             flops_attn += 2.0 * batch * vocab * heads * ATTN_D
     elif attn:
@@ -1034,8 +1204,17 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
                     "activations_finite": finite()})
         if layer:
             out["ffn"] = ffn
+        if experts:
+            # what a step reads depends on its routing: the weights are counted for the experts the last step hit
+            hits = step.hits()
+            read_bytes = sum(moe_layer_read_bytes(heads, kv_heads, ffn, experts, h) for h in hits) / len(hits)
+            step_bytes = layers * (read_bytes + kv_layer_bytes(kv_dtype, batch, context, kv_heads))
+            out.update({"experts": experts, "experts_active": active, "experts_hit_mean": sum(hits) / len(hits),
+                        "tbps": done * step_bytes / el / 1e12,
+                        "tbps_basis": "the experts hit by the last step's routing, taken for every step"})
         if generate:
-            step_bytes = generate_step_bytes(layers, one_layer_bytes, kv_layer_bytes(kv_dtype, batch, context, kv_heads),
+            one_read = read_bytes if experts else one_layer_bytes
+            step_bytes = generate_step_bytes(layers, one_read, kv_layer_bytes(kv_dtype, batch, context, kv_heads),
                                              batch, heads * ATTN_D, vocab)
             out.update({"vocab": vocab, "temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed,
                         "bytes_per_step": step_bytes, "tbps": done * step_bytes / el / 1e12,
@@ -1074,6 +1253,8 @@ class _Parser(argparse.ArgumentParser):
             self.error(f"argument --batch: {ns.batch} is not in 1..{top} (--workload {ns.workload})")
         if ns.workload == "generate" and (why := generate_refusal(ns.batch, ns.vocab)):
             self.error(f"--workload generate: {why}")
+        if why := moe_refusal(ns.workload, getattr(ns, "experts", 0), getattr(ns, "experts_active", MOE_MAX_ACTIVE)):
+            self.error(why)
         if ns.workload == "prefill":
             # --context means something else here, the length AFTER the chunk, and the chunk's place follows from it:
             # the other workloads' default is not taken over silently
@@ -1114,6 +1295,15 @@ def add_generate_arguments(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--seed", type=int, default=0, help="--workload generate: row r draws with seed + r")
 
 
+def add_moe_arguments(ap: argparse.ArgumentParser) -> None:
+    """The options of the MoE form of ``--workload layer`` and ``generate`` (shared with the isolation harness)."""
+    ap.add_argument("--experts", type=int, default=0,
+                    help="--workload layer and generate: experts of the MLP, each --ffn wide (0: a dense MLP; otherwise "
+                         "a multiple of 16 up to 1024)")
+    ap.add_argument("--experts-active", type=int, default=MOE_MAX_ACTIVE,
+                    help="--experts > 0: experts a token picks, 1..8, capped at --experts")
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = os.environ.get("GSX_ENV_PREFIX", "SHARED_GPU_MEM")
     ap = _Parser(description="GEMM loop inside the pod's GPU share (the gpushare sample workload)")
@@ -1148,6 +1338,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--ffn", type=int, default=None,
                     help="--workload layer and prefill: width of the MLP (default 3.5 x hidden, rounded to a multiple of 64)")
     add_generate_arguments(ap)
+    add_moe_arguments(ap)
     ap.add_argument("--seconds", type=float, default=0.0, help="0 = run forever (like the reference sample)")
     ap.add_argument("--iters", type=int, default=0)
     ap.add_argument("--touch", action="store_true")
@@ -1162,7 +1353,7 @@ def main(argv=None) -> int:
               quiet=a.json, probe_limit=a.probe_limit, dtype=a.dtype, workload=a.workload, batch=a.batch,
               weights_gib=a.weights_gib, context=a.context, heads=a.heads, kv_heads=a.kv_heads, kv_dtype=a.kv_dtype,
               kv_gib=a.kv_gib, page=a.page, ffn=a.ffn, chunk=a.chunk, vocab=a.vocab, temperature=a.temperature,
-              top_k=a.top_k, top_p=a.top_p, seed=a.seed)
+              top_k=a.top_k, top_p=a.top_p, seed=a.seed, experts=a.experts, experts_active=a.experts_active)
     print(json.dumps(res) if a.json else res, flush=True)
     return 0
 

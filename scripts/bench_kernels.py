@@ -3,8 +3,10 @@
 GEMM (every configuration vs torch and a read-bandwidth yardstick), the decode attention over a paged KV cache (every
 configuration and split count vs torch SDPA and the same yardstick), RoPE + KV append and the fused add + RMSNorm and
 SwiGLU (vs a read-and-rewrite yardstick), the causal prefill attention over the paged cache (vs torch SDPA on a
-contiguous copy), HBM fill, stamp/verify."""
+contiguous copy), the sampler, the MoE router, grouped expert GEMM and combine (vs one plain decode GEMM per active
+expert and the read yardstick), HBM fill, stamp/verify."""
 import json
+import math
 import os
 import statistics
 import sys
@@ -860,6 +862,199 @@ def sample(vocabs=SAMPLE_VOCABS, rows=SAMPLE_ROWS, hidden=8192, iters=50, gemm_i
     return out
 
 
+MOE_SHAPES = [(2048, 768, 128, 8), (4096, 14336, 8, 2), (7168, 2048, 256, 8)]  # (hidden, ffn, experts, topk)
+
+
+def moe(shapes=MOE_SHAPES, ms=(1, 8, 16), kinds=("bf16", "fp8", "mxfp4"), ring_bytes=(2 << 30) + 1, reps=3, rounds=3):
+    """The MoE decode kernels by the protocol of :func:`gemm_decode`: rings of expert tensors of more than 2 GiB for
+    the up projection ``[E][2 ffn][hidden]`` and for the down projection ``[E][hidden][ffn]``, ``reps`` passes over a
+    ring between two events, the median of ``rounds`` repeats after a warm-up and their spread, the variants
+    interleaved in one process.  Routing comes from random router weights and inputs through ``moe_route`` and is the
+    same for every layer of the ring; ``n_active`` is recorded.  Per row and projection, TB/s over the ACTIVE experts'
+    weight and scale bytes for every grouped configuration, the dispatching entry point (``gsx``), one plain
+    ``decode_gemm_nt`` per active expert with the routing known in advance and the rows gathered beforehand
+    (``per_expert``: what the library offered before, without the host synchronisation it would need), and
+    ``gsx_memtest_check`` over the same number of bytes.  ``route_us`` and ``combine_us`` are per call; ``mlp_us`` is
+    the whole bf16 MoE MLP of one layer (route, up, SwiGLU, down, combine) over the ring."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    unit = {"bf16": 2.0, "fp8": 1.0, "mxfp4": 0.5 + 1 / 32}
+    wdt = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn, "mxfp4": torch.uint8}
+
+    def operand(kind, rows, k):
+        """``(tensor, scales or None)``: random normal bf16 / e4m3, or bf16 quantised to MXFP4 by the library."""
+        x = torch.randn(rows, k, device="cuda", dtype=torch.bfloat16)
+        if kind != "mxfp4":
+            return x.to(wdt[kind]), None
+        q = torch.empty(rows, k // 2, device="cuda", dtype=torch.uint8)
+        sc = torch.empty(rows, k // 32, device="cuda", dtype=torch.uint8)
+        torch.cuda.synchronize()
+        hip.quant_mxfp4(s, x.data_ptr(), q.data_ptr(), sc.data_ptr(), rows, k)
+        s.sync()
+        return q, sc
+
+    for hidden, ffn, e, topk in shapes:
+        gen = torch.Generator(device="cuda").manual_seed(hidden + e)
+        rw = torch.randn(e, hidden, device="cuda", generator=gen) / math.sqrt(hidden)
+        for kind in kinds:
+            if (kind == "mxfp4" and (hidden % 256 or ffn % 256)) or (kind == "fp8" and (hidden % 128 or ffn % 128)):
+                continue
+            proj = {"up": (2 * ffn, hidden), "down": (hidden, ffn)}  # name: (N, K)
+            ring = {}
+            for name, (n, k) in proj.items():
+                per = int(e * n * k * unit[kind])
+                layers = max(2, -(-ring_bytes // per))
+                wcols = k // 2 if kind == "mxfp4" else k
+                w = torch.empty(layers, e * n, wcols, device="cuda", dtype=wdt[kind])
+                ws = torch.empty(layers, e * n, k // 32, device="cuda", dtype=torch.uint8) if kind == "mxfp4" else None
+                for i in range(layers):
+                    for x0 in range(e):  # an expert at a time: nothing larger is held in bf16
+                        t, sc = operand(kind, n, k)
+                        w[i, x0 * n:(x0 + 1) * n].copy_(t)
+                        if ws is not None:
+                            ws[i, x0 * n:(x0 + 1) * n].copy_(sc)
+                ring[name] = (w, ws, layers, per // e)
+            for m in ms:
+                pairs = m * topk
+                xin = torch.randn(m, hidden, device="cuda", generator=gen)
+                logits = (xin @ rw.t()).bfloat16().contiguous()
+                ids = torch.empty(pairs, device="cuda", dtype=torch.int32)
+                tw = torch.empty(pairs, device="cuda", dtype=torch.float32)
+                plan = torch.empty(hip.MOE_PLAN_INTS, device="cuda", dtype=torch.int32)
+                torch.cuda.synchronize()
+                hip.moe_route(s, logits.data_ptr(), e, ids.data_ptr(), tw.data_ptr(), plan.data_ptr(), m, e, topk)
+                s.sync()
+                ph = plan.cpu().numpy()
+                n_active = int(ph[0])
+                row = {"kind": kind, "hidden": hidden, "ffn": ffn, "experts": e, "topk": topk, "m": m,
+                       "n_active": n_active, "empty_slots": min(e, pairs) - n_active}
+                row["route_us"] = round(hip.time_moe_route(s, logits.data_ptr(), e, ids.data_ptr(), tw.data_ptr(),
+                                                           plan.data_ptr(), m, e, topk, 50) / 50 * 1e3, 2)
+                yb = torch.randn(pairs, hidden, device="cuda", dtype=torch.bfloat16)
+                ob = torch.empty(m, hidden, device="cuda", dtype=torch.bfloat16)
+                torch.cuda.synchronize()
+                row["combine_us"] = round(hip.time_moe_combine(s, yb.data_ptr(), hidden, tw.data_ptr(), ob.data_ptr(),
+                                                               hidden, m, topk, hidden, 50) / 50 * 1e3, 2)
+                for name, (n, k) in proj.items():
+                    w, ws, layers, xbytes = ring[name]
+                    a_div = topk if name == "up" else 1
+                    a, sa = operand(kind, -(-pairs // a_div), k)
+                    c = torch.empty(pairs, n, device="cuda", dtype=torch.bfloat16)
+                    wb, sbb = w[0].numel() * w.element_size(), (ws[0].numel() if ws is not None else 0)
+                    xw, xs = wb // e, sbb // e  # bytes of one expert's matrix and scales
+                    slots = []
+                    for sl in range(n_active):  # the per-expert loop's operands, gathered beforehand
+                        x0, b0, cnt = int(ph[4 + sl]), int(ph[4 + 128 + sl]), int(ph[4 + 256 + sl])
+                        src = torch.from_numpy(ph[4 + 384 + b0:4 + 384 + b0 + cnt] // a_div).cuda().long()
+                        slots.append((x0, cnt, a[src].contiguous(), None if sa is None else sa[src].contiguous(),
+                                      torch.empty(cnt, n, device="cuda", dtype=torch.bfloat16)))
+                    torch.cuda.synchronize()
+                    sap = 0 if sa is None else sa.data_ptr()
+
+                    def grouped(cfg):
+                        for i in range(layers):
+                            args = (s, kind, a.data_ptr(), a_div, w.data_ptr() + i * wb, c.data_ptr(), plan.data_ptr(),
+                                    m, topk, e, n, k)
+                            scales = (sap, ws.data_ptr() + i * sbb if ws is not None else 0)
+                            if cfg is None:
+                                hip.moe_gemm_nt(*args, *scales)
+                            else:
+                                hip.moe_gemm_nt_cfg(*args, cfg, *scales)
+
+                    def per_expert():
+                        for i in range(layers):
+                            for x0, cnt, ga, gsa, gc_ in slots:
+                                hip.decode_gemm_nt(s, kind, ga.data_ptr(), w.data_ptr() + i * wb + x0 * xw,
+                                                   gc_.data_ptr(), cnt, n, k, 0 if gsa is None else gsa.data_ptr(),
+                                                   ws.data_ptr() + i * sbb + x0 * xs if ws is not None else 0)
+
+                    variants = {f"cfg{cfg}_{cn}": (lambda cfg=cfg: grouped(cfg))
+                                for cfg, (cn, bn, *_) in hip.moe_gemm_cfgs().items() if n % bn == 0}
+                    variants["gsx"] = lambda: grouped(None)
+                    variants["per_expert"] = per_expert
+                    moved = layers * n_active * xbytes
+                    yard = hip.DeviceBuffer(0, moved & ~255)
+                    hip.memtest_write(s, yard.addr(), yard.nbytes, 0, MEMTEST_RANDOM, 1)
+                    s.sync()
+
+                    def timed(fn):
+                        torch.cuda.synchronize()
+                        with torch.cuda.stream(ts):
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record(ts)
+                            for _ in range(reps):
+                                fn()
+                            e1.record(ts)
+                        e1.synchronize()
+                        return reps * moved / (e0.elapsed_time(e1) * 1e-3) / 1e12
+
+                    def yardstick():
+                        s.sync()
+                        t0 = time.perf_counter()
+                        rep = hip.memtest_check(s, yard.addr(), yard.nbytes, 0, MEMTEST_RANDOM, 1)
+                        dt = time.perf_counter() - t0
+                        assert rep.bad_dwords == 0
+                        return yard.nbytes / dt / 1e12
+
+                    runs = {v: [] for v in [*variants, "memtest_check"]}
+                    for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                        for v, fn in variants.items():
+                            t = timed(fn)
+                            if r:
+                                runs[v].append(t)
+                        t = yardstick()
+                        if r:
+                            runs["memtest_check"].append(t)
+                    yard.free()
+                    row[f"{name}_layers"], row[f"{name}_active_bytes"] = layers, moved
+                    for v, ts_ in runs.items():
+                        med = statistics.median(ts_)
+                        row[f"{name}_{v}_TBps"] = round(med, 3)
+                        row[f"{name}_{v}_spread"] = round((max(ts_) - min(ts_)) / med, 3)
+                    del slots, a, sa, c
+                if kind == "bf16":  # the whole MLP of a layer, over the rings
+                    (wu, _, lu, _), (wd, _, ld, _) = ring["up"], ring["down"]
+                    xa = xin.bfloat16().contiguous()
+                    gu = torch.empty(pairs, 2 * ffn, device="cuda", dtype=torch.bfloat16)
+                    act = torch.empty(pairs, ffn, device="cuda", dtype=torch.bfloat16)
+                    torch.cuda.synchronize()
+                    ub, db, n_l = wu[0].numel() * 2, wd[0].numel() * 2, min(lu, ld)
+
+                    def mlp():
+                        for i in range(n_l):
+                            hip.moe_route(s, logits.data_ptr(), e, ids.data_ptr(), tw.data_ptr(), plan.data_ptr(), m, e,
+                                          topk)
+                            hip.moe_gemm_nt(s, "bf16", xa.data_ptr(), topk, wu.data_ptr() + i * ub, gu.data_ptr(),
+                                            plan.data_ptr(), m, topk, e, 2 * ffn, hidden)
+                            hip.silu_mul(s, "bf16", gu.data_ptr(), 2 * ffn, act.data_ptr(), ffn, 0, pairs, ffn)
+                            hip.moe_gemm_nt(s, "bf16", act.data_ptr(), 1, wd.data_ptr() + i * db, yb.data_ptr(),
+                                            plan.data_ptr(), m, topk, e, hidden, ffn)
+                            hip.moe_combine(s, yb.data_ptr(), hidden, tw.data_ptr(), ob.data_ptr(), hidden, m, topk,
+                                            hidden)
+
+                    us = []
+                    for r in range(rounds + 1):
+                        torch.cuda.synchronize()
+                        with torch.cuda.stream(ts):
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record(ts)
+                            for _ in range(reps):
+                                mlp()
+                            e1.record(ts)
+                        e1.synchronize()
+                        if r:
+                            us.append(e0.elapsed_time(e1) * 1e3 / (reps * n_l))
+                    row["mlp_us"] = round(statistics.median(us), 2)
+                    row["mlp_spread"] = round((max(us) - min(us)) / statistics.median(us), 3)
+                out.append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+            del ring
+            torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 def hbm(nbytes=16 << 30, reps=5):
     s = hip.Stream(0)
     buf = hip.DeviceBuffer(0, nbytes)
@@ -894,6 +1089,7 @@ if __name__ == "__main__":
                 "kv_append": kv_append, "norm_act": norm_act, "attn_prefill": attn_prefill, "sample": sample,
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
+                "moe": moe, "moe_128": lambda: moe(shapes=MOE_SHAPES[:1]),  # the 128-expert shape alone
                 "hbm": hbm}
     only = sys.argv[2].split(",") if len(sys.argv) > 2 else list(sections)  # [out.json [section,section..]]
     res = {name: sections[name]() for name in only}
