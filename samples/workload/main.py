@@ -697,6 +697,9 @@ def server_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, he
         return all(bool(torch.isfinite(t.float()).all()) for t in (*x, qkv, q, o))
 
     step.keep = (wqkv, wo, kc, vc, table, start, lens, cos, sin, x, qkv, q, o, ws)  # the closures hold addresses
+    step.buffers = {"wqkv": wqkv, "wo": wo, "kc": kc, "vc": vc, "table": table, "start": start, "lens0": lens[0],
+                    "lens1": lens[1], "cos": cos, "sin": sin, "x0": x[0], "x1": x[1], "x2": x[2], "qkv": qkv, "q": q,
+                    "o": o, "ws": ws}  # every tensor the step addresses, by name: what a test resolves a launch against
     return step, sync, finite
 
 
@@ -825,6 +828,10 @@ def layer_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, hea
     step.keep = (wqkv, wo, wgu, wdown, router, ln, kc, vc, table, start, lens, cos, sin, x0, resid, xn, sub, qkv, q, o,
                  gu, act, ws, rlogits, ids, tw, yexp, plans)
     step.io = {"x0": x0, "resid": resid, "sub": sub, "xn": xn}  # what the generate workload puts around the layers
+    step.buffers = {"wqkv": wqkv, "wo": wo, "wgu": wgu, "wdown": wdown, "router": router, "ln": ln, "kc": kc, "vc": vc,
+                    "table": table, "start": start, "lens0": lens[0], "lens1": lens[1], "cos": cos, "sin": sin,
+                    "x0": x0, "resid": resid, "xn": xn, "sub": sub, "qkv": qkv, "q": q, "o": o, "gu": gu, "act": act,
+                    "ws": ws, "rlogits": rlogits, "ids": ids, "tw": tw, "yexp": yexp, "plans": plans}  # as server_steps'
     return step, sync, finite
 
 
@@ -892,6 +899,8 @@ def generate_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, 
 
     step.hits = layers.hits
     step.keep = (layers, embed, head, lnf, logits, tokens, temp, topk, topp, seeds)
+    step.buffers = {**layers.buffers, "embed": embed, "head": head, "lnf": lnf, "logits": logits, "tokens0": tokens[0],
+                    "tokens1": tokens[1], "temp": temp, "topk": topk, "topp": topp, "seeds": seeds}
     return step, sync, finite, last_tokens
 
 
@@ -968,6 +977,9 @@ def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, con
 
     # the closures hold addresses, not tensors
     step.keep = (wqkv, wo, wgu, wdown, ln, kc, vc, table, lens, cos, sin, x0, resid, xn, sub, qkv, q, o, gu, act)
+    step.buffers = {"wqkv": wqkv, "wo": wo, "wgu": wgu, "wdown": wdown, "ln": ln, "kc": kc, "vc": vc, "table": table,
+                    "lens": lens, "cos": cos, "sin": sin, "x0": x0, "resid": resid, "xn": xn, "sub": sub, "qkv": qkv,
+                    "q": q, "o": o, "gu": gu, "act": act}  # as server_steps'
     return step, sync, finite
 
 
