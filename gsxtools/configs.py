@@ -48,7 +48,9 @@ from gpushare_scheduler_extender_amd.models.profile import (ALIYUN, NODE_ALLOCAT
 from gsxtools.cluster import start_apiserver, start_extender, start_node_agent, start_scheduler
 
 GIB = 1 << 30
-NODE = "mi355x-node-0"
+ALIGN = 2 << 20  # the pod runtime carves its arena in 2 MiB units
+ARENA_RESERVE = GIB  # device memory a real arena leaves free (gsx-memtest's default --reserve)
+NODE ="mi355x-node-0"
 CU_COUNT_ANNOTATION = "gpushare.amd.com/cu-count"
 AGENT = {"kind": "plugin", "args": [], "api_latency_ms": 0.0}  # --agent, --faithful, --api-latency-ms
 
@@ -71,6 +73,10 @@ class Runtimes:
                 from gpushare_scheduler_extender_amd.ops import hip
 
                 phys = 0 if share_gpu else i
+                # the device's size is its total memory, of which the driver or a hypervisor may hold some back: the
+                # arena takes what is free now, less the reserve gsx-memtest leaves for the runtime's own needs
+                free = hip.mem_info(phys)[0] - ARENA_RESERVE
+                arena = min(arena, free // ALIGN * ALIGN)
                 buf = hip.DeviceBuffer(phys, arena)
                 st = hip.Stream(phys)
                 rt = E.PodRuntime(phys, arena, buf.addr(0), st.ptr, 1 << 20, hip.lib()._name)
