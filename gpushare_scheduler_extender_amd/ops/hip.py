@@ -135,6 +135,12 @@ def lib():
         _moe_gemm_sig = [vp, i32, vp, i32, vp, vp, vp] + [i32] * 5 + [vp, vp, i32]
         # stream, Y, y_stride, topk_w, out, out_stride; M, topk, H
         _moe_combine_sig = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i32, i32, i32]
+        # stream, logits, logits_stride, topk_ids, topk_w; M, E, topk
+        _pf_route_sig = [vp, vp, ctypes.c_int64, vp, vp, i32, i32, i32]
+        # stream, topk_ids, plan; M, topk, E; workspace, workspace_bytes
+        _pf_plan_sig = [vp, vp, vp, i32, i32, i32, vp, u64]
+        # stream, A, a_div, B, C, plan; M, topk, E, N, K
+        _pf_gemm_sig = [vp, vp, i32, vp, vp, vp] + [i32] * 5
         sig = {
             "gsx_last_error": ([], ctypes.c_char_p),
             "gsx_device_count": ([ctypes.POINTER(i32)], i32),
@@ -208,6 +214,19 @@ def lib():
             "gsx_event_time_moe_gemm": ([*_moe_gemm_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_moe_combine": (_moe_combine_sig, i32),
             "gsx_event_time_moe_combine": ([*_moe_combine_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_moe_prefill_route": (_pf_route_sig, i32),
+            "gsx_event_time_moe_prefill_route": ([*_pf_route_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_moe_prefill_plan_ints": ([i32] * 3 + [ctypes.POINTER(u64)], i32),
+            "gsx_moe_prefill_workspace_bytes": ([i32] * 3 + [ctypes.POINTER(u64)], i32),
+            "gsx_moe_prefill_plan": (_pf_plan_sig, i32),
+            "gsx_event_time_moe_prefill_plan": ([*_pf_plan_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_moe_prefill_gemm_nt": (_pf_gemm_sig, i32),
+            "gsx_moe_prefill_gemm_nt_launch_cfg": ([*_pf_gemm_sig, i32], i32),
+            "gsx_moe_prefill_gemm_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_moe_prefill_gemm_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
+            "gsx_event_time_moe_prefill_gemm": ([*_pf_gemm_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_moe_prefill_combine": (_moe_combine_sig, i32),
+            "gsx_event_time_moe_prefill_combine": ([*_moe_combine_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
             "gsx_memtest_check": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32, i32, ctypes.POINTER(MemtestReport)],
                                   i32),
@@ -1023,4 +1042,128 @@ def time_moe_combine(stream: Stream, y: int, y_stride: int, topk_w: int, out: in
     ms = ctypes.c_float(0)
     _ck(lib().gsx_event_time_moe_combine(*_moe_combine_args(stream, y, y_stride, topk_w, out, out_stride, m, topk, h),
                                          iters, ctypes.byref(ms)), "time_moe_combine")
+    return ms.value
+
+
+# Mixture-of-experts prefill (gsx_kernels.h): the same layer for up to 32768 tokens.  The plan is a tile plan of
+# ``moe_prefill_plan_ints(m, topk, e)`` int32: every expert's pairs padded to the grouped GEMM's 128-row tile.
+MOE_PREFILL_BM = 128
+
+
+def _moe_prefill_route_args(stream: Stream, logits: int, logits_stride: int, topk_ids: int, topk_w: int, m: int,
+                            e: int, topk: int) -> tuple:
+    return (stream.handle, ctypes.c_void_p(logits), logits_stride, ctypes.c_void_p(topk_ids), ctypes.c_void_p(topk_w),
+            m, e, topk)
+
+
+def moe_prefill_route(stream: Stream, logits: int, logits_stride: int, topk_ids: int, topk_w: int, m: int, e: int,
+                      topk: int):
+    """The router for ``m <= 32768`` rows: :func:`moe_route`'s ids and weights per row, and no plan
+    (:func:`moe_prefill_plan` makes it).  Not synchronised."""
+    _ck(lib().gsx_moe_prefill_route(*_moe_prefill_route_args(stream, logits, logits_stride, topk_ids, topk_w, m, e,
+                                                             topk)), "moe_prefill_route")
+
+
+def time_moe_prefill_route(stream: Stream, logits: int, logits_stride: int, topk_ids: int, topk_w: int, m: int, e: int,
+                           topk: int, iters: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_moe_prefill_route(*_moe_prefill_route_args(stream, logits, logits_stride, topk_ids,
+                                                                        topk_w, m, e, topk), iters, ctypes.byref(ms)),
+        "time_moe_prefill_route")
+    return ms.value
+
+
+def moe_prefill_plan_ints(m: int, topk: int, e: int) -> int:
+    """int32 of the tile plan: ``4 + T_max + 128 T_max`` with ``T_max = (P + min(e, P) * 127) // 128``."""
+    n = ctypes.c_uint64(0)
+    _ck(lib().gsx_moe_prefill_plan_ints(m, topk, e, ctypes.byref(n)), "moe_prefill_plan_ints")
+    return n.value
+
+
+def moe_prefill_workspace_bytes(m: int, topk: int, e: int) -> int:
+    """Bytes of scratch :func:`moe_prefill_plan` needs for these sizes."""
+    n = ctypes.c_uint64(0)
+    _ck(lib().gsx_moe_prefill_workspace_bytes(m, topk, e, ctypes.byref(n)), "moe_prefill_workspace_bytes")
+    return n.value
+
+
+def _moe_prefill_plan_args(stream: Stream, topk_ids: int, plan: int, m: int, topk: int, e: int, workspace: int,
+                           workspace_bytes: int) -> tuple:
+    return (stream.handle, ctypes.c_void_p(topk_ids), ctypes.c_void_p(plan), m, topk, e, ctypes.c_void_p(workspace),
+            workspace_bytes)
+
+
+def moe_prefill_plan(stream: Stream, topk_ids: int, plan: int, m: int, topk: int, e: int, workspace: int,
+                     workspace_bytes: int):
+    """The tile plan of ``topk_ids[m][topk]``: header ``{n_tiles, P, e, 128}``, ``tile_expert[T_max]`` and
+    ``rows[T_max * 128]``, the pairs sorted stably by expert and padded per expert to 128 rows with -1.  Built on the
+    device, a pure function of the ids; an id outside ``[0, e)`` is dropped.  ``workspace`` is
+    :func:`moe_prefill_workspace_bytes` bytes of device memory.  Not synchronised."""
+    _ck(lib().gsx_moe_prefill_plan(*_moe_prefill_plan_args(stream, topk_ids, plan, m, topk, e, workspace,
+                                                           workspace_bytes)), "moe_prefill_plan")
+
+
+def time_moe_prefill_plan(stream: Stream, topk_ids: int, plan: int, m: int, topk: int, e: int, workspace: int,
+                          workspace_bytes: int, iters: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_moe_prefill_plan(*_moe_prefill_plan_args(stream, topk_ids, plan, m, topk, e, workspace,
+                                                                      workspace_bytes), iters, ctypes.byref(ms)),
+        "time_moe_prefill_plan")
+    return ms.value
+
+
+def _moe_prefill_gemm_args(stream: Stream, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                           n: int, k: int) -> tuple:
+    return (stream.handle, ctypes.c_void_p(a), a_div, ctypes.c_void_p(b), ctypes.c_void_p(c), ctypes.c_void_p(plan), m,
+            topk, e, n, k)
+
+
+def moe_prefill_gemm_nt(stream: Stream, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                        n: int, k: int):
+    """The grouped 128x128 GEMM (bf16): for every pair ``p`` of the tile plan with expert ``x``, ``C[p][n] =
+    A[p // a_div][k] * B[x][n][k]^T``; ``a_div`` as :func:`moe_gemm_nt`.  ``n % 128 == 0``, ``k % 64 == 0``.  The grid
+    is fixed by the sizes, unused tiles return at once.  Not synchronised."""
+    _ck(lib().gsx_moe_prefill_gemm_nt(*_moe_prefill_gemm_args(stream, a, a_div, b, c, plan, m, topk, e, n, k)),
+        "moe_prefill_gemm_nt")
+
+
+def moe_prefill_gemm_cfgs() -> dict[int, tuple[str, int, int, int]]:
+    """``{index: (name, bm, bn, waves)}`` of the grouped prefill GEMM's configurations, read from the library."""
+    out: dict[int, tuple[str, int, int, int]] = {}
+    while (name := lib().gsx_moe_prefill_gemm_cfg_name(len(out))) is not None:
+        v = [ctypes.c_int(0) for _ in range(3)]
+        if lib().gsx_moe_prefill_gemm_cfg_shape(len(out), *map(ctypes.byref, v)) != 0:
+            raise HipError(f"moe prefill gemm cfg {len(out)} has a name and no shape")
+        out[len(out)] = (name.decode(), *(x.value for x in v))
+    return out
+
+
+def moe_prefill_gemm_nt_cfg(stream: Stream, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                            n: int, k: int, cfg: int):
+    """Launch one configuration of the grouped prefill GEMM; an unknown config raises HipError."""
+    _ck(lib().gsx_moe_prefill_gemm_nt_launch_cfg(*_moe_prefill_gemm_args(stream, a, a_div, b, c, plan, m, topk, e, n,
+                                                                         k), cfg), f"moe prefill gemm cfg {cfg}")
+
+
+def time_moe_prefill_gemm(stream: Stream, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                          n: int, k: int, iters: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_moe_prefill_gemm(*_moe_prefill_gemm_args(stream, a, a_div, b, c, plan, m, topk, e, n, k),
+                                              iters, ctypes.byref(ms)), "time_moe_prefill_gemm")
+    return ms.value
+
+
+def moe_prefill_combine(stream: Stream, y: int, y_stride: int, topk_w: int, out: int, out_stride: int, m: int,
+                        topk: int, h: int):
+    """:func:`moe_combine` for ``m <= 32768`` rows, the same bits.  Not synchronised."""
+    _ck(lib().gsx_moe_prefill_combine(*_moe_combine_args(stream, y, y_stride, topk_w, out, out_stride, m, topk, h)),
+        "moe_prefill_combine")
+
+
+def time_moe_prefill_combine(stream: Stream, y: int, y_stride: int, topk_w: int, out: int, out_stride: int, m: int,
+                             topk: int, h: int, iters: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_moe_prefill_combine(*_moe_combine_args(stream, y, y_stride, topk_w, out, out_stride, m,
+                                                                    topk, h), iters, ctypes.byref(ms)),
+        "time_moe_prefill_combine")
     return ms.value

@@ -16,7 +16,8 @@ Targets (outputs land in ``gpushare_scheduler_extender_amd/_native/``):
                 paged KV cache (attn_decode.hip), RoPE + KV-cache append (kv_append.hip), fused residual add + RMSNorm
                 and SwiGLU (norm_act.hip), causal prefill attention over the same cache (attn_prefill.hip), the token
                 sampler and the embedding gather (sample.hip), the MoE router and combine (moe.hip; the grouped expert
-                GEMM is a form of the decode kernel in gemm_decode.hip), CU-masked streams.
+                GEMM is a form of the decode kernel in gemm_decode.hip), MoE prefill: the many-token router, the tile
+                plan, the grouped 128x128 GEMM and the combine (moe_prefill.hip), CU-masked streams.
 * ``tools``   – standalone HIP executables (``gsx-cuprobe``, ``gsx-memprobe``, ``gsx-memtest``, ``gsx-cutest``).
 * ``isolate`` – ``libgsx_isolate.so``, the HSA tools library that enforces a pod's CU partition and HBM share
                 inside every HIP/HSA process of the pod, plus its host-only test driver (fake HSA runtime).
@@ -87,7 +88,8 @@ def _run(cmd: list[str], verbose: bool) -> None:
 
 
 def _compile_objs(srcs: list[Path], compiler: str, flags: list[str], tag: str, force: bool, verbose: bool,
-                  headers: list[Path]) -> list[Path]:
+                  headers: list[Path], extra: dict[str, list[str]] | None = None) -> list[Path]:
+    """``extra``: more flags for the sources whose stem it names."""
     OBJ.mkdir(parents=True, exist_ok=True)
     jobs = []
     objs = []
@@ -95,7 +97,7 @@ def _compile_objs(srcs: list[Path], compiler: str, flags: list[str], tag: str, f
         o = OBJ / f"{tag}_{s.stem}.o"
         objs.append(o)
         if force or _newer(o, [s, *headers]):
-            jobs.append([compiler, *flags, "-c", str(s), "-o", str(o)])
+            jobs.append([compiler, *flags, *(extra or {}).get(s.stem, []), "-c", str(s), "-o", str(o)])
     if jobs:
         with cf.ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:
             list(ex.map(lambda c: _run(c, verbose), jobs))
@@ -179,6 +181,10 @@ def _hipcc() -> str:
 
 
 KERNELS = NATIVE / "kernels"
+# Per-source flags on top of the common set.  moe_prefill.hip is compiled without the packed fp32 instructions
+# (v_pk_add_f32, v_pk_mul_f32, v_pk_fma_f32): its router and combine round every operation on its own, and the scalar
+# forms are the ones their contracts were written against.  The older sources keep the flags they were measured with.
+HIP_EXTRA = {"moe_prefill": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 _hip_forced: set[Path] = set()  # what a --force has compiled in this process already
 
 
@@ -196,9 +202,9 @@ def _hip_objs(srcs: list[Path], force: bool, verbose: bool) -> list[Path]:
              "-munsafe-fp-atomics"]
     headers = _kernel_sources()[2]
     again = [s for s in srcs if force and s not in _hip_forced]
-    _compile_objs(again, _hipcc(), flags, "kern", True, verbose, headers)
+    _compile_objs(again, _hipcc(), flags, "kern", True, verbose, headers, HIP_EXTRA)
     _hip_forced.update(again)
-    return _compile_objs(srcs, _hipcc(), flags, "kern", False, verbose, headers)
+    return _compile_objs(srcs, _hipcc(), flags, "kern", False, verbose, headers, HIP_EXTRA)
 
 
 def build_kernels(force: bool = False, verbose: bool = False) -> Path:

@@ -36,6 +36,9 @@
 //  * add + RMSNorm, SwiGLU — the residual stream, the normalisation and the MLP's activation of
 //                          a decoder layer, to bf16 or to e4m3 with a scale per row
 //                          (norm_act.hip);
+//  * MoE prefill         — a mixture-of-experts layer at prefill row counts: a router over thousands
+//                          of tokens, a tile plan built on the device, and a compute-bound grouped
+//                          128x128 GEMM whose A rows are gathered by expert (moe_prefill.hip);
 //  * CU-masked streams   — hipExtStreamCreateWithCUMask.
 //
 // All functions return 0 or a hipError_t value; gsx_last_error() has text.
@@ -557,6 +560,82 @@ int gsx_event_time_moe_gemm(void* stream, int kind, const void* A, int a_div, co
                             const void* scale_b, int scale_mode, int iters, float* ms);
 int gsx_event_time_moe_combine(void* stream, const void* Y, int64_t y_stride, const float* topk_w, void* out,
                                int64_t out_stride, int M, int topk, int H, int iters, float* ms);
+
+// Mixture-of-experts prefill (moe_prefill.hip): the same layer for 1 <= M <= 32768 tokens, 8 <= E <= 1024 experts with
+// E % 8 == 0 and 1 <= topk <= min(8, E); P = M topk pairs, pair p = m topk + j as in decode.  Four entry points that
+// hand ids, weights and a tile plan to each other through device memory; none synchronises.  bf16 operands only: fp8
+// and mxfp4 experts are out of scope here, as they are for the dense prefill workload.  The decode entry points above,
+// their limits and their refusals are unchanged.
+//
+// gsx_moe_prefill_route: logits[M][logits_stride] bf16 (the large GEMM's output against the router matrix),
+// topk_ids[M][topk] int32, topk_w[M][topk] fp32.  Per row exactly gsx_moe_route's rules: selection by the sampler's key
+// with ties to the lowest index, ids in descending key order, weights the softmax over the selected logits by the same
+// operation sequence, so within the same delta(x_j) = (3 |x_j| + 3.2 (topk - 1) + 4) u of the exact weight.  It writes
+// no plan.  A wave owns a row, four rows to a workgroup; a row never crosses a workgroup and nothing passes between
+// workgroups.  No logit content writes an id outside [0, E) or anything outside the two outputs.
+// Requirements: the sizes above; logits_stride >= E and a multiple of 8; pointers non-NULL, logits 16-B aligned, the
+// outputs 4-B aligned; the outputs overlap nothing.
+//
+// gsx_moe_prefill_plan: the tile plan, a stable counting sort of the pairs by expert, padded per expert to the grouped
+// GEMM's 128-row tile.  With T_max = (P + min(E, P) * 127) / 128 (integer division; it bounds the sum over experts of
+// ceil(c_e / 128), c_e the pairs of expert e), plan is 4 + T_max + 128 T_max int32:
+//   header       {n_tiles, P, E, 128}
+//   tile_expert  [T_max]: the experts that have at least one pair, in ascending expert index, each ceil(c_e / 128)
+//                consecutive tiles; every tile at or past n_tiles is -1.
+//   rows         [T_max * 128]: tile t's 128 entries are its expert's pairs in ascending pair order, continuing across
+//                that expert's tiles; the tail of its last tile and every unused tile are -1.
+// The whole buffer is defined and a pure function of topk_ids: it does not depend on where workgroups ran (counts are
+// integer sums, and a pair's place is its expert's base plus its rank, found without an ordering atomic).  An id
+// outside [0, E) is dropped, not clamped: its pair is in no tile.  gsx_moe_prefill_plan_ints gives the plan's size and
+// gsx_moe_prefill_workspace_bytes the scratch the caller passes as `workspace` (ceil(P / 1024) * E int32: per-block
+// histograms that become per-block offsets); nothing is allocated per call.  Three launches on `stream`.
+// Requirements: the sizes above; pointers non-NULL and 4-B aligned; workspace_bytes at least what the query gives;
+// plan and workspace overlap neither topk_ids nor each other.
+//
+// gsx_moe_prefill_gemm_nt: for every pair p of the plan, with e its tile's expert, C[p][0..N) = A[p / a_div][0..K) *
+// B[e][N][K]^T, in bf16 with fp32 accumulation and one rounding.  a_div = topk is the up projection, a_div = 1 the down
+// projection; A has ceil(P / a_div) contiguous rows, C[P][N] is contiguous, B[E][N][K] are the experts back to back: the
+// convention of gsx_moe_gemm_nt.  N % 128 == 0, K % 64 == 0.  One configuration, 0 "128x128/4w-gather": a 128x128 block
+// tile, 4 waves as 2x2 on v_mfma_f32_16x16x32_bf16, two LDS stages filled by 16-B global_load_lds; the A rows of a tile
+// are gathered through rows (addresses made once per workgroup, 64-bit: A may exceed 2 GiB) and every output row is
+// stored to its pair's row of C (64-bit offsets).  The grid is (N / 128) * T_max workgroups, fixed by the host; a
+// workgroup reads n_tiles and its tile_expert from the plan and returns at once if its tile is unused, so no host
+// synchronisation is needed.  Summation order per output element: K-tiles in order and the MFMA k-steps in order, that
+// of the dense configuration "128x128/4w" (gsx_gemm_bf16_nt_launch_cfg): a pair's row has the bits that configuration
+// gives for the same A row against that expert's matrix.  A pair that no tile lists keeps what C held.
+// The plan is device memory anyone may have written, and no content of it makes the kernel read outside A or B or
+// write outside C: n_tiles is clamped to T_max, a tile whose expert is outside [0, E) is skipped, a row outside [0, P)
+// is padding (it reads row 0 of A and stores nothing).  The same pair listed twice is a race: the caller's business.
+// Requirements: the sizes above; a_div >= 1; N and K as above, 127 K + 56 < 2^31 and (N / 128) T_max < 2^31; A, B, C
+// and plan non-NULL, A, B and C 16-B aligned, plan 4-B aligned; C overlaps nothing.
+//
+// gsx_moe_prefill_combine: gsx_moe_combine's arithmetic bit for bit (acc = fl(w_0 y_0), then fl(acc + fl(w_j y_j)) in
+// the order of j, nothing contracted, one rounding to bf16) for 1 <= M <= 32768, with 64-bit row offsets; a thread
+// handles 8 columns with 16-B loads and stores.  Its other requirements are gsx_moe_combine's.
+// Everything is validated before the first device call; every launch is on `stream` and returns without synchronising.
+int gsx_moe_prefill_route(void* stream, const void* logits, int64_t logits_stride, int32_t* topk_ids, float* topk_w,
+                          int M, int E, int topk);
+int gsx_moe_prefill_plan_ints(int M, int topk, int E, uint64_t* ints);
+int gsx_moe_prefill_workspace_bytes(int M, int topk, int E, uint64_t* bytes);
+int gsx_moe_prefill_plan(void* stream, const int32_t* topk_ids, int32_t* plan, int M, int topk, int E, void* workspace,
+                         uint64_t workspace_bytes);
+int gsx_moe_prefill_gemm_nt(void* stream, const void* A, int a_div, const void* B, void* C, const int32_t* plan, int M,
+                            int topk, int E, int N, int K);
+const char* gsx_moe_prefill_gemm_cfg_name(int cfg);
+int gsx_moe_prefill_gemm_cfg_shape(int cfg, int* bm, int* bn, int* waves);
+int gsx_moe_prefill_gemm_nt_launch_cfg(void* stream, const void* A, int a_div, const void* B, void* C,
+                                       const int32_t* plan, int M, int topk, int E, int N, int K, int cfg);
+int gsx_moe_prefill_combine(void* stream, const void* Y, int64_t y_stride, const float* topk_w, void* out,
+                            int64_t out_stride, int M, int topk, int H);
+// elapsed milliseconds of `iters` back-to-back calls on `stream`, by hip events (for benches)
+int gsx_event_time_moe_prefill_route(void* stream, const void* logits, int64_t logits_stride, int32_t* topk_ids,
+                                     float* topk_w, int M, int E, int topk, int iters, float* ms);
+int gsx_event_time_moe_prefill_plan(void* stream, const int32_t* topk_ids, int32_t* plan, int M, int topk, int E,
+                                    void* workspace, uint64_t workspace_bytes, int iters, float* ms);
+int gsx_event_time_moe_prefill_gemm(void* stream, const void* A, int a_div, const void* B, void* C,
+                                    const int32_t* plan, int M, int topk, int E, int N, int K, int iters, float* ms);
+int gsx_event_time_moe_prefill_combine(void* stream, const void* Y, int64_t y_stride, const float* topk_w, void* out,
+                                       int64_t out_stride, int M, int topk, int H, int iters, float* ms);
 
 // HBM pre-flight memory test (memtest.hip).  The expected content of 16-byte word W = origin/16 + word index is
 // generated from (pattern, seed, invert, W) and never stored; `origin` is the byte offset of `base` in the whole

@@ -62,6 +62,13 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   over the paged cache, attends over it.  The lengths are a constant device buffer, so an endless run rewrites the same
   slots.  It reports ``tokens_per_s`` (prompt tokens), ``tflops`` (the projections, and the attention over visible
   pairs only), ``tbps``, ``chunk`` and the layer workload's fields.
+* ``--workload prefill-moe`` is that prefill layer with a mixture-of-experts MLP: ``--experts`` experts (a multiple of
+  128 up to 1024: the router matrix runs on the large GEMM) of width ``--ffn``, of which a token picks
+  ``--experts-active``.  The router's logits go through ``gsx_moe_prefill_route`` and ``gsx_moe_prefill_plan``, the two
+  projections through the grouped 128x128 GEMM with SwiGLU on the pairs between them, and ``gsx_moe_prefill_combine``
+  closes the layer.  It reports the prefill workload's fields (``tflops`` counts real pairs only), ``experts``,
+  ``experts_active`` and ``pad_share``, the share of the grouped GEMM's 128-row tiles that the last step's routing
+  left as padding.
 """
 from __future__ import annotations
 
@@ -195,6 +202,13 @@ def moe_active(experts: int, experts_active: int) -> int:
 
 def moe_refusal(workload: str, experts: int, experts_active: int) -> str | None:
     """Why ``--experts`` cannot run with these options, or None: known before anything touches the device."""
+    if workload == "prefill-moe":
+        if not 128 <= experts <= MOE_MAX_EXPERTS or experts % 128:
+            return (f"--workload prefill-moe --experts {experts}: a multiple of 128 in 128..{MOE_MAX_EXPERTS} "
+                    "(the router is the large GEMM)")
+        if not 1 <= experts_active <= MOE_MAX_ACTIVE:
+            return f"--experts-active {experts_active}: 1..{MOE_MAX_ACTIVE}"
+        return None
     if experts == 0:
         return None
     if workload == "prefill":
@@ -292,6 +306,17 @@ class Kernels:
             for f in (L.gsx_moe_route, L.gsx_moe_gemm_nt, L.gsx_moe_gemm_nt_launch_cfg, L.gsx_moe_combine,
                       L.gsx_moe_gemm_cfg_shape, L.gsx_event_time_moe_route, L.gsx_event_time_moe_gemm,
                       L.gsx_event_time_moe_combine):
+                f.restype = i32
+        if hasattr(L, "gsx_moe_prefill_route"):  # likewise: an image built before the MoE prefill kernels
+            i64, u64 = ctypes.c_int64, ctypes.c_uint64
+            L.gsx_moe_prefill_route.argtypes = [vp, vp, i64, vp, vp, i32, i32, i32]
+            L.gsx_moe_prefill_plan_ints.argtypes = [i32, i32, i32, ctypes.POINTER(u64)]
+            L.gsx_moe_prefill_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(u64)]
+            L.gsx_moe_prefill_plan.argtypes = [vp, vp, vp, i32, i32, i32, vp, u64]
+            L.gsx_moe_prefill_gemm_nt.argtypes = [vp, vp, i32, vp, vp, vp] + [i32] * 5
+            L.gsx_moe_prefill_combine.argtypes = [vp, vp, i64, vp, vp, i64, i32, i32, i32]
+            for f in (L.gsx_moe_prefill_route, L.gsx_moe_prefill_plan_ints, L.gsx_moe_prefill_workspace_bytes,
+                      L.gsx_moe_prefill_plan, L.gsx_moe_prefill_gemm_nt, L.gsx_moe_prefill_combine):
                 f.restype = i32
         L.gsx_last_error.argtypes, L.gsx_last_error.restype = [], ctypes.c_char_p
         self.L, self.path = L, path
@@ -495,6 +520,36 @@ class Kernels:
         self._ck(self.L.gsx_event_time_moe_combine(*self._moe_combine_args(s, y, w, out, m, topk, h), iters,
                                                    ctypes.byref(ms)), "time_moe_combine")
         return ms.value
+
+    def moe_prefill_sizes(self, m: int, topk: int, e: int) -> tuple[int, int]:
+        """``(int32 of the tile plan, bytes of the plan's scratch)`` for ``m`` tokens that pick ``topk`` of ``e``."""
+        if not hasattr(self.L, "gsx_moe_prefill_route"):
+            raise RuntimeError(f"{self.path} has no gsx_moe_prefill_route: rebuild it")
+        ints, ws = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._ck(self.L.gsx_moe_prefill_plan_ints(m, topk, e, ctypes.byref(ints)), "moe_prefill_plan_ints")
+        self._ck(self.L.gsx_moe_prefill_workspace_bytes(m, topk, e, ctypes.byref(ws)), "moe_prefill_workspace_bytes")
+        return ints.value, ws.value
+
+    def moe_prefill_route(self, s, logits: int, ids: int, w: int, m: int, e: int, topk: int):
+        """From ``logits[m][e]`` (bf16, contiguous rows), m up to 32768: ``ids[m][topk]`` int32 and ``w[m][topk]``
+        fp32."""
+        self._ck(self.L.gsx_moe_prefill_route(s, ctypes.c_void_p(logits), e, ctypes.c_void_p(ids), ctypes.c_void_p(w),
+                                              m, e, topk), "moe_prefill_route")
+
+    def moe_prefill_plan(self, s, ids: int, plan: int, m: int, topk: int, e: int, ws: int, ws_bytes: int):
+        """The tile plan of ``ids``: the pairs by expert, padded per expert to 128 rows."""
+        self._ck(self.L.gsx_moe_prefill_plan(s, ctypes.c_void_p(ids), ctypes.c_void_p(plan), m, topk, e,
+                                             ctypes.c_void_p(ws), ws_bytes), "moe_prefill_plan")
+
+    def moe_prefill_gemm_nt(self, s, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int, n: int,
+                            k: int):
+        """``c[p][n] = a[p // a_div][k] * b[expert of p][n][k]^T`` for every pair ``p`` of the tile plan (bf16)."""
+        self._ck(self.L.gsx_moe_prefill_gemm_nt(s, ctypes.c_void_p(a), a_div, ctypes.c_void_p(b), ctypes.c_void_p(c),
+                                                ctypes.c_void_p(plan), m, topk, e, n, k), "moe_prefill_gemm_nt")
+
+    def moe_prefill_combine(self, s, y: int, w: int, out: int, m: int, topk: int, h: int):
+        self._ck(self.L.gsx_moe_prefill_combine(s, ctypes.c_void_p(y), h, ctypes.c_void_p(w), ctypes.c_void_p(out), h,
+                                                m, topk, h), "moe_prefill_combine")
 
     def sync(self, s):
         self._ck(self.L.gsx_stream_sync(s), "stream_sync")
@@ -905,22 +960,32 @@ def generate_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, 
 
 
 def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, context: int, heads: int, kv_heads: int,
-                  page: int, ffn: int, w_layers: int, kv_layers: int):
+                  page: int, ffn: int, w_layers: int, kv_layers: int, *, experts: int = 0, active: int = 0):
     """``(step, sync, finite)`` of the prefill workload: :func:`layer_steps` on ``batch * chunk`` rows.  The
     projections go through the large GEMM, the append writes ``chunk`` tokens per sequence at positions
-    ``[context - chunk, context)`` and the causal attention reads the lengths the append read: one constant buffer."""
+    ``[context - chunk, context)`` and the causal attention reads the lengths the append read: one constant buffer.
+
+    With ``experts`` > 0 (``--workload prefill-moe``) the MLP is a mixture of experts of width ``ffn``, of which a
+    token picks ``active``: the router (the large GEMM with N = ``experts``), ``moe_prefill_route``, the tile plan, the
+    grouped up projection, SwiGLU on the ``rows * active`` pairs, the grouped down projection and the combine; ids,
+    weights and plan never leave the device.  ``step.plan_header()`` reads the last plan's ``(n_tiles, P)``."""
     hidden, nqkv = heads * ATTN_D, (heads + 2 * kv_heads) * ATTN_D
     rows = batch * chunk
     per_seq, pages = kv_pages(batch, context, page)
     layers = max(w_layers, kv_layers)
     bf = torch.bfloat16
+    nexp, pairs = max(experts, 1), rows * max(active, 1)  # a dense MLP is one expert that every row takes once
     wqkv = torch.empty(w_layers, nqkv, hidden, device=dev, dtype=bf)
     wo = torch.empty(w_layers, hidden, hidden, device=dev, dtype=bf)
-    wgu = torch.empty(w_layers, 2 * ffn, hidden, device=dev, dtype=bf)
-    wdown = torch.empty(w_layers, hidden, ffn, device=dev, dtype=bf)
+    wgu = torch.empty(w_layers, nexp * 2 * ffn, hidden, device=dev, dtype=bf)
+    wdown = torch.empty(w_layers, nexp * hidden, ffn, device=dev, dtype=bf)
+    router = torch.empty(w_layers, experts, hidden, device=dev, dtype=bf)
     for i in range(w_layers):  # one matrix at a time: nothing larger is ever held in fp32
-        for w, k in ((wqkv, hidden), (wo, hidden), (wgu, hidden), (wdown, ffn)):
-            w[i].copy_(torch.randn(w.shape[1], k, device=dev) / math.sqrt(k))
+        for w, k, per in ((wqkv, hidden, 1), (wo, hidden, 1), (wgu, hidden, nexp), (wdown, ffn, nexp),
+                          (router, hidden, 1)):
+            n = w.shape[1] // per  # an expert at a time; a dense layer has no router
+            for x in range(per if n else 0):
+                w[i, x * n:(x + 1) * n].copy_(torch.randn(n, k, device=dev) / math.sqrt(k))
     ln = torch.ones(w_layers, 2, hidden, device=dev, dtype=bf)
     kdt = bf if kv_dtype == "bf16" else torch.float8_e4m3fn
     kc = torch.empty(kv_layers, pages, kv_heads, page, ATTN_D, device=dev, dtype=kdt)
@@ -938,12 +1003,32 @@ def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, con
     qkv = torch.empty(rows, nqkv, device=dev, dtype=bf)
     q = torch.empty(rows, heads, ATTN_D, device=dev, dtype=bf)
     o = torch.empty_like(q)
-    gu = torch.empty(rows, 2 * ffn, device=dev, dtype=bf)
-    act = torch.empty(rows, ffn, device=dev, dtype=bf)
+    gu = torch.empty(pairs, 2 * ffn, device=dev, dtype=bf)
+    act = torch.empty(pairs, ffn, device=dev, dtype=bf)
     wqkv_b, wo_b, wgu_b, wdown_b = (w[0].numel() * 2 for w in (wqkv, wo, wgu, wdown))
     cache_bytes = kc[0].numel() * kc.element_size()
     scale = 1.0 / math.sqrt(ATTN_D)
+    if experts:
+        plan_ints, ws_bytes = kl.moe_prefill_sizes(rows, active, experts)
+        rlogits = torch.empty(rows, experts, device=dev, dtype=bf)
+        ids = torch.empty(rows, active, device=dev, dtype=torch.int32)
+        tw = torch.empty(rows, active, device=dev, dtype=torch.float32)
+        plan = torch.zeros(plan_ints, device=dev, dtype=torch.int32)
+        ws = torch.empty(max(ws_bytes, 4) // 4, device=dev, dtype=torch.int32)
+        yexp = torch.empty(pairs, hidden, device=dev, dtype=bf)
     torch.cuda.synchronize()
+
+    def moe_mlp(wi):
+        kl.gemm(gs, xn.data_ptr(), router.data_ptr() + wi * experts * hidden * 2, rlogits.data_ptr(), rows, experts,
+                hidden)
+        kl.moe_prefill_route(gs, rlogits.data_ptr(), ids.data_ptr(), tw.data_ptr(), rows, experts, active)
+        kl.moe_prefill_plan(gs, ids.data_ptr(), plan.data_ptr(), rows, active, experts, ws.data_ptr(), ws_bytes)
+        kl.moe_prefill_gemm_nt(gs, xn.data_ptr(), active, wgu.data_ptr() + wi * wgu_b, gu.data_ptr(), plan.data_ptr(),
+                               rows, active, experts, 2 * ffn, hidden)
+        kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), pairs, ffn)
+        kl.moe_prefill_gemm_nt(gs, act.data_ptr(), 1, wdown.data_ptr() + wi * wdown_b, yexp.data_ptr(),
+                               plan.data_ptr(), rows, active, experts, hidden, ffn)
+        kl.moe_prefill_combine(gs, yexp.data_ptr(), tw.data_ptr(), sub.data_ptr(), rows, active, hidden)
 
     def step():
         for i in range(layers):
@@ -964,6 +1049,9 @@ def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, con
             kl.gemm(gs, o.data_ptr(), wo.data_ptr() + wi * wo_b, sub.data_ptr(), rows, hidden, hidden)
             kl.add_rmsnorm(gs, sub.data_ptr(), resid.data_ptr(), resid.data_ptr(), ln1 + hidden * 2, xn.data_ptr(),
                            rows, hidden, LAYER_EPS)
+            if experts:
+                moe_mlp(wi)
+                continue
             kl.gemm(gs, xn.data_ptr(), wgu.data_ptr() + wi * wgu_b, gu.data_ptr(), rows, 2 * ffn, hidden)
             kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), rows, ffn)
             kl.gemm(gs, act.data_ptr(), wdown.data_ptr() + wi * wdown_b, sub.data_ptr(), rows, hidden, ffn)
@@ -971,15 +1059,26 @@ def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, con
     def sync():
         kl.sync(gs)
 
+    moe = (rlogits, tw, yexp) if experts else ()
+
     def finite():
         kl.sync(gs)
-        return all(bool(torch.isfinite(t.float()).all()) for t in (resid, xn, sub, qkv, q, o, gu, act))
+        return all(bool(torch.isfinite(t.float()).all()) for t in (resid, xn, sub, qkv, q, o, gu, act, *moe))
+
+    def plan_header():
+        kl.sync(gs)
+        n_tiles, p = plan[:2].tolist()
+        return n_tiles, p
 
     # the closures hold addresses, not tensors
     step.keep = (wqkv, wo, wgu, wdown, ln, kc, vc, table, lens, cos, sin, x0, resid, xn, sub, qkv, q, o, gu, act)
     step.buffers = {"wqkv": wqkv, "wo": wo, "wgu": wgu, "wdown": wdown, "ln": ln, "kc": kc, "vc": vc, "table": table,
                     "lens": lens, "cos": cos, "sin": sin, "x0": x0, "resid": resid, "xn": xn, "sub": sub, "qkv": qkv,
                     "q": q, "o": o, "gu": gu, "act": act}  # as server_steps'
+    if experts:
+        step.keep += (router, rlogits, ids, tw, plan, ws, yexp)
+        step.buffers.update({"router": router, "rlogits": rlogits, "ids": ids, "tw": tw, "plan": plan, "yexp": yexp})
+        step.plan_header = plan_header
     return step, sync, finite
 
 
@@ -992,8 +1091,8 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         seed: int = 0, experts: int = 0, experts_active: int = MOE_MAX_ACTIVE) -> dict:
     if why := moe_refusal(workload, experts, experts_active):
         raise SystemExit(why)
-    if workload == "prefill" and (why := prefill_refusal(batch, chunk, context)):
-        raise SystemExit(f"--workload prefill: {why}")
+    if workload in ("prefill", "prefill-moe") and (why := prefill_refusal(batch, chunk, context)):
+        raise SystemExit(f"--workload {workload}: {why}")
     if workload == "generate" and (why := generate_refusal(batch, vocab)):
         raise SystemExit(f"--workload generate: {why}")
     import torch
@@ -1027,10 +1126,10 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     m = n = k = size
     if dtype not in ("bf16", "fp8", "mxfp4"):
         raise SystemExit(f"--dtype {dtype}: bf16, fp8 or mxfp4")
-    if workload not in ("gemm", "decode", "attn", "server", "layer", "prefill", "generate"):
-        raise SystemExit(f"--workload {workload}: gemm, decode, attn, server, layer, prefill or generate")
+    if workload not in ("gemm", "decode", "attn", "server", "layer", "prefill", "prefill-moe", "generate"):
+        raise SystemExit(f"--workload {workload}: gemm, decode, attn, server, layer, prefill, prefill-moe or generate")
     decode = workload == "decode"
-    prefill = workload == "prefill"
+    prefill = workload in ("prefill", "prefill-moe")  # the MoE form is the same layer with another MLP
     generate = workload == "generate"
     layer = workload == "layer" or generate  # the generate workload is the layer workload between tokens
     server = workload == "server" or layer  # the layer workload is the server workload with more in a layer
@@ -1082,15 +1181,19 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     finite = None
     if prefill:
         weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
-        one_layer_bytes = layer_weight_bytes(heads, kv_heads, ffn)
+        active = moe_active(experts, experts_active)
+        one_layer_bytes = (moe_layer_weight_bytes(heads, kv_heads, ffn, experts) if experts
+                           else layer_weight_bytes(heads, kv_heads, ffn))
         w_layers = ring_layers(weights_bytes, one_layer_bytes)
         kv_layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB),
                                    kv_layer_bytes(kv_dtype, batch, context, kv_heads))
         layers = max(w_layers, kv_layers)
         step, sync, finite = prefill_steps(torch, kl, gs, dev, kv_dtype, batch, chunk, context, heads, kv_heads, page,
-                                           ffn, w_layers, kv_layers)
-        # the projections (2 flops per weight and row: a weight is 2 bytes), and QK^T and PV over the visible pairs
-        flops_attn = layers * (batch * chunk * one_layer_bytes
+                                           ffn, w_layers, kv_layers, experts=experts, active=active)
+        # the projections (2 flops per weight and row: a weight is 2 bytes), and QK^T and PV over the visible pairs;
+        # with experts a row meets the dense part, the router and its `active` experts: real pairs only, no padding
+        row_bytes = moe_layer_read_bytes(heads, kv_heads, ffn, experts, active) if experts else one_layer_bytes
+        flops_attn = layers * (batch * chunk * row_bytes
                                + 4.0 * ATTN_D * heads * prefill_visible_pairs(batch, chunk, context))
     elif server:
         weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
@@ -1207,6 +1310,9 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
                     "kv_layers": kv_layers, "context": context, "heads": heads, "kv_heads": kv_heads,
                     "kv_dtype": kv_dtype, "page": page, "ffn": ffn, "tbps": done * step_bytes / el / 1e12,
                     "tokens_per_s": done * batch * chunk / el, "activations_finite": finite()})
+        if experts:  # how much of the grouped GEMM's 128-row tiles the last step's routing left empty
+            n_tiles, real = step.plan_header()
+            out.update({"experts": experts, "experts_active": active, "pad_share": 1.0 - real / (128.0 * n_tiles)})
     elif server:
         step_bytes = layers * (one_layer_bytes + kv_layer_bytes(kv_dtype, batch, context, kv_heads))
         out.update({"workload": workload, "batch": batch, "layers": layers, "weight_layers": w_layers,
@@ -1259,7 +1365,7 @@ class _Parser(argparse.ArgumentParser):
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
         scenarios = getattr(ns, "scenarios", "").split(",")
-        wide = ns.workload in ("attn", "prefill") or any(sc.startswith("attn-") for sc in scenarios)
+        wide = ns.workload in ("attn", "prefill", "prefill-moe") or any(sc.startswith("attn-") for sc in scenarios)
         top = 256 if wide else 16
         if not 1 <= ns.batch <= top:
             self.error(f"argument --batch: {ns.batch} is not in 1..{top} (--workload {ns.workload})")
@@ -1267,15 +1373,15 @@ class _Parser(argparse.ArgumentParser):
             self.error(f"--workload generate: {why}")
         if why := moe_refusal(ns.workload, getattr(ns, "experts", 0), getattr(ns, "experts_active", MOE_MAX_ACTIVE)):
             self.error(why)
-        if ns.workload == "prefill":
+        if ns.workload in ("prefill", "prefill-moe"):
             # --context means something else here, the length AFTER the chunk, and the chunk's place follows from it:
             # the other workloads' default is not taken over silently
             given = sys.argv[1:] if args is None else args
             if not any(len(a.split("=")[0]) >= 5 and "--context".startswith(a.split("=")[0]) for a in given):
-                self.error("--workload prefill: give --context, the length after the chunk (the chunk lands at "
+                self.error(f"--workload {ns.workload}: give --context, the length after the chunk (the chunk lands at "
                            "[context - chunk, context))")
             if why := prefill_refusal(ns.batch, ns.chunk, ns.context):
-                self.error(f"--workload prefill: {why}")
+                self.error(f"--workload {ns.workload}: {why}")
         return ns
 
 
@@ -1311,7 +1417,7 @@ def add_moe_arguments(ap: argparse.ArgumentParser) -> None:
     """The options of the MoE form of ``--workload layer`` and ``generate`` (shared with the isolation harness)."""
     ap.add_argument("--experts", type=int, default=0,
                     help="--workload layer and generate: experts of the MLP, each --ffn wide (0: a dense MLP; otherwise "
-                         "a multiple of 16 up to 1024)")
+                         "a multiple of 16 up to 1024); --workload prefill-moe: a multiple of 128 up to 1024")
     ap.add_argument("--experts-active", type=int, default=MOE_MAX_ACTIVE,
                     help="--experts > 0: experts a token picks, 1..8, capped at --experts")
 
@@ -1329,7 +1435,7 @@ def build_parser() -> argparse.ArgumentParser:
                          "quantised from bf16 by the library; --kernel gsx only); the output stays bf16")
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--workload", default="gemm",
-                    choices=["gemm", "decode", "attn", "server", "layer", "prefill", "generate"],
+                    choices=["gemm", "decode", "attn", "server", "layer", "prefill", "prefill-moe", "generate"],
                     help="gemm: one large square GEMM per step (compute-bound); decode: --batch activation rows "
                          "against a ring of --size x --size weight matrices, one launch each (HBM-bandwidth-bound); "
                          "attn: one decode step of attention per layer over a ring of paged KV caches; server: a "
@@ -1337,7 +1443,8 @@ def build_parser() -> argparse.ArgumentParser:
                          "projection) over caches that grow; layer: a whole decoder layer per ring layer (the server "
                          "workload's with a residual stream, two RMSNorms and the SwiGLU MLP); prefill: the same layer on "
                          "--batch sequences of --chunk new tokens each, causal attention over the paged cache "
-                         "(compute-bound); generate: the layer workload closed into generation: the embedding lookup of "
+                         "(compute-bound); prefill-moe: that prefill layer with a mixture-of-experts MLP (--experts, a "
+                         "multiple of 128; --experts-active) on the grouped 128x128 GEMM; generate: the layer workload closed into generation: the embedding lookup of "
                          "the last step's tokens, the layers, a final RMSNorm, the LM head (--vocab columns) and the "
                          "sampler, token to token through device memory")
     ap.add_argument("--batch", type=int, default=8, metavar="N",

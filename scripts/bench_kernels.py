@@ -4,7 +4,8 @@ GEMM (every configuration vs torch and a read-bandwidth yardstick), the decode a
 configuration and split count vs torch SDPA and the same yardstick), RoPE + KV append and the fused add + RMSNorm and
 SwiGLU (vs a read-and-rewrite yardstick), the causal prefill attention over the paged cache (vs torch SDPA on a
 contiguous copy), the sampler, the MoE router, grouped expert GEMM and combine (vs one plain decode GEMM per active
-expert and the read yardstick), HBM fill, stamp/verify."""
+expert and the read yardstick), the MoE prefill router, tile plan, grouped 128x128 GEMM and combine (vs the dense
+128x128 configuration at equal padded rows), HBM fill, stamp/verify."""
 import json
 import math
 import os
@@ -1055,6 +1056,105 @@ def moe(shapes=MOE_SHAPES, ms=(1, 8, 16), kinds=("bf16", "fp8", "mxfp4"), ring_b
     return out
 
 
+def moe_prefill(shapes=((2048, 768, 128, 8), (4096, 14336, 8, 2)), ms=(1024, 8192), rounds=3, window_ms=30.0):
+    """The MoE prefill kernels.  Routing comes from random router weights and inputs through ``moe_prefill_route`` and
+    ``moe_prefill_plan``.  Per shape, ``m`` and projection the grouped 128x128 GEMM is timed against the dense
+    ``128x128/4w`` configuration at ``128 * n_tiles`` rows with the same N and K (the same MFMA work without the gather
+    and the row-scattered stores; its B is one expert's matrix, so it reads fewer weights), the two interleaved in one
+    process: the median of ``rounds`` windows of about ``window_ms`` each after a warm-up, and their spread.
+    ``tflops_real`` counts the P real pairs, ``tflops_padded`` the padded rows; ``route_us``, ``plan_us`` and
+    ``combine_us`` are per call."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    dense = {name: i for i, name in hip.gemm_cfgs().items()}["128x128/4w"]
+
+    def windows(call):
+        """``(iters, one)``: ``one(iters)`` times a window of ``iters`` calls by the stream's events and gives the
+        milliseconds per call; ``iters`` fills ``window_ms``, from a first window of 3 calls."""
+        def one(iters):
+            with torch.cuda.stream(ts):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(ts)
+                for _ in range(iters):
+                    call()
+                e1.record(ts)
+            e1.synchronize()
+            return e0.elapsed_time(e1) / iters
+        iters = max(5, min(500, int(window_ms / max(one(3), 1e-3))))
+        return iters, one
+
+    for hidden, ffn, e, topk in shapes:
+        gen = torch.Generator(device="cuda").manual_seed(hidden + e)
+        rw = torch.randn(e, hidden, device="cuda", generator=gen) / math.sqrt(hidden)
+        proj = {"up": (2 * ffn, hidden), "down": (hidden, ffn)}  # name: (N, K)
+        w = {}
+        for name, (n, k) in proj.items():
+            w[name] = torch.empty(e * n, k, device="cuda", dtype=torch.bfloat16)
+            for x0 in range(e):  # an expert at a time: nothing larger is held in fp32
+                w[name][x0 * n:(x0 + 1) * n].copy_(torch.randn(n, k, device="cuda", generator=gen) / math.sqrt(k))
+        for m in ms:
+            pairs = m * topk
+            xin = torch.randn(m, hidden, device="cuda", generator=gen)
+            logits = (xin @ rw.t()).bfloat16().contiguous()
+            ids = torch.empty(pairs, device="cuda", dtype=torch.int32)
+            tw = torch.empty(pairs, device="cuda", dtype=torch.float32)
+            plan = torch.empty(hip.moe_prefill_plan_ints(m, topk, e), device="cuda", dtype=torch.int32)
+            wsb = hip.moe_prefill_workspace_bytes(m, topk, e)
+            ws = torch.empty(wsb // 4, device="cuda", dtype=torch.int32)
+            torch.cuda.synchronize()
+            route = (s, logits.data_ptr(), e, ids.data_ptr(), tw.data_ptr(), m, e, topk)
+            mkplan = (s, ids.data_ptr(), plan.data_ptr(), m, topk, e, ws.data_ptr(), wsb)
+            hip.moe_prefill_route(*route)
+            hip.moe_prefill_plan(*mkplan)
+            s.sync()
+            n_tiles = int(plan[0].item())
+            base = {"hidden": hidden, "ffn": ffn, "experts": e, "topk": topk, "m": m, "pairs": pairs,
+                    "n_tiles": n_tiles, "pad_share": round(1 - pairs / (128 * n_tiles), 4),
+                    "route_us": round(hip.time_moe_prefill_route(*route, 50) / 50 * 1e3, 2),
+                    "plan_us": round(hip.time_moe_prefill_plan(*mkplan, 50) / 50 * 1e3, 2)}
+            yb = torch.randn(pairs, hidden, device="cuda", dtype=torch.bfloat16)
+            ob = torch.empty(m, hidden, device="cuda", dtype=torch.bfloat16)
+            torch.cuda.synchronize()
+            base["combine_us"] = round(hip.time_moe_prefill_combine(s, yb.data_ptr(), hidden, tw.data_ptr(),
+                                                                    ob.data_ptr(), hidden, m, topk, hidden, 50) / 50 * 1e3, 2)
+            del yb, ob
+            for name, (n, k) in proj.items():
+                a_div = topk if name == "up" else 1
+                a = torch.randn(pairs // a_div, k, device="cuda", dtype=torch.bfloat16)
+                c = torch.empty(pairs, n, device="cuda", dtype=torch.bfloat16)
+                mp = 128 * n_tiles
+                da = torch.randn(mp, k, device="cuda", dtype=torch.bfloat16)
+                dc = torch.empty(mp, n, device="cuda", dtype=torch.bfloat16)
+                torch.cuda.synchronize()
+                calls = {"grouped": lambda: hip.moe_prefill_gemm_nt(s, a.data_ptr(), a_div, w[name].data_ptr(),
+                                                                    c.data_ptr(), plan.data_ptr(), m, topk, e, n, k),
+                         "dense": lambda: hip.gemm_bf16_nt_cfg(s, da.data_ptr(), w[name].data_ptr(), dc.data_ptr(), mp,
+                                                               n, k, dense)}
+                timers = {v: windows(call) for v, call in calls.items()}  # this is the warm-up too
+                got = {v: [] for v in calls}
+                for _ in range(rounds):
+                    for v, (iters, one) in timers.items():  # interleaved
+                        got[v].append(one(iters))
+                med = {v: statistics.median(t) for v, t in got.items()}
+                row = {**base, "proj": name, "n": n, "k": k}
+                for v in calls:
+                    row[f"{v}_ms"] = round(med[v], 4)
+                    row[f"{v}_spread"] = round((max(got[v]) - min(got[v])) / med[v], 4)
+                row["grouped_over_dense"] = round(med["grouped"] / med["dense"], 4)
+                row["tflops_real"] = round(2.0 * pairs * n * k / med["grouped"] / 1e9, 1)
+                row["tflops_padded"] = round(2.0 * mp * n * k / med["grouped"] / 1e9, 1)
+                row["dense_tflops"] = round(2.0 * mp * n * k / med["dense"] / 1e9, 1)
+                out.append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                del a, c, da, dc
+            torch.cuda.empty_cache()
+        del w
+        torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 def hbm(nbytes=16 << 30, reps=5):
     s = hip.Stream(0)
     buf = hip.DeviceBuffer(0, nbytes)
@@ -1090,6 +1190,7 @@ if __name__ == "__main__":
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
                 "moe": moe, "moe_128": lambda: moe(shapes=MOE_SHAPES[:1]),  # the 128-expert shape alone
+                "moe_prefill": moe_prefill,
                 "hbm": hbm}
     only = sys.argv[2].split(",") if len(sys.argv) > 2 else list(sections)  # [out.json [section,section..]]
     res = {name: sections[name]() for name in only}
