@@ -141,6 +141,8 @@ def lib():
         _pf_plan_sig = [vp, vp, vp, i32, i32, i32, vp, u64]
         # stream, A, a_div, B, C, plan; M, topk, E, N, K
         _pf_gemm_sig = [vp, vp, i32, vp, vp, vp] + [i32] * 5
+        # stream, kind, A, B, C; M, N, K; scale_a, scale_b, scale_mode; workspace, workspace_bytes
+        _skinny_sig = [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, u64]
         sig = {
             "gsx_last_error": ([], ctypes.c_char_p),
             "gsx_device_count": ([ctypes.POINTER(i32)], i32),
@@ -184,6 +186,13 @@ def lib():
             "gsx_decode_gemm_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
             "gsx_event_time_decode_gemm": ([vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32,
                                             ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_skinny_gemm_nt": (_skinny_sig, i32),
+            "gsx_skinny_gemm_workspace_bytes": ([i32, i32, i32, ctypes.POINTER(u64)], i32),
+            "gsx_skinny_gemm_pick": ([i32] * 4 + [ctypes.POINTER(i32)] * 2, i32),
+            "gsx_skinny_gemm_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_skinny_gemm_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
+            "gsx_skinny_gemm_nt_launch_cfg": ([*_skinny_sig, i32, i32], i32),
+            "gsx_event_time_skinny_gemm": ([*_skinny_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_decode_attn": (_attn_sig, i32),
             "gsx_decode_attn_launch_cfg": ([*_attn_sig, i32, i32], i32),
             "gsx_decode_attn_workspace_bytes": ([i32] * 5 + [ctypes.POINTER(u64)], i32),
@@ -658,6 +667,69 @@ def time_decode_gemm(stream: Stream, kind: str, a: int, b: int, c: int, m: int, 
     ms = ctypes.c_float(0)
     _ck(lib().gsx_event_time_decode_gemm(*_decode_args(stream, kind, a, b, c, m, n, k, scale_a, scale_b, scale_mode),
                                          iters, ctypes.byref(ms)), "time_decode_gemm")
+    return ms.value
+
+
+def _skinny_args(stream: Stream, kind: str, a: int, b: int, c: int, m: int, n: int, k: int, scale_a: int,
+                 scale_b: int, scale_mode: int, workspace: int, workspace_bytes: int) -> tuple:
+    return (*_decode_args(stream, kind, a, b, c, m, n, k, scale_a, scale_b, scale_mode), ctypes.c_void_p(workspace),
+            workspace_bytes)
+
+
+def skinny_gemm_nt(stream: Stream, kind: str, a: int, b: int, c: int, m: int, n: int, k: int, scale_a: int = 0,
+                   scale_b: int = 0, scale_mode: int = SCALE_NONE, workspace: int = 0, workspace_bytes: int = 0):
+    """``C[m][n]`` (bf16) ``= A[m][k] * B[n][k]^T`` for ``1 <= m <= 128``: the skinny GEMM, which streams ``b`` from
+    HBM once.  ``kind`` is ``"bf16"`` or ``"fp8"`` with the scales of :func:`decode_gemm_nt`; ``"mxfp4"`` is refused.
+    ``workspace`` is device memory of at least :func:`skinny_gemm_workspace_bytes` bytes for the partials of the split
+    of K.  Not synchronised."""
+    _ck(lib().gsx_skinny_gemm_nt(*_skinny_args(stream, kind, a, b, c, m, n, k, scale_a, scale_b, scale_mode,
+                                               workspace, workspace_bytes)), "skinny_gemm_nt")
+
+
+def skinny_gemm_workspace_bytes(m: int, n: int, k: int) -> int:
+    """Bytes of workspace :func:`skinny_gemm_nt` can need for this shape, whatever the kind (0: none)."""
+    v = ctypes.c_uint64(0)
+    _ck(lib().gsx_skinny_gemm_workspace_bytes(m, n, k, ctypes.byref(v)), "skinny_gemm_workspace_bytes")
+    return v.value
+
+
+def skinny_gemm_pick(kind: str, m: int, n: int, k: int) -> tuple[int, int]:
+    """``(cfg, splits)`` that :func:`skinny_gemm_nt` takes for this kind and shape."""
+    cfg, splits = ctypes.c_int(0), ctypes.c_int(0)
+    _ck(lib().gsx_skinny_gemm_pick(_decode_kind(kind), m, n, k, ctypes.byref(cfg), ctypes.byref(splits)),
+        "skinny_gemm_pick")
+    return cfg.value, splits.value
+
+
+def skinny_gemm_cfgs() -> dict[int, tuple[str, int, int, int]]:
+    """``{index: (name, bn, waves, inflight)}`` of the skinny configurations, read from the library's table
+    (native/kernels/gemm_skinny.hip)."""
+    out: dict[int, tuple[str, int, int, int]] = {}
+    while (name := lib().gsx_skinny_gemm_cfg_name(len(out))) is not None:
+        v = [ctypes.c_int(0) for _ in range(3)]
+        if lib().gsx_skinny_gemm_cfg_shape(len(out), *map(ctypes.byref, v)) != 0:
+            raise HipError(f"skinny cfg {len(out)} has a name and no shape")
+        out[len(out)] = (name.decode(), *(x.value for x in v))
+    return out
+
+
+def skinny_gemm_nt_cfg(stream: Stream, kind: str, a: int, b: int, c: int, m: int, n: int, k: int, cfg: int,
+                       splits: int, scale_a: int = 0, scale_b: int = 0, scale_mode: int = SCALE_NONE,
+                       workspace: int = 0, workspace_bytes: int = 0):
+    """Launch one configuration of the skinny GEMM with ``splits`` (1..16) splits of K; the workspace needs
+    ``splits * m * n * 4`` bytes when ``splits > 1``.  An unknown config raises HipError."""
+    _ck(lib().gsx_skinny_gemm_nt_launch_cfg(*_skinny_args(stream, kind, a, b, c, m, n, k, scale_a, scale_b,
+                                                          scale_mode, workspace, workspace_bytes), cfg, splits),
+        f"skinny gemm cfg {cfg} splits {splits}")
+
+
+def time_skinny_gemm(stream: Stream, kind: str, a: int, b: int, c: int, m: int, n: int, k: int, iters: int,
+                     scale_a: int = 0, scale_b: int = 0, scale_mode: int = SCALE_NONE, workspace: int = 0,
+                     workspace_bytes: int = 0) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_skinny_gemm(*_skinny_args(stream, kind, a, b, c, m, n, k, scale_a, scale_b, scale_mode,
+                                                       workspace, workspace_bytes), iters, ctypes.byref(ms)),
+        "time_skinny_gemm")
     return ms.value
 
 

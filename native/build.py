@@ -12,7 +12,8 @@ Targets (outputs land in ``gpushare_scheduler_extender_amd/_native/``):
                 ROCm-SMI copy bundled inside the torch wheel).
 * ``kernels`` – HIP/CDNA4 kernels for gfx950 (``libgsx_kernels.so``): CU probe,
                 HBM touch/verify, HBM memory test, compute (MFMA / VALU / LDS) test, bf16, fp8 and MXFP4 MFMA GEMM
-                workload with the MXFP4 quantiser, the decode GEMM (M <= 16) on the same operands, decode attention over a
+                workload with the MXFP4 quantiser, the decode GEMM (M <= 16) on the same operands, the skinny GEMM
+                (M <= 128, bf16 and fp8, with a split of K; gemm_skinny.hip), decode attention over a
                 paged KV cache (attn_decode.hip), RoPE + KV-cache append (kv_append.hip), fused residual add + RMSNorm
                 and SwiGLU (norm_act.hip), causal prefill attention over the same cache (attn_prefill.hip), the token
                 sampler and the embedding gather (sample.hip), the MoE router and combine (moe.hip; the grouped expert
@@ -183,8 +184,10 @@ def _hipcc() -> str:
 KERNELS = NATIVE / "kernels"
 # Per-source flags on top of the common set.  moe_prefill.hip is compiled without the packed fp32 instructions
 # (v_pk_add_f32, v_pk_mul_f32, v_pk_fma_f32): its router and combine round every operation on its own, and the scalar
-# forms are the ones their contracts were written against.  The older sources keep the flags they were measured with.
-HIP_EXTRA = {"moe_prefill": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# forms are the ones their contracts were written against.  gemm_skinny.hip likewise: its partial sums and its two-step
+# epilogue round one operation at a time.  The older sources keep the flags they were measured with.
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+HIP_EXTRA = {"moe_prefill": _NO_PACKED_FP32, "gemm_skinny": _NO_PACKED_FP32}
 _hip_forced: set[Path] = set()  # what a --force has compiled in this process already
 
 

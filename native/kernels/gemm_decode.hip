@@ -50,19 +50,6 @@
 
 namespace gsxgemm {
 
-// one 16-B chunk from global memory; NT: with the non-temporal hint (the line is not kept for a second use)
-template <class FRAG, bool NT>
-__device__ __forceinline__ FRAG load_chunk(const void* p) {
-  const i32x4* q = static_cast<const i32x4*>(p);
-  const i32x4 v = NT ? __builtin_nontemporal_load(q) : *q;
-  return __builtin_bit_cast(FRAG, v);
-}
-
-// A raw buffer over `bytes` bytes at `base`: a load at or past the end returns zeros and touches nothing.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_buffer(const void* base, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, static_cast<int>(bytes), 0x00020000);
-}
-
 // What the grouped form (gsx_moe_gemm_nt) passes instead of NoGroup: a plan in device memory, which gsx_moe_route
 // wrote, or anyone.  Workgroup (strip, slot); grid.y is min(E, P) <= 128.
 struct MoePlan {

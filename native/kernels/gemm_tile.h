@@ -165,6 +165,20 @@ __device__ __forceinline__ uint32_t swz(int row, int chunk) {  // in bytes, from
   return static_cast<uint32_t>(row * ROW_BYTES + ((chunk ^ ((row >> 1) & 7)) << 4));
 }
 
+// What the kernels that stream B past LDS share (gemm_decode.hip, gemm_skinny.hip).
+// one 16-B chunk from global memory; NT: with the non-temporal hint (the line is not kept for a second use)
+template <class FRAG, bool NT>
+__device__ __forceinline__ FRAG load_chunk(const void* p) {
+  const i32x4* q = static_cast<const i32x4*>(p);
+  const i32x4 v = NT ? __builtin_nontemporal_load(q) : *q;
+  return __builtin_bit_cast(FRAG, v);
+}
+
+// A raw buffer over `bytes` bytes at `base`: a load at or past the end returns zeros and touches nothing.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_buffer(const void* base, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, static_cast<int>(bytes), 0x00020000);
+}
+
 __device__ __forceinline__ uint16_t f2bf(float f) {
   uint32_t u = __float_as_uint(f);
   if ((u & 0x7f800000u) == 0x7f800000u) return static_cast<uint16_t>((u >> 16) | ((u & 0xffff) ? 0x40 : 0));

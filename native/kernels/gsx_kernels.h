@@ -27,6 +27,8 @@
 //  * decode GEMM / attention — an inference server's decode step: M <= 16 rows against
 //                          weights streamed from HBM (gemm_decode.hip), attention
 //                          over a paged KV cache in bf16 or e4m3 (attn_decode.hip);
+//  * skinny GEMM         — 17 to 128 rows (any M <= 128) against weights streamed from HBM
+//                          once, bf16 and e4m3, with a split of K (gemm_skinny.hip);
 //  * RoPE + KV append    — rotates Q and K and writes the new tokens' K and V into
 //                          their page slots, quantised for an e4m3 cache: what makes
 //                          the cache the attention reads (kv_append.hip);
@@ -221,6 +223,47 @@ int gsx_decode_gemm_nt_launch_cfg(void* stream, int kind, const void* A, const v
 // elapsed milliseconds of `iters` back-to-back gsx_decode_gemm_nt on `stream`, by hip events (for benches)
 int gsx_event_time_decode_gemm(void* stream, int kind, const void* A, const void* B, void* C, int M, int N, int K,
                                const void* scale_a, const void* scale_b, int scale_mode, int iters, float* ms);
+
+// Skinny GEMM (gemm_skinny.hip): C[M][N] (bf16) = A[M][K] * B[N][K]^T with 1 <= M <= 128, the row counts between the
+// decode GEMM and the large GEMMs: a server that decodes up to 128 sequences at once.  B is read from HBM once, straight
+// to the MFMA's registers.  A workgroup owns a strip of 32 or 64 columns, all ceil(M / 16) row fragments and one of
+// `splits` runs of K; its waves split the run.  With splits > 1 the workgroups store fp32 partials to `workspace`,
+// part[split][M][N], and a second launch on the same stream adds them in the order of the split index and applies the
+// epilogue; with splits == 1 there is one launch and the workspace may be NULL.  No atomics.
+//   GSX_DECODE_BF16 and GSX_DECODE_FP8   operands, scales, scale modes and epilogue exactly as gsx_decode_gemm_nt
+//                                        takes them: c = bf16((acc * sa) * sb); K % 64 == 0 and K % 128 == 0
+//   GSX_DECODE_MXFP4                     is refused ("mxfp4 is not supported by the skinny GEMM")
+// Requirements: 1 <= M <= 128; N % 64 == 0 (_launch_cfg: N % BN == 0 too); 1 <= splits <= 16; A, B, C and the workspace
+// 16-B aligned, A, B and C not NULL; the workspace holds splits * M * N * 4 bytes when splits > 1 (a smaller one is
+// refused with the bytes needed in the text); ceil(M / 16) * 16 rows of A stay below 4 GiB (a 32-bit buffer range),
+// which limits K beyond what an int does; C overlaps none of A, B, the scales and the workspace.  Nothing is read of A or
+// scale_a past row M - 1 and nothing written of C past it: rows past M cost no MFMA beyond the last fragment of 16.
+// Row offsets into B, scale_b, C and the workspace are 64-bit (B may exceed 4 GiB).
+// Accumulation is fp32 with one rounding to bf16, in a fixed order: a wave's K-tiles, the waves of a workgroup by
+// index, the splits by index.  The result depends on the configuration and on `splits` and on nothing else: row i has
+// the same bits at every M that contains it, wherever workgroups run.  gsx_skinny_gemm_nt picks both by ceil(M / 16), N
+// and K (skinny_pick() in gemm_skinny.hip; _pick returns its choice), so its result for a row can change where M
+// crosses 64.  Launches on `stream` and returns without synchronising; everything is validated before the first device
+// call.
+int gsx_skinny_gemm_nt(void* stream, int kind, const void* A, const void* B, void* C, int M, int N, int K,
+                       const void* scale_a, const void* scale_b, int scale_mode, void* workspace,
+                       uint64_t workspace_bytes);
+// bytes of workspace gsx_skinny_gemm_nt can need for this shape, whatever the kind (0: none)
+int gsx_skinny_gemm_workspace_bytes(int M, int N, int K, uint64_t* bytes);
+// the configuration and the splits gsx_skinny_gemm_nt takes for this kind and shape
+int gsx_skinny_gemm_pick(int kind, int M, int N, int K, int* cfg, int* splits);
+// The skinny configurations, one table for both kinds: 0 "32/4w-f2", 1 "64/4w-f2", 2 "64/4w-f3": columns of a strip
+// (BN) / waves per workgroup - K-tiles a wave keeps in flight.  _cfg_name returns NULL and _cfg_shape nonzero outside
+// the table.  _launch_cfg runs one configuration with `splits` splits of K.
+const char* gsx_skinny_gemm_cfg_name(int cfg);
+int gsx_skinny_gemm_cfg_shape(int cfg, int* bn, int* waves, int* inflight);
+int gsx_skinny_gemm_nt_launch_cfg(void* stream, int kind, const void* A, const void* B, void* C, int M, int N, int K,
+                                  const void* scale_a, const void* scale_b, int scale_mode, void* workspace,
+                                  uint64_t workspace_bytes, int cfg, int splits);
+// elapsed milliseconds of `iters` back-to-back gsx_skinny_gemm_nt on `stream`, by hip events (for benches)
+int gsx_event_time_skinny_gemm(void* stream, int kind, const void* A, const void* B, void* C, int M, int N, int K,
+                               const void* scale_a, const void* scale_b, int scale_mode, void* workspace,
+                               uint64_t workspace_bytes, int iters, float* ms);
 
 // Decode attention over a paged KV cache (attn_decode.hip): one new token per sequence, grouped-query attention in
 // which Hq query heads share Hkv KV heads in groups of G = Hq / Hkv.

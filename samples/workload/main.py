@@ -22,6 +22,10 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   come from HBM every time: the work is bound by memory bandwidth, and the result reports ``tbps``, the weight and
   weight-scale bytes streamed per second, next to ``tflops``.  The library's decode GEMM, or ``torch.matmul`` /
   ``torch._scaled_mm`` on the same ring;
+* ``--workload decode-wide`` is the decode workload at the row counts of continuous batching: ``--batch`` (1..128)
+  rows against the same ring through the library's skinny GEMM (``gsx_skinny_gemm_nt``), whose workspace for the split
+  of K is allocated once.  ``--dtype`` is bf16 or fp8 (the skinny GEMM has no mxfp4 form); ``--kernel torch`` runs the
+  decode workload's comparator.  It reports the decode workload's fields;
 * ``--workload attn`` is the other half of a decode step: attention of one new token per sequence over a paged KV
   cache.  ``--batch`` sequences (1..256) of ``--context`` tokens each, ``--heads`` query heads sharing ``--kv-heads``
   KV heads at D = 128, pages of ``--page`` tokens handed out through a random permutation, as an allocator leaves
@@ -267,6 +271,10 @@ class Kernels:
         if hasattr(L, "gsx_decode_gemm_nt"):  # likewise: an image built before the decode kernels
             L.gsx_decode_gemm_nt.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32]
             L.gsx_decode_gemm_nt.restype = i32
+        if hasattr(L, "gsx_skinny_gemm_nt"):  # likewise: an image built before the skinny GEMM
+            L.gsx_skinny_gemm_nt.argtypes = [*L.gsx_decode_gemm_nt.argtypes, vp, ctypes.c_uint64]
+            L.gsx_skinny_gemm_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_uint64)]
+            L.gsx_skinny_gemm_nt.restype = L.gsx_skinny_gemm_workspace_bytes.restype = i32
         if hasattr(L, "gsx_decode_attn"):  # likewise: an image built before the attention kernel
             L.gsx_decode_attn.argtypes = ([vp, i32] + [vp] * 6 + [i32] * 8 + [ctypes.c_float] * 3
                                           + [vp, ctypes.c_uint64])
@@ -365,6 +373,19 @@ class Kernels:
         self._ck(self.L.gsx_decode_gemm_nt(s, DECODE_KINDS[dtype], ctypes.c_void_p(a), ctypes.c_void_p(b),
                                            ctypes.c_void_p(c), m, n, k, ctypes.c_void_p(sa), ctypes.c_void_p(sb), 0),
                  "decode_gemm_nt")
+
+    def skinny_workspace_bytes(self, m: int, n: int, k: int) -> int:
+        if not hasattr(self.L, "gsx_skinny_gemm_nt"):
+            raise RuntimeError(f"{self.path} has no gsx_skinny_gemm_nt: rebuild it")
+        v = ctypes.c_uint64(0)
+        self._ck(self.L.gsx_skinny_gemm_workspace_bytes(m, n, k, ctypes.byref(v)), "skinny_gemm_workspace_bytes")
+        return v.value
+
+    def skinny_gemm(self, s, dtype: str, a: int, b: int, c: int, m: int, n: int, k: int, ws: int, ws_bytes: int):
+        """``c[m][n] = a[m][k] * b[n][k]^T`` for m <= 128, bf16 or fp8 without scales."""
+        self._ck(self.L.gsx_skinny_gemm_nt(s, DECODE_KINDS[dtype], ctypes.c_void_p(a), ctypes.c_void_p(b),
+                                           ctypes.c_void_p(c), m, n, k, None, None, 0, ctypes.c_void_p(ws), ws_bytes),
+                 "skinny_gemm_nt")
 
     def attn_workspace_bytes(self, b: int, hq: int, page: int, max_seq_len: int) -> int:
         if not hasattr(self.L, "gsx_decode_attn"):
@@ -558,11 +579,12 @@ class Kernels:
         self.L.gsx_stream_destroy(s)
 
 
-def decode_steps(torch, kl, gs, stream, dev, dtype: str, a, c, layers: int):
+def decode_steps(torch, kl, gs, stream, dev, dtype: str, a, c, layers: int, wide: bool = False):
     """``(step, sync)`` of the decode workload: the ring of ``layers`` weight matrices ``[n][k]`` (random normal, made
     one at a time so that nothing larger than one matrix is ever held in bf16), and a step that multiplies the ``m``
     activation rows ``a`` by each of them in turn into ``c``.  ``kl`` and ``gs`` are the library and its stream, or
-    None for torch's own GEMMs (on ``stream`` if there is one)."""
+    None for torch's own GEMMs (on ``stream`` if there is one).  ``wide``: the library's skinny GEMM (up to 128 rows)
+    instead of its decode GEMM, with one workspace for all launches."""
     m, k = a.shape
     n = c.shape[1]
     wdt = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn, "mxfp4": torch.uint8}[dtype]
@@ -588,6 +610,20 @@ def decode_steps(torch, kl, gs, stream, dev, dtype: str, a, c, layers: int):
             a_ptr, sa_ptr, s_bytes = qa.data_ptr(), sa.data_ptr(), ws[0].numel()
         else:
             a_ptr, sa_ptr, s_bytes, ws = a.data_ptr(), 0, 0, None
+        if wide:
+            part_bytes = kl.skinny_workspace_bytes(m, n, k)
+            part = torch.empty(max(part_bytes, 16), device=dev, dtype=torch.uint8)
+
+            def step():
+                for i in range(layers):
+                    kl.skinny_gemm(gs, dtype, a_ptr, w.data_ptr() + i * w_bytes, c.data_ptr(), m, n, k,
+                                   part.data_ptr(), part_bytes)
+
+            def sync():
+                kl.sync(gs)
+
+            step.keep = (w, a, part)
+            return step, sync
 
         def step():
             for i in range(layers):
@@ -1126,9 +1162,12 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     m = n = k = size
     if dtype not in ("bf16", "fp8", "mxfp4"):
         raise SystemExit(f"--dtype {dtype}: bf16, fp8 or mxfp4")
-    if workload not in ("gemm", "decode", "attn", "server", "layer", "prefill", "prefill-moe", "generate"):
-        raise SystemExit(f"--workload {workload}: gemm, decode, attn, server, layer, prefill, prefill-moe or generate")
-    decode = workload == "decode"
+    if workload not in ("gemm", "decode", "decode-wide", "attn", "server", "layer", "prefill", "prefill-moe",
+                        "generate"):
+        raise SystemExit(f"--workload {workload}: gemm, decode, decode-wide, attn, server, layer, prefill, prefill-moe "
+                         "or generate")
+    wide = workload == "decode-wide"  # the decode workload on the skinny GEMM
+    decode = workload == "decode" or wide
     prefill = workload in ("prefill", "prefill-moe")  # the MoE form is the same layer with another MLP
     generate = workload == "generate"
     layer = workload == "layer" or generate  # the generate workload is the layer workload between tokens
@@ -1158,8 +1197,10 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
             raise SystemExit(f"--page {page}: a multiple of 16 in 16..256")
         m, n, k = batch, heads, ATTN_D  # nothing of the GEMM's operands is needed: keep them tiny
     if decode:
-        if not 1 <= batch <= 16:
-            raise SystemExit(f"--batch {batch}: 1..16")
+        if not 1 <= batch <= (128 if wide else 16):
+            raise SystemExit(f"--batch {batch}: 1..{128 if wide else 16}")
+        if wide and dtype == "mxfp4":
+            raise SystemExit("--workload decode-wide --dtype mxfp4: the skinny GEMM takes bf16 and fp8 only")
         m = batch
     if dtype == "mxfp4" and kernel != "gsx":
         raise SystemExit("--dtype mxfp4 needs the library's kernels (--kernel gsx): "
@@ -1233,7 +1274,7 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
         layers = ring_layers(weights_bytes, matrix_bytes(dtype, n, k))
         step, sync = decode_steps(torch, kl if kernel == "gsx" else None, gs if kernel == "gsx" else None, stream, dev,
-                                  dtype, a, c, layers)
+                                  dtype, a, c, layers, wide)
     elif kernel == "gsx":
         gemm = kl.gemm_fp8 if dtype == "fp8" else kl.gemm
         if dtype == "mxfp4":  # quantise the random bf16 operands once; the loop runs on the result
@@ -1358,7 +1399,8 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
 
 
 class _Parser(argparse.ArgumentParser):
-    """``--batch`` has a range per workload: 1..16 rows (gemm ignores it, decode uses it), 1..256 sequences for attn
+    """``--batch`` has a range per workload: 1..16 rows (gemm ignores it, decode uses it), 1..128 rows for decode-wide,
+    1..256 sequences for attn
     and prefill, also where only an ``attn-*`` scenario of the isolation harness (its ``--scenarios``) runs an
     attention pod.  The sizes ``--workload prefill`` cannot run are refused here too, before anything loads torch."""
 
@@ -1366,7 +1408,7 @@ class _Parser(argparse.ArgumentParser):
         ns = super().parse_args(args, namespace)
         scenarios = getattr(ns, "scenarios", "").split(",")
         wide = ns.workload in ("attn", "prefill", "prefill-moe") or any(sc.startswith("attn-") for sc in scenarios)
-        top = 256 if wide else 16
+        top = 256 if wide else 128 if ns.workload == "decode-wide" else 16
         if not 1 <= ns.batch <= top:
             self.error(f"argument --batch: {ns.batch} is not in 1..{top} (--workload {ns.workload})")
         if ns.workload == "generate" and (why := generate_refusal(ns.batch, ns.vocab)):
@@ -1435,9 +1477,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "quantised from bf16 by the library; --kernel gsx only); the output stays bf16")
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--workload", default="gemm",
-                    choices=["gemm", "decode", "attn", "server", "layer", "prefill", "prefill-moe", "generate"],
+                    choices=["gemm", "decode", "decode-wide", "attn", "server", "layer", "prefill", "prefill-moe",
+                             "generate"],
                     help="gemm: one large square GEMM per step (compute-bound); decode: --batch activation rows "
                          "against a ring of --size x --size weight matrices, one launch each (HBM-bandwidth-bound); "
+                         "decode-wide: the same with up to 128 rows, on the skinny GEMM (bf16 and fp8); "
                          "attn: one decode step of attention per layer over a ring of paged KV caches; server: a "
                          "whole decode layer per ring layer (QKV projection, RoPE and KV append, attention, output "
                          "projection) over caches that grow; layer: a whole decoder layer per ring layer (the server "
@@ -1448,7 +1492,8 @@ def build_parser() -> argparse.ArgumentParser:
                          "the last step's tokens, the layers, a final RMSNorm, the LM head (--vocab columns) and the "
                          "sampler, token to token through device memory")
     ap.add_argument("--batch", type=int, default=8, metavar="N",
-                    help="--workload decode, server, layer and generate: the activation rows (M), 1..16; --workload attn and "
+                    help="--workload decode, server, layer and generate: the activation rows (M), 1..16; --workload "
+                         "decode-wide: the rows, 1..128; --workload attn and "
                          "prefill: the sequences, 1..256")
     add_attn_arguments(ap)
     ap.add_argument("--weights-gib", type=float, default=None,

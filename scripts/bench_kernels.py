@@ -334,7 +334,116 @@ def gemm_decode(shapes=DECODE_SHAPES, ms=(1, 4, 16), kinds=("bf16", "fp8", "mxfp
     return out
 
 
-ATTN_SHAPES = [(1, 32768), (8, 8192), (64, 2048), (256, 1024)]  # (sequences, tokens each)
+SKINNY_SHAPES = [(8192, 8192), (8192, 28672), (1024, 8192)]  # decode_pick()'s table, and a narrow N for the split of K
+
+
+def gemm_skinny(shapes=SKINNY_SHAPES, ms=(17, 32, 64, 128), kinds=("bf16", "fp8"), ring_bytes=(2 << 30) + 1, reps=3,
+                rounds=3):
+    """The skinny GEMM by the protocol of :func:`gemm_decode` (a ring of weight matrices of more than 2 GiB, ``reps``
+    passes between two events, median TB/s of weight bytes of ``rounds`` repeats and the spread): every configuration
+    with the dispatched splits, the dispatched configuration with other splits (``gsx_s<splits>``), the dispatching
+    entry point (``gsx``), and the yardsticks: ``decode_slices``, ``ceil(M / 16)`` calls of the decode GEMM on 16-row
+    slices of the same operands (how these shapes run without this kernel: the bar); ``decode_m16``, one decode GEMM of
+    16 rows; ``gemm128``, the large GEMM's "128x128/4w" on A padded to 128 rows; and torch."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    one = torch.ones((), device="cuda", dtype=torch.float32)
+    big = {"bf16": ({name: i for i, name in hip.gemm_cfgs().items()}["128x128/4w"], hip.gemm_bf16_nt_cfg),
+           "fp8": ({name: i for i, name in hip.gemm_fp8_cfgs().items()}["128x128/4w"], hip.gemm_fp8_nt_cfg)}
+    for kind in kinds:
+        wdt, unit = (torch.bfloat16, 2) if kind == "bf16" else (torch.float8_e4m3fn, 1)
+        for n, k in shapes:
+            per = n * k * unit
+            layers = max(2, -(-ring_bytes // per))
+            w = torch.empty(layers, n, k, device="cuda", dtype=wdt)
+            for i in range(layers):
+                w[i].copy_(torch.randn(n, k, device="cuda", dtype=torch.bfloat16).to(wdt))
+            part = torch.empty(16 * 128 * n * 4, device="cuda", dtype=torch.uint8)
+            for m in ms:
+                a = torch.zeros(128, k, device="cuda", dtype=torch.bfloat16)  # rows m .. 127: the padding of gemm128
+                a[:m] = torch.randn(m, k, device="cuda", dtype=torch.bfloat16)
+                a = a.to(wdt)
+                c = torch.empty(128, n, device="cuda", dtype=torch.bfloat16)
+                torch.cuda.synchronize()
+                row_a, row_c = k * unit, n * 2
+
+                def skinny(cfg, splits):
+                    for i in range(layers):
+                        args = (s, kind, a.data_ptr(), w.data_ptr() + i * per, c.data_ptr(), m, n, k)
+                        ws = {"workspace": part.data_ptr(), "workspace_bytes": part.numel()}
+                        if cfg is None:
+                            hip.skinny_gemm_nt(*args, **ws)
+                        else:
+                            hip.skinny_gemm_nt_cfg(*args, cfg, splits, **ws)
+
+                def decode(rows):
+                    for i in range(layers):
+                        for r0 in range(0, rows, 16):
+                            hip.decode_gemm_nt(s, kind, a.data_ptr() + r0 * row_a, w.data_ptr() + i * per,
+                                               c.data_ptr() + r0 * row_c, min(16, rows - r0), n, k)
+
+                def gemm128():
+                    for i in range(layers):
+                        big[kind][1](s, a.data_ptr(), w.data_ptr() + i * per, c.data_ptr(), 128, n, k, big[kind][0])
+
+                def torch_pass():
+                    for i in range(layers):
+                        if kind == "fp8":
+                            torch._scaled_mm(a[:m], w[i].t(), scale_a=one, scale_b=one, out_dtype=torch.bfloat16,
+                                             out=c[:m])
+                        else:
+                            torch.matmul(a[:m], w[i].t(), out=c[:m])
+
+                cfg0, splits0 = hip.skinny_gemm_pick(kind, m, n, k)
+                variants = {f"cfg{cfg}_{name}": (lambda cfg=cfg: skinny(cfg, splits0))
+                            for cfg, (name, bn, _, _) in hip.skinny_gemm_cfgs().items() if n % bn == 0}
+                variants.update({f"gsx_s{sp}": (lambda sp=sp: skinny(cfg0, sp)) for sp in (1, 2, 4, 8) if sp != splits0})
+                variants.update({"gsx": lambda: skinny(None, 0), "decode_slices": lambda: decode(m),
+                                 "decode_m16": lambda: decode(16), "gemm128": gemm128})
+                row = {"kind": kind, "m": m, "n": n, "k": k, "layers": layers, "ring_bytes": layers * per,
+                       "picked": hip.skinny_gemm_cfgs()[cfg0][0], "picked_splits": splits0}
+                try:
+                    with torch.cuda.stream(ts):
+                        torch_pass()
+                    ts.synchronize()
+                    variants["torch"] = torch_pass
+                except RuntimeError as e:  # torch refuses the shape: said, not hidden
+                    row["torch_refused"] = str(e).splitlines()[0][:200]
+
+                def timed(fn):
+                    torch.cuda.synchronize()
+                    with torch.cuda.stream(ts):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(ts)
+                        for _ in range(reps):
+                            fn()
+                        e1.record(ts)
+                    e1.synchronize()
+                    return reps * layers * per / (e0.elapsed_time(e1) * 1e-3) / 1e12
+
+                runs = {name: [] for name in variants}
+                for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                    for name, fn in variants.items():
+                        t = timed(fn)
+                        if r:
+                            runs[name].append(t)
+                for name, v in runs.items():
+                    med = statistics.median(v)
+                    row[f"{name}_TBps"] = round(med, 3)
+                    row[f"{name}_spread"] = round((max(v) - min(v)) / med, 3)
+                # the bar: faster than the slices by more than the larger of the two spreads
+                margin = max(row["gsx_spread"], row["decode_slices_spread"])
+                row["beats_decode_slices"] = row["gsx_TBps"] > row["decode_slices_TBps"] * (1 + margin)
+                out.append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                del a, c
+            del w, part
+    s.destroy()
+    return out
+
+
+ATTN_SHAPES =[(1, 32768), (8, 8192), (64, 2048), (256, 1024)]  # (sequences, tokens each)
 ATTN_HEADS = [(64, 8), (32, 32)]  # (query heads, KV heads): groups of 8, and plain multi-head attention
 ATTN_SPLITS = (1, 2, 4, 8, 16, 32, 64)
 
@@ -1185,7 +1294,8 @@ if __name__ == "__main__":
     sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (2048, 8192, 4096), (16384, 16384, 8192)]
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
-                "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "attn_decode": attn_decode,
+                "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "gemm_skinny": gemm_skinny,
+                "attn_decode": attn_decode,
                 "kv_append": kv_append, "norm_act": norm_act, "attn_prefill": attn_prefill, "sample": sample,
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
