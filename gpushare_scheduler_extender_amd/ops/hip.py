@@ -120,6 +120,7 @@ def lib():
         # stream, kind, Q, K_cache, V_cache, block_table, seq_lens, O; B, T, Hq, Hkv, D, page, num_pages, table_stride,
         # max_seq_len; scale, k_scale, v_scale
         _prefill_sig = [vp, i32] + [vp] * 6 + [i32] * 9 + [ctypes.c_float] * 3
+        _attn_multi_sig = [*_prefill_sig, vp, u64]  # and workspace, workspace_bytes
         # stream, out_kind, X, x_stride, R_in, R_out, r_stride, W, Y, y_stride, scale_out; M, H; eps
         _norm_sig = [vp, i32, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, i32, i32,
                      ctypes.c_float]
@@ -206,6 +207,12 @@ def lib():
             "gsx_prefill_attn_cfg_name": ([i32], ctypes.c_char_p),
             "gsx_prefill_attn_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
             "gsx_event_time_prefill_attn": ([*_prefill_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_decode_attn_multi": (_attn_multi_sig, i32),
+            "gsx_decode_attn_multi_launch_cfg": ([*_attn_multi_sig, i32, i32], i32),
+            "gsx_decode_attn_multi_workspace_bytes": ([i32] * 6 + [ctypes.POINTER(u64)], i32),
+            "gsx_decode_attn_multi_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_decode_attn_multi_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 2, i32),
+            "gsx_event_time_decode_attn_multi": ([*_attn_multi_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_add_rmsnorm": (_norm_sig, i32),
             "gsx_event_time_add_rmsnorm": ([*_norm_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_silu_mul": (_silu_sig, i32),
@@ -904,6 +911,79 @@ def time_prefill_attn(stream: Stream, kind: str, q: int, k_cache: int, v_cache: 
                                                          b, t, hq, hkv, d, page, num_pages, table_stride, max_seq_len,
                                                          scale, k_scale, v_scale), iters, ctypes.byref(ms)),
         "time_prefill_attn")
+    return ms.value
+
+
+def _attn_multi_args(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int, seq_lens: int,
+                     o: int, b: int, t: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int,
+                     max_seq_len: int, scale: float, k_scale: float, v_scale: float, workspace: int,
+                     workspace_bytes: int) -> tuple:
+    return (*_prefill_args(stream, kind, q, k_cache, v_cache, block_table, seq_lens, o, b, t, hq, hkv, d, page,
+                           num_pages, table_stride, max_seq_len, scale, k_scale, v_scale),
+            ctypes.c_void_p(workspace), workspace_bytes)
+
+
+def decode_attn_multi(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int, seq_lens: int,
+                      o: int, b: int, t: int, hq: int, hkv: int, d: int, page: int, num_pages: int, table_stride: int,
+                      max_seq_len: int, scale: float, k_scale: float = 1.0, v_scale: float = 1.0, workspace: int = 0,
+                      workspace_bytes: int = 0):
+    """Causal grouped-query attention of ``t`` new tokens per sequence (1..16, ``hq // hkv * t <= 64``) over the paged
+    KV cache, on the decode attention's bandwidth-bound path: the arguments and the result of :func:`prefill_attn`
+    (``seq_lens[b]`` is the length BEFORE the chunk), plus ``workspace``, device memory of at least
+    :func:`decode_attn_multi_workspace_bytes` bytes for the split-KV partials.  Not synchronised."""
+    _ck(lib().gsx_decode_attn_multi(*_attn_multi_args(stream, kind, q, k_cache, v_cache, block_table, seq_lens, o, b,
+                                                      t, hq, hkv, d, page, num_pages, table_stride, max_seq_len, scale,
+                                                      k_scale, v_scale, workspace, workspace_bytes)),
+        "decode_attn_multi")
+
+
+def decode_attn_multi_workspace_bytes(b: int, t: int, hq: int, d: int, page: int, max_seq_len: int) -> int:
+    """Bytes of workspace :func:`decode_attn_multi` can need for these arguments, whatever ``hkv`` (0: none)."""
+    n = ctypes.c_uint64(0)
+    _ck(lib().gsx_decode_attn_multi_workspace_bytes(b, t, hq, d, page, max_seq_len, ctypes.byref(n)),
+        "decode_attn_multi_workspace_bytes")
+    return n.value
+
+
+def decode_attn_multi_cfg_name(cfg: int) -> str | None:
+    """The name of multi-token decode attention configuration ``cfg``, or None outside the library's table."""
+    name = lib().gsx_decode_attn_multi_cfg_name(cfg)
+    return None if name is None else name.decode()
+
+
+def decode_attn_multi_cfg_shape(cfg: int) -> tuple[int, int]:
+    """``(waves, inflight)`` of configuration ``cfg`` (native/kernels/attn_decode_multi.hip): waves per workgroup,
+    tiles of 32 tokens a wave keeps in flight.  An unknown config raises HipError."""
+    v = [ctypes.c_int(0) for _ in range(2)]
+    if lib().gsx_decode_attn_multi_cfg_shape(cfg, *map(ctypes.byref, v)) != 0:
+        raise HipError(f"decode attn multi cfg {cfg}: unknown config")
+    return tuple(x.value for x in v)
+
+
+def decode_attn_multi_launch_cfg(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int,
+                                 seq_lens: int, o: int, b: int, t: int, hq: int, hkv: int, d: int, page: int,
+                                 num_pages: int, table_stride: int, max_seq_len: int, scale: float, cfg: int,
+                                 splits: int, k_scale: float = 1.0, v_scale: float = 1.0, workspace: int = 0,
+                                 workspace_bytes: int = 0):
+    """Launch one configuration of the multi-token decode attention with ``splits`` (1..64) splits of every sequence;
+    the workspace needs ``b * t * hq * splits * 520`` bytes when ``splits > 1``.  An unknown config raises HipError."""
+    _ck(lib().gsx_decode_attn_multi_launch_cfg(*_attn_multi_args(stream, kind, q, k_cache, v_cache, block_table,
+                                                                 seq_lens, o, b, t, hq, hkv, d, page, num_pages,
+                                                                 table_stride, max_seq_len, scale, k_scale, v_scale,
+                                                                 workspace, workspace_bytes), cfg, splits),
+        f"decode attn multi cfg {cfg} splits {splits}")
+
+
+def time_decode_attn_multi(stream: Stream, kind: str, q: int, k_cache: int, v_cache: int, block_table: int,
+                           seq_lens: int, o: int, b: int, t: int, hq: int, hkv: int, d: int, page: int, num_pages: int,
+                           table_stride: int, max_seq_len: int, scale: float, iters: int, k_scale: float = 1.0,
+                           v_scale: float = 1.0, workspace: int = 0, workspace_bytes: int = 0) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_decode_attn_multi(*_attn_multi_args(stream, kind, q, k_cache, v_cache, block_table,
+                                                                 seq_lens, o, b, t, hq, hkv, d, page, num_pages,
+                                                                 table_stride, max_seq_len, scale, k_scale, v_scale,
+                                                                 workspace, workspace_bytes), iters, ctypes.byref(ms)),
+        "time_decode_attn_multi")
     return ms.value
 
 

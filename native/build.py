@@ -14,8 +14,8 @@ Targets (outputs land in ``gpushare_scheduler_extender_amd/_native/``):
                 HBM touch/verify, HBM memory test, compute (MFMA / VALU / LDS) test, bf16, fp8 and MXFP4 MFMA GEMM
                 workload with the MXFP4 quantiser, the decode GEMM (M <= 16) on the same operands, the skinny GEMM
                 (M <= 128, bf16 and fp8, with a split of K; gemm_skinny.hip), decode attention over a
-                paged KV cache (attn_decode.hip), RoPE + KV-cache append (kv_append.hip), fused residual add + RMSNorm
-                and SwiGLU (norm_act.hip), causal prefill attention over the same cache (attn_prefill.hip), the token
+                paged KV cache (attn_decode.hip) and its multi-token form (attn_decode_multi.hip), RoPE + KV-cache
+                append (kv_append.hip), fused residual add + RMSNorm and SwiGLU (norm_act.hip), causal prefill attention over the same cache (attn_prefill.hip), the token
                 sampler and the embedding gather (sample.hip), the MoE router and combine (moe.hip; the grouped expert
                 GEMM is a form of the decode kernel in gemm_decode.hip), MoE prefill: the many-token router, the tile
                 plan, the grouped 128x128 GEMM and the combine (moe_prefill.hip), CU-masked streams.
@@ -187,7 +187,7 @@ KERNELS = NATIVE / "kernels"
 # forms are the ones their contracts were written against.  gemm_skinny.hip likewise: its partial sums and its two-step
 # epilogue round one operation at a time.  The older sources keep the flags they were measured with.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-HIP_EXTRA = {"moe_prefill": _NO_PACKED_FP32, "gemm_skinny": _NO_PACKED_FP32}
+HIP_EXTRA = {"moe_prefill": _NO_PACKED_FP32, "gemm_skinny": _NO_PACKED_FP32, "attn_decode_multi": _NO_PACKED_FP32}
 _hip_forced: set[Path] = set()  # what a --force has compiled in this process already
 
 

@@ -35,6 +35,9 @@
 //  * prefill attention   — causal attention of a chunk of new tokens over the same paged
 //                          cache, the compute-bound half of an inference server
 //                          (attn_prefill.hip);
+//  * multi-token decode attention — 2 to 16 new tokens per sequence (speculative verification, multi-token
+//                          prediction, the tail of a chunked prefill) over the same cache on the decode
+//                          attention's bandwidth-bound plan, the cache streamed once (attn_decode_multi.hip);
 //  * add + RMSNorm, SwiGLU — the residual stream, the normalisation and the MLP's activation of
 //                          a decoder layer, to bf16 or to e4m3 with a scale per row
 //                          (norm_act.hip);
@@ -411,6 +414,52 @@ int gsx_event_time_prefill_attn(void* stream, int kind, const void* Q, const voi
                                 const void* block_table, const void* seq_lens, void* O, int B, int T, int Hq, int Hkv,
                                 int D, int page, int num_pages, int table_stride, int max_seq_len, float scale,
                                 float k_scale, float v_scale, int iters, float* ms);
+
+// Multi-token decode attention over the paged KV cache (attn_decode_multi.hip): T new tokens per sequence, 1 <= T <=
+// 16, on the plan of gsx_decode_attn: a workgroup per (sequence, KV head, split), both products transposed on
+// v_mfma_f32_16x16x32_bf16 with the G * T query rows that share a KV head as the columns of ceil(G * T / 16) fragments,
+// every tile of 32 tokens of K and V loaded once for all of them.
+// Semantics: exactly those of gsx_prefill_attn.  Q[B * T][Hq][D] and O[B * T][Hq][D] are bf16, Q the Q_out of
+// gsx_kv_append(T); seq_lens holds the lengths BEFORE the chunk; base = clamp(seq_lens[b], 0, max_seq_len); row n =
+// b * T + t is at pos = base + t, is LIVE when pos < max_seq_len and then attends to tokens 0 .. pos of its sequence; a
+// row that is not live gives a row of zeros.
+// Numerics per row: those of gsx_decode_attn (fp32 logits on the bf16 MFMA, p = exp2(x - m), l the sum of the unrounded
+// p, P rounded to bf16 for the PV product, O = bf16((acc / l) * v_scale) rounded once, e4m3 K and V converted to bf16
+// exactly).  A token a row may not see has its x replaced by -inf by a select; V at or past the sequence's end, min(base
+// + T, max_seq_len), is replaced by zeros; between a row's pos and that end V must be finite, as for gsx_prefill_attn.
+// Partials are merged in a fixed order: a wave's tiles, the waves by index, the splits by index; a partial in which a
+// row saw no token has m = -inf, l = 0 and weight 0 for that row.  The result is deterministic and independent of where
+// workgroups run; it depends on the configuration and on `splits`.
+// Requirements: those of gsx_decode_attn, and 1 <= T <= 16, G * T <= 64, B * T * Hq below 2^31 (the merge's grid), O not
+// overlapping Q.  With splits > 1 the partials go to `workspace`, B * Hq * T * splits * 520 bytes, and a second small
+// launch on the same stream merges them; a workspace too small for `splits` is refused with the bytes needed in the
+// text.  Everything is validated before the first device call; launches on `stream` and returns without synchronising.
+// Safety: the clamps of gsx_decode_attn (a page index by an unsigned min into [0, num_pages), lengths to max_seq_len);
+// offsets into the caches are 64-bit; no content of block_table, seq_lens or the caches makes the kernel read outside
+// the caches or write outside O and the workspace.
+// gsx_decode_attn_multi picks the configuration and `splits` from B * Hkv, T and max_seq_len alone (am_pick() in
+// attn_decode_multi.hip); gsx_decode_attn_multi_workspace_bytes returns what it can need with any legal Hkv.
+int gsx_decode_attn_multi(void* stream, int kind, const void* Q, const void* K_cache, const void* V_cache,
+                          const void* block_table, const void* seq_lens, void* O, int B, int T, int Hq, int Hkv, int D,
+                          int page, int num_pages, int table_stride, int max_seq_len, float scale, float k_scale,
+                          float v_scale, void* workspace, uint64_t workspace_bytes);
+int gsx_decode_attn_multi_workspace_bytes(int B, int T, int Hq, int D, int page, int max_seq_len, uint64_t* bytes);
+// The configurations, one table for both cache types and every fragment count: 0 "4w-f1", 1 "4w-f2": waves per
+// workgroup - tiles of 32 tokens a wave keeps in flight.  _cfg_name returns NULL and _cfg_shape nonzero outside the
+// table.  _launch_cfg takes 1 <= splits <= 64 and otherwise what gsx_decode_attn_multi takes.
+const char* gsx_decode_attn_multi_cfg_name(int cfg);
+int gsx_decode_attn_multi_cfg_shape(int cfg, int* waves, int* inflight);
+int gsx_decode_attn_multi_launch_cfg(void* stream, int kind, const void* Q, const void* K_cache, const void* V_cache,
+                                     const void* block_table, const void* seq_lens, void* O, int B, int T, int Hq,
+                                     int Hkv, int D, int page, int num_pages, int table_stride, int max_seq_len,
+                                     float scale, float k_scale, float v_scale, void* workspace,
+                                     uint64_t workspace_bytes, int cfg, int splits);
+// elapsed milliseconds of `iters` back-to-back gsx_decode_attn_multi on `stream`, by hip events (for benches)
+int gsx_event_time_decode_attn_multi(void* stream, int kind, const void* Q, const void* K_cache, const void* V_cache,
+                                     const void* block_table, const void* seq_lens, void* O, int B, int T, int Hq,
+                                     int Hkv, int D, int page, int num_pages, int table_stride, int max_seq_len,
+                                     float scale, float k_scale, float v_scale, void* workspace,
+                                     uint64_t workspace_bytes, int iters, float* ms);
 
 // Fused residual add + RMSNorm, and SwiGLU (norm_act.hip): what a decoder layer has between its projections.  Both
 // write bf16, or OCP e4m3 with one fp32 scale per row, which is exactly the A and scale_a that

@@ -33,7 +33,9 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   of per-layer caches (``--kv-gib``; 4 GiB or a quarter of the share, never fewer than two layers) and runs one
   attention per layer and step, so a step streams more than the Infinity Cache.  It reports ``tbps`` (KV bytes read
   per second) and ``tokens_per_s``.  The library's decode attention, or (``--kernel torch``, bf16 only)
-  ``scaled_dot_product_attention(enable_gqa=True)`` on a contiguous copy of the same data;
+  ``scaled_dot_product_attention(enable_gqa=True)`` on a contiguous copy of the same data.  ``--new-tokens T`` (2..16,
+  the library only) makes the last T tokens of every sequence new ones and runs ``gsx_decode_attn_multi`` over them:
+  the cache is read once for all T, ``tokens_per_s`` counts B * T and ``new_tokens`` is reported;
 * ``--workload server`` is a whole decode layer per ring layer and step, on the library's kernels only: the fused QKV
   projection of ``--batch`` rows (1..16; hidden = ``--heads`` x 128, bf16 weights) through the decode GEMM, RoPE and
   the append of the new token's K and V to the layer's paged cache (``gsx_kv_append``; ``--kv-dtype`` selects the
@@ -284,6 +286,11 @@ class Kernels:
             L.gsx_kv_append.argtypes = ([vp, i32, vp, ctypes.c_int64] + [vp] * 8 + [i32] * 10
                                         + [ctypes.c_float] * 2)
             L.gsx_kv_append.restype = i32
+        if hasattr(L, "gsx_decode_attn_multi"):  # likewise: an image built before the multi-token attention
+            L.gsx_decode_attn_multi.argtypes = ([vp, i32] + [vp] * 6 + [i32] * 9 + [ctypes.c_float] * 3
+                                                + [vp, ctypes.c_uint64])
+            L.gsx_decode_attn_multi_workspace_bytes.argtypes = [i32] * 6 + [ctypes.POINTER(ctypes.c_uint64)]
+            L.gsx_decode_attn_multi.restype = L.gsx_decode_attn_multi_workspace_bytes.restype = i32
         if hasattr(L, "gsx_prefill_attn"):  # likewise: an image built before the prefill attention
             L.gsx_prefill_attn.argtypes = [vp, i32] + [vp] * 6 + [i32] * 9 + [ctypes.c_float] * 3
             L.gsx_prefill_attn.restype = i32
@@ -403,6 +410,24 @@ class Kernels:
                                                                       (q, kc, vc, table, lens, o)),
                                         b, hq, hkv, ATTN_D, page, num_pages, table_stride, max_seq_len, scale, 1.0, 1.0,
                                         ctypes.c_void_p(ws), ws_bytes), "decode_attn")
+
+    def attn_multi_workspace_bytes(self, b: int, t: int, hq: int, page: int, max_seq_len: int) -> int:
+        if not hasattr(self.L, "gsx_decode_attn_multi"):
+            raise RuntimeError(f"{self.path} has no gsx_decode_attn_multi: rebuild it")
+        n = ctypes.c_uint64(0)
+        self._ck(self.L.gsx_decode_attn_multi_workspace_bytes(b, t, hq, ATTN_D, page, max_seq_len, ctypes.byref(n)),
+                 "decode_attn_multi_workspace_bytes")
+        return n.value
+
+    def decode_attn_multi(self, s, kv_dtype: str, q: int, kc: int, vc: int, table: int, lens: int, o: int, b: int,
+                          t: int, hq: int, hkv: int, page: int, num_pages: int, table_stride: int, max_seq_len: int,
+                          scale: float, ws: int, ws_bytes: int):
+        """Causal attention of ``t`` (1..16) new tokens per sequence over the paged cache on the decode attention's
+        path (unit cache scales); ``lens`` are the lengths before the new tokens."""
+        self._ck(self.L.gsx_decode_attn_multi(s, ATTN_KV_KINDS[kv_dtype], *(ctypes.c_void_p(x) for x in
+                                                                            (q, kc, vc, table, lens, o)),
+                                              b, t, hq, hkv, ATTN_D, page, num_pages, table_stride, max_seq_len, scale,
+                                              1.0, 1.0, ctypes.c_void_p(ws), ws_bytes), "decode_attn_multi")
 
     def kv_append(self, s, kv_dtype: str, qkv: int, qkv_stride: int, q_out: int, kc: int, vc: int, table: int,
                   lens: int, lens_out: int, cos: int, sin: int, rope_len: int, b: int, t: int, hq: int, hkv: int,
@@ -663,14 +688,34 @@ def decode_steps(torch, kl, gs, stream, dev, dtype: str, a, c, layers: int, wide
     return step, sync
 
 
+def new_tokens_refusal(workload: str, kernel: str, new_tokens: int, context: int, heads: int,
+                       kv_heads: int) -> str | None:
+    """Why ``--new-tokens`` cannot run, or None: known before anything touches the device.  The limits are the
+    library's (``gsx_decode_attn_multi``), in its wording."""
+    if new_tokens == 1:
+        return None
+    if workload != "attn":
+        return f"--new-tokens {new_tokens}: --workload attn only"
+    if not 1 <= new_tokens <= 16:
+        return f"--new-tokens {new_tokens}: need 1 <= T <= 16"
+    if kv_heads >= 1 and heads % kv_heads == 0 and heads // kv_heads * new_tokens > 64:
+        return f"--new-tokens {new_tokens}: need (Hq / Hkv) * T <= 64"
+    if kernel == "torch":
+        return f"--new-tokens {new_tokens}: the library's kernel only (--kernel gsx)"
+    if new_tokens > context:
+        return f"--new-tokens {new_tokens}: at most --context"
+    return None
+
+
 def attn_steps(torch, kl, gs, stream, dev, kv_dtype: str, batch: int, context: int, heads: int, kv_heads: int,
-               page: int, layers: int):
+               page: int, layers: int, new_tokens: int = 1):
     """``(step, sync)`` of the attention workload: a ring of ``layers`` paged KV caches (random normal), one block
     table (a random permutation of a layer's pages: every layer has the same map and its own memory), and a step that
     runs one attention per layer.  ``kl`` and ``gs`` are the library and its stream, or None for torch's SDPA on a
-    contiguous bf16 copy (on ``stream`` if there is one)."""
+    contiguous bf16 copy (on ``stream`` if there is one).  With ``new_tokens`` > 1 (the library only) the last
+    ``new_tokens`` slots of every sequence belong to the new tokens and a layer is one ``gsx_decode_attn_multi``."""
     per_seq, pages = kv_pages(batch, context, page)
-    q = torch.randn(batch, heads, ATTN_D, device=dev, dtype=torch.bfloat16)
+    q = torch.randn(batch * new_tokens, heads, ATTN_D, device=dev, dtype=torch.bfloat16)
     o = torch.empty_like(q)
     scale = 1.0 / math.sqrt(ATTN_D)
     if kl is None:
@@ -701,14 +746,23 @@ def attn_steps(torch, kl, gs, stream, dev, kv_dtype: str, batch: int, context: i
         for c in (kc, vc):
             c[i].copy_(torch.randn(pages, kv_heads, page, ATTN_D, device=dev, dtype=torch.bfloat16).to(kdt))
     table = torch.randperm(pages, device=dev).to(torch.int32).view(batch, per_seq).contiguous()
-    lens = torch.full((batch,), context, device=dev, dtype=torch.int32)
-    ws_bytes = kl.attn_workspace_bytes(batch, heads, page, context)
+    multi = new_tokens > 1
+    # the lengths a launch takes: all of the context for one new token, what precedes the new tokens for several
+    lens = torch.full((batch,), context - new_tokens if multi else context, device=dev, dtype=torch.int32)
+    ws_bytes = (kl.attn_multi_workspace_bytes(batch, new_tokens, heads, page, context) if multi
+                else kl.attn_workspace_bytes(batch, heads, page, context))
     ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
     layer_bytes = kc[0].numel() * kc.element_size()
     torch.cuda.synchronize()
 
     def step():
         for i in range(layers):
+            if multi:
+                kl.decode_attn_multi(gs, kv_dtype, q.data_ptr(), kc.data_ptr() + i * layer_bytes,
+                                     vc.data_ptr() + i * layer_bytes, table.data_ptr(), lens.data_ptr(), o.data_ptr(),
+                                     batch, new_tokens, heads, kv_heads, page, pages, per_seq, context, scale,
+                                     ws.data_ptr(), ws_bytes)
+                continue
             kl.decode_attn(gs, kv_dtype, q.data_ptr(), kc.data_ptr() + i * layer_bytes,
                            vc.data_ptr() + i * layer_bytes, table.data_ptr(), lens.data_ptr(), o.data_ptr(), batch,
                            heads, kv_heads, page, pages, per_seq, context, scale, ws.data_ptr(), ws_bytes)
@@ -1124,7 +1178,7 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         weights_gib: float | None = None, context: int = 8192, heads: int = 64, kv_heads: int = 8,
         kv_dtype: str = "bf16", kv_gib: float | None = None, page: int = 16, ffn: int | None = None,
         chunk: int = 2048, vocab: int = 128256, temperature: float = 0.8, top_k: int = 50, top_p: float = 0.95,
-        seed: int = 0, experts: int = 0, experts_active: int = MOE_MAX_ACTIVE) -> dict:
+        seed: int = 0, experts: int = 0, experts_active: int = MOE_MAX_ACTIVE, new_tokens: int = 1) -> dict:
     if why := moe_refusal(workload, experts, experts_active):
         raise SystemExit(why)
     if workload in ("prefill", "prefill-moe") and (why := prefill_refusal(batch, chunk, context)):
@@ -1138,6 +1192,8 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         kernel = "gsx" if lib_path is not None else "torch"
         if lib_path is None and not quiet:
             print("[workload] libgsx_kernels.so not found: torch.matmul (hipBLASLt) instead", flush=True)
+    if why := new_tokens_refusal(workload, kernel, new_tokens, context, heads, kv_heads):
+        raise SystemExit(why)
     kl = None
     if kernel == "gsx" or os.environ.get("GSX_CU_MASK"):
         if lib_path is None:
@@ -1267,9 +1323,10 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         layer_bytes = kv_layer_bytes(kv_dtype, batch, context, kv_heads)
         layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB), layer_bytes)
         step, sync = attn_steps(torch, kl if kernel == "gsx" else None, gs if kernel == "gsx" else None, stream, dev,
-                                kv_dtype, batch, context, heads, kv_heads, page, layers)
-        # QK^T and PV: 2 * 2 * D flops per (sequence, query head, token)
-        flops_attn = 4.0 * batch * heads * context * ATTN_D * layers
+                                kv_dtype, batch, context, heads, kv_heads, page, layers, new_tokens)
+        # QK^T and PV: 2 * 2 * D flops per (sequence, query head, token); new token t sees new_tokens - 1 - t fewer
+        flops_attn = 4.0 * batch * heads * ATTN_D * layers * (new_tokens * context
+                                                              - new_tokens * (new_tokens - 1) / 2.0)
     elif decode:
         weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
         layers = ring_layers(weights_bytes, matrix_bytes(dtype, n, k))
@@ -1382,7 +1439,9 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         out.update({"workload": workload, "batch": batch, "layers": layers, "context": context, "heads": heads,
                     "kv_heads": kv_heads, "kv_dtype": kv_dtype, "page": page,
                     "tbps": done * layers * kv_layer_bytes(kv_dtype, batch, context, kv_heads) / el / 1e12,
-                    "tokens_per_s": done * batch / el})
+                    "tokens_per_s": done * batch * new_tokens / el})
+        if new_tokens > 1:
+            out["new_tokens"] = new_tokens
     if probe_limit and allocated:
         # the share is a ceiling: one more share-sized tensor must be refused by the caching allocator
         try:
@@ -1496,6 +1555,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "decode-wide: the rows, 1..128; --workload attn and "
                          "prefill: the sequences, 1..256")
     add_attn_arguments(ap)
+    ap.add_argument("--new-tokens", type=int, default=1, metavar="T",
+                    help="--workload attn: new tokens per sequence, 1..16 with heads / kv-heads * T <= 64; above 1 the "
+                         "last T tokens of --context are the new ones and a layer is one gsx_decode_attn_multi "
+                         "(--kernel gsx only)")
     ap.add_argument("--weights-gib", type=float, default=None,
                     help="--workload decode, server, layer and prefill: size of the weight ring (default 4, or a quarter of the "
                          "share if that is smaller; never fewer than two matrices or layers)")
@@ -1517,7 +1580,8 @@ def main(argv=None) -> int:
               quiet=a.json, probe_limit=a.probe_limit, dtype=a.dtype, workload=a.workload, batch=a.batch,
               weights_gib=a.weights_gib, context=a.context, heads=a.heads, kv_heads=a.kv_heads, kv_dtype=a.kv_dtype,
               kv_gib=a.kv_gib, page=a.page, ffn=a.ffn, chunk=a.chunk, vocab=a.vocab, temperature=a.temperature,
-              top_k=a.top_k, top_p=a.top_p, seed=a.seed, experts=a.experts, experts_active=a.experts_active)
+              top_k=a.top_k, top_p=a.top_p, seed=a.seed, experts=a.experts, experts_active=a.experts_active,
+              new_tokens=a.new_tokens)
     print(json.dumps(res) if a.json else res, flush=True)
     return 0
 

@@ -570,6 +570,117 @@ def attn_decode(shapes=ATTN_SHAPES, heads=ATTN_HEADS, kinds=("bf16", "fp8"), rin
     return out
 
 
+ATTN_MULTI_ROWS = [(64, 8, 1, 32768, (2, 4, 8)), (64, 8, 8, 8192, (2, 4, 8)), (64, 8, 64, 2048, (2, 4, 8)),
+                   (32, 32, 8, 8192, (2, 4, 8, 16))]  # (query heads, KV heads, sequences, tokens each, new tokens)
+
+
+def attn_multi(rows=ATTN_MULTI_ROWS, kinds=("bf16", "fp8"), ring_bytes=(1 << 30) + 1, reps=3, rounds=3, page=16,
+               splits=ATTN_SPLITS):
+    """The multi-token decode attention under the protocol of :func:`attn_decode` (a ring of per-layer paged KV caches
+    of more than 1 GiB, pages of 16 tokens in random order, the median of ``rounds`` repeats after a warm-up round,
+    everything interleaved in one process): every configuration at every split count that makes 64 to 2048 workgroups
+    of at least a tile per wave, the dispatching entry point ``gsx``, and three yardsticks on the same caches:
+    ``decode_x_T`` (T launches of ``gsx_decode_attn``: how the shape runs today on the bandwidth path), ``prefill``
+    (``gsx_prefill_attn`` at the same T: the only single-launch way today) and ``decode_1`` (one launch of
+    ``gsx_decode_attn``: the floor, the cache streamed once).  Reported are microseconds per layer and the spread
+    (max - min) / median; ``gsx_beats_both`` says whether ``gsx`` is faster than ``decode_x_T`` and ``prefill`` by more
+    than the row's largest spread."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    d = 128
+    cfgs = {}
+    while (name := hip.decode_attn_multi_cfg_name(len(cfgs))) is not None:
+        cfgs[len(cfgs)] = (name, *hip.decode_attn_multi_cfg_shape(len(cfgs)))
+    for kind in kinds:
+        kdt = torch.bfloat16 if kind == "bf16" else torch.float8_e4m3fn
+        for hq, hkv, b, ctx, ts_new in rows:
+            per_seq = -(-ctx // page)
+            pages = b * per_seq
+            per = 2 * pages * hkv * page * d * (2 if kind == "bf16" else 1)
+            layers = max(2, -(-ring_bytes // per))
+            kc = torch.empty(layers, pages, hkv, page, d, device="cuda", dtype=kdt)
+            vc = torch.empty_like(kc)
+            for i in range(layers):
+                for c in (kc, vc):
+                    c[i].copy_(torch.randn(pages, hkv, page, d, device="cuda", dtype=torch.bfloat16).to(kdt))
+            table = torch.randperm(pages, device="cuda").to(torch.int32).view(b, per_seq).contiguous()
+            full = torch.full((b,), ctx, device="cuda", dtype=torch.int32)
+            lb = kc[0].numel() * kc.element_size()
+            scale = d ** -0.5
+            tmax = max(ts_new)
+            q = torch.randn(b * tmax, hq, d, device="cuda", dtype=torch.bfloat16)
+            o = torch.empty_like(q)
+            ws = torch.empty(max(b * tmax * hq * max(splits) * 520,
+                                 hip.decode_attn_workspace_bytes(b, hq, d, page, ctx)), device="cuda", dtype=torch.uint8)
+            for t in ts_new:
+                before = torch.full((b,), ctx - t, device="cuda", dtype=torch.int32)  # the lengths before the chunk
+                torch.cuda.synchronize()
+
+                def layer_args(i, lens, *shape):
+                    return (s, kind, q.data_ptr(), kc.data_ptr() + i * lb, vc.data_ptr() + i * lb, table.data_ptr(),
+                            lens.data_ptr(), o.data_ptr(), b, *shape, hq, hkv, d, page, pages, per_seq, ctx, scale)
+
+                def ours(cfg, sp):
+                    for i in range(layers):
+                        if cfg is None:
+                            hip.decode_attn_multi(*layer_args(i, before, t), 1.0, 1.0, ws.data_ptr(), ws.numel())
+                        else:
+                            hip.decode_attn_multi_launch_cfg(*layer_args(i, before, t), cfg, sp, 1.0, 1.0,
+                                                             ws.data_ptr(), ws.numel())
+
+                def decode(times):
+                    for i in range(layers):
+                        for _ in range(times):
+                            hip.decode_attn(*layer_args(i, full), 1.0, 1.0, ws.data_ptr(), ws.numel())
+
+                def prefill():
+                    for i in range(layers):
+                        hip.prefill_attn(*layer_args(i, before, t))
+
+                tiles = -(-ctx // 32)
+                variants = {f"cfg{cfg}_{name}_s{sp}": (lambda cfg=cfg, sp=sp: ours(cfg, sp))
+                            for cfg, (name, waves, _) in cfgs.items() for sp in splits
+                            if sp * waves <= tiles and 64 <= b * hkv * sp <= 2048}
+                variants.update({"gsx": lambda: ours(None, None), "decode_x_T": lambda: decode(t), "prefill": prefill,
+                                 "decode_1": lambda: decode(1)})
+
+                def timed(fn):
+                    torch.cuda.synchronize()
+                    with torch.cuda.stream(ts):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(ts)
+                        for _ in range(reps):
+                            fn()
+                        e1.record(ts)
+                    e1.synchronize()
+                    return e0.elapsed_time(e1) * 1e3 / (reps * layers)  # microseconds per layer
+
+                runs = {name: [] for name in variants}
+                for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                    for name, fn in variants.items():
+                        us = timed(fn)
+                        if r:
+                            runs[name].append(us)
+                row = {"kind": kind, "b": b, "context": ctx, "heads": hq, "kv_heads": hkv, "new_tokens": t,
+                       "page": page, "layers": layers, "ring_bytes": layers * per}
+                for name, v in runs.items():
+                    med = statistics.median(v)
+                    row[f"{name}_us"] = round(med, 2)
+                    row[f"{name}_spread"] = round((max(v) - min(v)) / med, 3)
+                margin = max(v for k, v in row.items() if k.endswith("_spread"))
+                row["gsx_TBps"] = round(per / (row["gsx_us"] * 1e-6) / 1e12, 3)
+                row["gsx_over_decode_1"] = round(row["gsx_us"] / row["decode_1_us"], 3)
+                row["best"] = min((k for k in runs if k.startswith("cfg")), key=lambda k: row[f"{k}_us"])
+                row["gsx_beats_both"] = row["gsx_us"] * (1 + margin) < min(row["decode_x_T_us"], row["prefill_us"])
+                out.append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+            del kc, vc, table, full, q, o, ws
+            torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 KV_APPEND_SHAPES = [(8, 2048), (64, 512), (1, 16384)]  # (sequences, new tokens each): prefill chunks of 16384 tokens
 KV_APPEND_DECODE = (8, 64, 256)  # sequences of a decode step (T = 1)
 
@@ -1295,7 +1406,7 @@ if __name__ == "__main__":
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
                 "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "gemm_skinny": gemm_skinny,
-                "attn_decode": attn_decode,
+                "attn_decode": attn_decode, "attn_multi": attn_multi,
                 "kv_append": kv_append, "norm_act": norm_act, "attn_prefill": attn_prefill, "sample": sample,
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
