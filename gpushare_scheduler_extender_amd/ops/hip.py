@@ -121,6 +121,9 @@ def lib():
         # max_seq_len; scale, k_scale, v_scale
         _prefill_sig = [vp, i32] + [vp] * 6 + [i32] * 9 + [ctypes.c_float] * 3
         _attn_multi_sig = [*_prefill_sig, vp, u64]  # and workspace, workspace_bytes
+        # stream, kind, Q, KV_cache, block_table, seq_lens, O; B, Hq, page, num_pages, table_stride, max_seq_len; scale,
+        # kv_scale; workspace, workspace_bytes
+        _mla_sig = [vp, i32] + [vp] * 5 + [i32] * 6 + [ctypes.c_float] * 2 + [vp, u64]
         # stream, out_kind, X, x_stride, R_in, R_out, r_stride, W, Y, y_stride, scale_out; M, H; eps
         _norm_sig = [vp, i32, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, i32, i32,
                      ctypes.c_float]
@@ -213,6 +216,12 @@ def lib():
             "gsx_decode_attn_multi_cfg_name": ([i32], ctypes.c_char_p),
             "gsx_decode_attn_multi_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 2, i32),
             "gsx_event_time_decode_attn_multi": ([*_attn_multi_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_mla_decode_attn": (_mla_sig, i32),
+            "gsx_mla_decode_attn_launch_cfg": ([*_mla_sig, i32, i32], i32),
+            "gsx_mla_decode_attn_workspace_bytes": ([i32] * 4 + [ctypes.POINTER(u64)], i32),
+            "gsx_mla_decode_attn_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_mla_decode_attn_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 2, i32),
+            "gsx_event_time_mla_decode_attn": ([*_mla_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_add_rmsnorm": (_norm_sig, i32),
             "gsx_event_time_add_rmsnorm": ([*_norm_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_silu_mul": (_silu_sig, i32),
@@ -984,6 +993,76 @@ def time_decode_attn_multi(stream: Stream, kind: str, q: int, k_cache: int, v_ca
                                                                  table_stride, max_seq_len, scale, k_scale, v_scale,
                                                                  workspace, workspace_bytes), iters, ctypes.byref(ms)),
         "time_decode_attn_multi")
+    return ms.value
+
+
+def _mla_args(stream: Stream, kind: str, q: int, kv_cache: int, block_table: int, seq_lens: int, o: int, b: int,
+              hq: int, page: int, num_pages: int, table_stride: int, max_seq_len: int, scale: float, kv_scale: float,
+              workspace: int, workspace_bytes: int) -> tuple:
+    if kind not in ATTN_KV_KINDS:
+        raise ValueError(f"attention cache kind {kind!r}: one of {', '.join(ATTN_KV_KINDS)}")
+    return (stream.handle, ATTN_KV_KINDS[kind], *(ctypes.c_void_p(x) for x in (q, kv_cache, block_table, seq_lens, o)),
+            b, hq, page, num_pages, table_stride, max_seq_len, scale, kv_scale, ctypes.c_void_p(workspace),
+            workspace_bytes)
+
+
+def mla_decode_attn(stream: Stream, kind: str, q: int, kv_cache: int, block_table: int, seq_lens: int, o: int, b: int,
+                    hq: int, page: int, num_pages: int, table_stride: int, max_seq_len: int, scale: float,
+                    kv_scale: float = 1.0, workspace: int = 0, workspace_bytes: int = 0):
+    """Multi-head latent attention of one new token per sequence over the paged latent cache: ``o[b][hq][512]`` (bf16,
+    in latent space) from ``q[b][hq][576]`` (bf16: the absorbed query, then its 64 rotated RoPE elements) and
+    ``kv_cache[num_pages][page][576]`` of ``kind`` ``"bf16"`` or ``"fp8"`` (OCP e4m3 times ``kv_scale``), one row per
+    token that is K (all 576) and V (the first 512) for all ``hq`` heads (1..128).  ``workspace`` is device memory of
+    at least :func:`mla_decode_attn_workspace_bytes` bytes for the split-KV partials.  All addresses are device
+    addresses.  Not synchronised."""
+    _ck(lib().gsx_mla_decode_attn(*_mla_args(stream, kind, q, kv_cache, block_table, seq_lens, o, b, hq, page,
+                                             num_pages, table_stride, max_seq_len, scale, kv_scale, workspace,
+                                             workspace_bytes)), "mla_decode_attn")
+
+
+def mla_decode_attn_workspace_bytes(b: int, hq: int, page: int, max_seq_len: int) -> int:
+    """Bytes of workspace :func:`mla_decode_attn` needs for these arguments (0: none)."""
+    n = ctypes.c_uint64(0)
+    _ck(lib().gsx_mla_decode_attn_workspace_bytes(b, hq, page, max_seq_len, ctypes.byref(n)),
+        "mla_decode_attn_workspace_bytes")
+    return n.value
+
+
+def mla_decode_attn_cfg_name(cfg: int) -> str | None:
+    """The name of MLA decode attention configuration ``cfg``, or None outside the library's table."""
+    name = lib().gsx_mla_decode_attn_cfg_name(cfg)
+    return None if name is None else name.decode()
+
+
+def mla_decode_attn_cfg_shape(cfg: int) -> tuple[int, int]:
+    """``(waves, inflight)`` of configuration ``cfg`` (native/kernels/attn_mla.hip): waves per workgroup, tiles of 32
+    tokens a workgroup keeps in flight.  An unknown config raises HipError."""
+    v = [ctypes.c_int(0) for _ in range(2)]
+    if lib().gsx_mla_decode_attn_cfg_shape(cfg, *map(ctypes.byref, v)) != 0:
+        raise HipError(f"mla decode attn cfg {cfg}: unknown config")
+    return tuple(x.value for x in v)
+
+
+def mla_decode_attn_launch_cfg(stream: Stream, kind: str, q: int, kv_cache: int, block_table: int, seq_lens: int,
+                               o: int, b: int, hq: int, page: int, num_pages: int, table_stride: int, max_seq_len: int,
+                               scale: float, cfg: int, splits: int, kv_scale: float = 1.0, workspace: int = 0,
+                               workspace_bytes: int = 0):
+    """Launch one configuration of the MLA decode attention with ``splits`` (1..64) splits of every sequence; the
+    workspace needs ``b * hq * splits * 2056`` bytes when ``splits > 1``.  An unknown config raises HipError."""
+    _ck(lib().gsx_mla_decode_attn_launch_cfg(*_mla_args(stream, kind, q, kv_cache, block_table, seq_lens, o, b, hq,
+                                                        page, num_pages, table_stride, max_seq_len, scale, kv_scale,
+                                                        workspace, workspace_bytes), cfg, splits),
+        f"mla decode attn cfg {cfg} splits {splits}")
+
+
+def time_mla_decode_attn(stream: Stream, kind: str, q: int, kv_cache: int, block_table: int, seq_lens: int, o: int,
+                         b: int, hq: int, page: int, num_pages: int, table_stride: int, max_seq_len: int, scale: float,
+                         iters: int, kv_scale: float = 1.0, workspace: int = 0, workspace_bytes: int = 0) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_mla_decode_attn(*_mla_args(stream, kind, q, kv_cache, block_table, seq_lens, o, b, hq,
+                                                        page, num_pages, table_stride, max_seq_len, scale, kv_scale,
+                                                        workspace, workspace_bytes), iters, ctypes.byref(ms)),
+        "time_mla_decode_attn")
     return ms.value
 
 

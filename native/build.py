@@ -14,7 +14,8 @@ Targets (outputs land in ``gpushare_scheduler_extender_amd/_native/``):
                 HBM touch/verify, HBM memory test, compute (MFMA / VALU / LDS) test, bf16, fp8 and MXFP4 MFMA GEMM
                 workload with the MXFP4 quantiser, the decode GEMM (M <= 16) on the same operands, the skinny GEMM
                 (M <= 128, bf16 and fp8, with a split of K; gemm_skinny.hip), decode attention over a
-                paged KV cache (attn_decode.hip) and its multi-token form (attn_decode_multi.hip), RoPE + KV-cache
+                paged KV cache (attn_decode.hip) and its multi-token form (attn_decode_multi.hip), multi-head latent
+                attention decode over a paged latent cache (attn_mla.hip), RoPE + KV-cache
                 append (kv_append.hip), fused residual add + RMSNorm and SwiGLU (norm_act.hip), causal prefill attention over the same cache (attn_prefill.hip), the token
                 sampler and the embedding gather (sample.hip), the MoE router and combine (moe.hip; the grouped expert
                 GEMM is a form of the decode kernel in gemm_decode.hip), MoE prefill: the many-token router, the tile

@@ -38,6 +38,10 @@
 //  * multi-token decode attention — 2 to 16 new tokens per sequence (speculative verification, multi-token
 //                          prediction, the tail of a chunked prefill) over the same cache on the decode
 //                          attention's bandwidth-bound plan, the cache streamed once (attn_decode_multi.hip);
+//  * MLA decode attention — multi-head latent attention (DeepSeek-V2/V3/R1, Kimi K2) over a paged cache of one
+//                          576-element latent row per token that is K and V for all 1..128 heads, bf16 or e4m3:
+//                          the tile staged in LDS once and read as both operands, the output split by d over the
+//                          waves (attn_mla.hip);
 //  * add + RMSNorm, SwiGLU — the residual stream, the normalisation and the MLP's activation of
 //                          a decoder layer, to bf16 or to e4m3 with a scale per row
 //                          (norm_act.hip);
@@ -460,6 +464,59 @@ int gsx_event_time_decode_attn_multi(void* stream, int kind, const void* Q, cons
                                      int Hkv, int D, int page, int num_pages, int table_stride, int max_seq_len,
                                      float scale, float k_scale, float v_scale, void* workspace,
                                      uint64_t workspace_bytes, int iters, float* ms);
+
+// Multi-head latent attention (MLA) decode over a paged latent cache (attn_mla.hip): one new token per sequence, in the
+// absorbed form of DeepSeek-V2/V3/R1 and Kimi K2.  A token is ONE cache row of 576 elements shared by all query heads.
+//   Q[B][Hq][576]                        bf16: elements 0..511 the query absorbed through W_UK (the caller's GEMM),
+//                                        512..575 its rotated RoPE part
+//   KV_cache[num_pages][page][576]       bf16 (GSX_ATTN_KV_BF16) or OCP e4m3 (GSX_ATTN_KV_FP8); a page is a contiguous
+//                                        run of page * 576 elements.  Elements 0..511 of a row are the latent, used as
+//                                        K and as V; 512..575 are the rotated k_pe, used as K only
+//   O[B][Hq][512]                        bf16, the attention output in latent space (W_UV is the caller's GEMM)
+//   block_table[B][table_stride], seq_lens[B]   int32 device memory, as gsx_decode_attn takes them
+//   scale                                the caller's softmax scale; kv_scale the one per-tensor dequantisation factor
+//                                        of an e4m3 cache (K and V are the same bytes), exactly 1.0f for bf16
+// Numerics per (sequence, head), over the tokens t < seq_len, those of gsx_decode_attn:
+//   x = (q . k_t) * (scale * kv_scale * log2 e)   fp32, bf16 products accumulated in fp32 on v_mfma_f32_16x16x32_bf16
+//                                        over all 576 elements, as two halves of k added once; e4m3 is converted to
+//                                        bf16 exactly
+//   p = exp2(x - m), l = sum of the unrounded p, P = bf16(p) feeds the PV product over the first 512 elements,
+//   O = bf16((acc / l) * kv_scale), rounded once.
+// Partials are merged in a fixed order: a workgroup's tiles, then the splits by index (the waves of a workgroup share
+// the tiles and own 128 output elements each, so there is nothing to merge between them); a partial without a token has
+// m = -inf, l = 0 and weight 0; a sequence of length 0 gives a row of zeros.  No atomics: the result is deterministic
+// and independent of where workgroups run; it depends on `splits`.
+// Requirements: a known kind; 1 <= B <= 2^20; 1 <= Hq <= 128, any value; page % 16 == 0 and 16 <= page <= 256;
+// num_pages >= 1; 1 <= max_seq_len <= table_stride * page; every pointer non-NULL; Q, the cache, O and the workspace
+// 16-B aligned, the int32 arrays 4-B aligned; O overlaps none of the other operands; scale and kv_scale finite and > 0.
+// With splits > 1 the fp32 partials go to `workspace`, B * Hq * splits * (512 + 2) * 4 bytes, and a small second launch
+// on the same stream merges them; a workspace too small is refused with the bytes needed in the text.  Everything is
+// validated before the first device call; launches on `stream` and returns without synchronising.
+// Safety, as gsx_decode_attn: lengths are clamped into [0, max_seq_len] and a page index into [0, num_pages) by an
+// unsigned min; offsets into the cache are 64-bit; slots at or past seq_len and table entries past the last used page
+// contribute nothing whatever they hold, NaN and inf included (their x is replaced by -inf by a select, their V by
+// zeros).  No content of block_table, seq_lens or the cache makes the kernel read outside the cache or write outside O
+// and the workspace.
+// gsx_mla_decode_attn picks the configuration and `splits` from B, Hq (two head blocks when Hq > 64) and max_seq_len
+// alone (mla_pick() in attn_mla.hip); gsx_mla_decode_attn_workspace_bytes returns what it then needs.
+int gsx_mla_decode_attn(void* stream, int kind, const void* Q, const void* KV_cache, const void* block_table,
+                        const void* seq_lens, void* O, int B, int Hq, int page, int num_pages, int table_stride,
+                        int max_seq_len, float scale, float kv_scale, void* workspace, uint64_t workspace_bytes);
+int gsx_mla_decode_attn_workspace_bytes(int B, int Hq, int page, int max_seq_len, uint64_t* bytes);
+// The configurations, one table for both cache types and every head count: 0 "4w-f1", 1 "4w-f2": waves per workgroup -
+// tiles of 32 tokens a workgroup keeps in flight.  _cfg_name returns NULL and _cfg_shape nonzero outside the table.
+// _launch_cfg takes 1 <= splits <= 64 and otherwise what gsx_mla_decode_attn takes.
+const char* gsx_mla_decode_attn_cfg_name(int cfg);
+int gsx_mla_decode_attn_cfg_shape(int cfg, int* waves, int* inflight);
+int gsx_mla_decode_attn_launch_cfg(void* stream, int kind, const void* Q, const void* KV_cache, const void* block_table,
+                                   const void* seq_lens, void* O, int B, int Hq, int page, int num_pages,
+                                   int table_stride, int max_seq_len, float scale, float kv_scale, void* workspace,
+                                   uint64_t workspace_bytes, int cfg, int splits);
+// elapsed milliseconds of `iters` back-to-back gsx_mla_decode_attn on `stream`, by hip events (for benches)
+int gsx_event_time_mla_decode_attn(void* stream, int kind, const void* Q, const void* KV_cache, const void* block_table,
+                                   const void* seq_lens, void* O, int B, int Hq, int page, int num_pages,
+                                   int table_stride, int max_seq_len, float scale, float kv_scale, void* workspace,
+                                   uint64_t workspace_bytes, int iters, float* ms);
 
 // Fused residual add + RMSNorm, and SwiGLU (norm_act.hip): what a decoder layer has between its projections.  Both
 // write bf16, or OCP e4m3 with one fp32 scale per row, which is exactly the A and scale_a that

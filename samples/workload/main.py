@@ -35,7 +35,11 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   per second) and ``tokens_per_s``.  The library's decode attention, or (``--kernel torch``, bf16 only)
   ``scaled_dot_product_attention(enable_gqa=True)`` on a contiguous copy of the same data.  ``--new-tokens T`` (2..16,
   the library only) makes the last T tokens of every sequence new ones and runs ``gsx_decode_attn_multi`` over them:
-  the cache is read once for all T, ``tokens_per_s`` counts B * T and ``new_tokens`` is reported;
+  the cache is read once for all T, ``tokens_per_s`` counts B * T and ``new_tokens`` is reported.  ``--mla`` (the
+  library only, one new token, ``--kv-heads`` left alone) is the attention of DeepSeek-V2/V3/R1 and Kimi K2 instead:
+  every layer of the ring is one latent cache of 576-element rows (512 latent + 64 RoPE) that all ``--heads`` query
+  heads (1..128) share as K and V, and a layer is one ``gsx_mla_decode_attn``; ``tbps`` counts rows of 576 elements,
+  ``tflops`` 2 * heads * (576 + 512) per cached token, and ``"mla": true`` is reported;
 * ``--workload server`` is a whole decode layer per ring layer and step, on the library's kernels only: the fused QKV
   projection of ``--batch`` rows (1..16; hidden = ``--heads`` x 128, bf16 weights) through the decode GEMM, RoPE and
   the append of the new token's K and V to the layer's paged cache (``gsx_kv_append``; ``--kv-dtype`` selects the
@@ -129,6 +133,14 @@ ATTN_D = 128
 def kv_layer_bytes(kv_dtype: str, batch: int, context: int, kv_heads: int) -> int:
     """Bytes of K and V one attention launch reads: ``batch`` sequences of ``context`` tokens, D = 128."""
     return 2 * batch * context * kv_heads * ATTN_D * (2 if kv_dtype == "bf16" else 1)
+
+
+MLA_DK, MLA_DV = 576, 512  # a latent cache row (all of it K), and its first elements that are V as well
+
+
+def mla_layer_bytes(kv_dtype: str, batch: int, context: int) -> int:
+    """Bytes of the latent cache one MLA launch reads: ``batch`` sequences of ``context`` rows of 576 elements."""
+    return batch * context * MLA_DK * (2 if kv_dtype == "bf16" else 1)
 
 
 def kv_pages(batch: int, context: int, page: int) -> tuple[int, int]:
@@ -291,6 +303,11 @@ class Kernels:
                                                 + [vp, ctypes.c_uint64])
             L.gsx_decode_attn_multi_workspace_bytes.argtypes = [i32] * 6 + [ctypes.POINTER(ctypes.c_uint64)]
             L.gsx_decode_attn_multi.restype = L.gsx_decode_attn_multi_workspace_bytes.restype = i32
+        if hasattr(L, "gsx_mla_decode_attn"):  # likewise: an image built before the MLA decode attention
+            L.gsx_mla_decode_attn.argtypes = ([vp, i32] + [vp] * 5 + [i32] * 6 + [ctypes.c_float] * 2
+                                              + [vp, ctypes.c_uint64])
+            L.gsx_mla_decode_attn_workspace_bytes.argtypes = [i32] * 4 + [ctypes.POINTER(ctypes.c_uint64)]
+            L.gsx_mla_decode_attn.restype = L.gsx_mla_decode_attn_workspace_bytes.restype = i32
         if hasattr(L, "gsx_prefill_attn"):  # likewise: an image built before the prefill attention
             L.gsx_prefill_attn.argtypes = [vp, i32] + [vp] * 6 + [i32] * 9 + [ctypes.c_float] * 3
             L.gsx_prefill_attn.restype = i32
@@ -428,6 +445,23 @@ class Kernels:
                                                                             (q, kc, vc, table, lens, o)),
                                               b, t, hq, hkv, ATTN_D, page, num_pages, table_stride, max_seq_len, scale,
                                               1.0, 1.0, ctypes.c_void_p(ws), ws_bytes), "decode_attn_multi")
+
+    def mla_workspace_bytes(self, b: int, hq: int, page: int, max_seq_len: int) -> int:
+        if not hasattr(self.L, "gsx_mla_decode_attn"):
+            raise RuntimeError(f"{self.path} has no gsx_mla_decode_attn: rebuild it")
+        n = ctypes.c_uint64(0)
+        self._ck(self.L.gsx_mla_decode_attn_workspace_bytes(b, hq, page, max_seq_len, ctypes.byref(n)),
+                 "mla_decode_attn_workspace_bytes")
+        return n.value
+
+    def mla_decode_attn(self, s, kv_dtype: str, q: int, kv: int, table: int, lens: int, o: int, b: int, hq: int,
+                        page: int, num_pages: int, table_stride: int, max_seq_len: int, scale: float, ws: int,
+                        ws_bytes: int):
+        """One decode step of multi-head latent attention over a paged latent cache (unit cache scale)."""
+        self._ck(self.L.gsx_mla_decode_attn(s, ATTN_KV_KINDS[kv_dtype], *(ctypes.c_void_p(x) for x in
+                                                                          (q, kv, table, lens, o)),
+                                            b, hq, page, num_pages, table_stride, max_seq_len, scale, 1.0,
+                                            ctypes.c_void_p(ws), ws_bytes), "mla_decode_attn")
 
     def kv_append(self, s, kv_dtype: str, qkv: int, qkv_stride: int, q_out: int, kc: int, vc: int, table: int,
                   lens: int, lens_out: int, cos: int, sin: int, rope_len: int, b: int, t: int, hq: int, hkv: int,
@@ -705,6 +739,57 @@ def new_tokens_refusal(workload: str, kernel: str, new_tokens: int, context: int
     if new_tokens > context:
         return f"--new-tokens {new_tokens}: at most --context"
     return None
+
+
+MLA_KV_HEADS_DEFAULT = 8  # --kv-heads as the parser leaves it: the latent cache has no KV heads to choose
+
+
+def mla_refusal(workload: str, kernel: str, new_tokens: int, heads: int, kv_heads: int) -> str | None:
+    """Why ``--mla`` cannot run, or None: known before torch loads.  The limits are the library's
+    (``gsx_mla_decode_attn``)."""
+    if workload != "attn":
+        return "--mla: --workload attn only"
+    if kernel != "gsx":
+        return "--mla: the library's kernel only (--kernel gsx)"
+    if new_tokens != 1:
+        return f"--mla --new-tokens {new_tokens}: one new token per sequence"
+    if kv_heads != MLA_KV_HEADS_DEFAULT:
+        return f"--mla --kv-heads {kv_heads}: the latent cache is one row per token for all heads; leave --kv-heads alone"
+    if not 1 <= heads <= 128:
+        return f"--mla --heads {heads}: need 1 <= Hq <= 128"
+    return None
+
+
+def mla_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, heads: int, page: int, layers: int):
+    """``(step, sync)`` of the MLA attention workload: the ring and the block table of :func:`attn_steps`, every layer
+    one latent cache ``[pages][page][576]`` filled with random normal rows, and a step that runs one
+    ``gsx_mla_decode_attn`` per layer (scale 192^-0.5, DeepSeek's 128 + 64 query-key width)."""
+    per_seq, pages = kv_pages(batch, context, page)
+    q = torch.randn(batch, heads, MLA_DK, device=dev, dtype=torch.bfloat16)
+    o = torch.empty(batch, heads, MLA_DV, device=dev, dtype=torch.bfloat16)
+    kdt = torch.bfloat16 if kv_dtype == "bf16" else torch.float8_e4m3fn
+    kv = torch.empty(layers, pages, page, MLA_DK, device=dev, dtype=kdt)
+    for i in range(layers):  # one layer at a time: nothing larger is ever held in bf16
+        kv[i].copy_(torch.randn(pages, page, MLA_DK, device=dev, dtype=torch.bfloat16).to(kdt))
+    table = torch.randperm(pages, device=dev).to(torch.int32).view(batch, per_seq).contiguous()
+    lens = torch.full((batch,), context, device=dev, dtype=torch.int32)
+    ws_bytes = kl.mla_workspace_bytes(batch, heads, page, context)
+    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+    layer_bytes = kv[0].numel() * kv.element_size()
+    scale = 192 ** -0.5
+    torch.cuda.synchronize()
+
+    def step():
+        for i in range(layers):
+            kl.mla_decode_attn(gs, kv_dtype, q.data_ptr(), kv.data_ptr() + i * layer_bytes, table.data_ptr(),
+                               lens.data_ptr(), o.data_ptr(), batch, heads, page, pages, per_seq, context, scale,
+                               ws.data_ptr(), ws_bytes)
+
+    def sync():
+        kl.sync(gs)
+
+    step.keep = (q, o, kv, table, lens, ws)  # the closure holds addresses, not tensors
+    return step, sync
 
 
 def attn_steps(torch, kl, gs, stream, dev, kv_dtype: str, batch: int, context: int, heads: int, kv_heads: int,
@@ -1178,8 +1263,11 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         weights_gib: float | None = None, context: int = 8192, heads: int = 64, kv_heads: int = 8,
         kv_dtype: str = "bf16", kv_gib: float | None = None, page: int = 16, ffn: int | None = None,
         chunk: int = 2048, vocab: int = 128256, temperature: float = 0.8, top_k: int = 50, top_p: float = 0.95,
-        seed: int = 0, experts: int = 0, experts_active: int = MOE_MAX_ACTIVE, new_tokens: int = 1) -> dict:
+        seed: int = 0, experts: int = 0, experts_active: int = MOE_MAX_ACTIVE, new_tokens: int = 1,
+        mla: bool = False) -> dict:
     if why := moe_refusal(workload, experts, experts_active):
+        raise SystemExit(why)
+    if mla and (why := mla_refusal(workload, kernel, new_tokens, heads, kv_heads)):
         raise SystemExit(why)
     if workload in ("prefill", "prefill-moe") and (why := prefill_refusal(batch, chunk, context)):
         raise SystemExit(f"--workload {workload}: {why}")
@@ -1247,7 +1335,9 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
             raise SystemExit(f"--kv-dtype {kv_dtype}: bf16 or fp8")
         if kernel != "gsx" and kv_dtype != "bf16":
             raise SystemExit("--kernel torch --workload attn runs scaled_dot_product_attention on bf16 only")
-        if context < 1 or heads < 1 or kv_heads < 1 or heads % kv_heads or heads // kv_heads > 16:
+        if context < 1:
+            raise SystemExit("--workload attn: --context >= 1")
+        if not mla and (heads < 1 or kv_heads < 1 or heads % kv_heads or heads // kv_heads > 16):
             raise SystemExit("--workload attn: --context >= 1, --heads a multiple of --kv-heads, at most 16 times it")
         if page % 16 or not 16 <= page <= 256:
             raise SystemExit(f"--page {page}: a multiple of 16 in 16..256")
@@ -1319,6 +1409,12 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
                                    + 4.0 * batch * heads * context * ATTN_D)
         if generate:  # the LM head
             flops_attn += 2.0 * batch * vocab * heads * ATTN_D
+    elif mla:
+        layer_bytes = mla_layer_bytes(kv_dtype, batch, context)
+        layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB), layer_bytes)
+        step, sync = mla_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, page, layers)
+        # QK^T over 576 and PV over 512 elements per (sequence, query head, cached token)
+        flops_attn = 2.0 * batch * heads * (MLA_DK + MLA_DV) * context * layers
     elif attn:
         layer_bytes = kv_layer_bytes(kv_dtype, batch, context, kv_heads)
         layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB), layer_bytes)
@@ -1435,6 +1531,11 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
             out.update({"vocab": vocab, "temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed,
                         "bytes_per_step": step_bytes, "tbps": done * step_bytes / el / 1e12,
                         "tokens_in_range": all(0 <= t < vocab for t in last_tokens())})
+    elif mla:
+        out.update({"workload": workload, "mla": True, "batch": batch, "layers": layers, "context": context,
+                    "heads": heads, "kv_dtype": kv_dtype, "page": page,
+                    "tbps": done * layers * mla_layer_bytes(kv_dtype, batch, context) / el / 1e12,
+                    "tokens_per_s": done * batch / el})  # tflops: 2 * heads * (576 + 512) per cached token
     elif attn:
         out.update({"workload": workload, "batch": batch, "layers": layers, "context": context, "heads": heads,
                     "kv_heads": kv_heads, "kv_dtype": kv_dtype, "page": page,
@@ -1559,6 +1660,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="--workload attn: new tokens per sequence, 1..16 with heads / kv-heads * T <= 64; above 1 the "
                          "last T tokens of --context are the new ones and a layer is one gsx_decode_attn_multi "
                          "(--kernel gsx only)")
+    ap.add_argument("--mla", action="store_true",
+                    help="--workload attn: multi-head latent attention (DeepSeek-V2/V3/R1, Kimi K2): every layer is one "
+                         "latent cache of 576-element rows shared by all --heads (1..128) query heads and a layer is "
+                         "one gsx_mla_decode_attn (--kernel gsx only, one new token, --kv-heads left alone)")
     ap.add_argument("--weights-gib", type=float, default=None,
                     help="--workload decode, server, layer and prefill: size of the weight ring (default 4, or a quarter of the "
                          "share if that is smaller; never fewer than two matrices or layers)")
@@ -1581,7 +1686,7 @@ def main(argv=None) -> int:
               weights_gib=a.weights_gib, context=a.context, heads=a.heads, kv_heads=a.kv_heads, kv_dtype=a.kv_dtype,
               kv_gib=a.kv_gib, page=a.page, ffn=a.ffn, chunk=a.chunk, vocab=a.vocab, temperature=a.temperature,
               top_k=a.top_k, top_p=a.top_p, seed=a.seed, experts=a.experts, experts_active=a.experts_active,
-              new_tokens=a.new_tokens)
+              new_tokens=a.new_tokens, mla=a.mla)
     print(json.dumps(res) if a.json else res, flush=True)
     return 0
 

@@ -681,6 +681,115 @@ def attn_multi(rows=ATTN_MULTI_ROWS, kinds=("bf16", "fp8"), ring_bytes=(1 << 30)
     return out
 
 
+def attn_mla(shapes=ATTN_SHAPES[:3], heads=(16, 128), kinds=("bf16", "fp8"), ring_bytes=(1 << 30) + 1, reps=3, rounds=3,
+             page=16, splits=ATTN_SPLITS):
+    """The MLA decode attention under the protocol of :func:`attn_decode`: a ring of per-layer latent caches
+    (``[pages][page][576]``) of more than 1 GiB, pages of 16 tokens handed out through a random permutation, the median
+    of ``rounds`` repeats after a warm-up round, every column interleaved in one process.  Columns: every configuration
+    at every split count that leaves a split 8 tiles and makes 16 to 4096 workgroups, the dispatching entry point
+    ``gsx``, and ``torch``, the yardstick that is not the code under test: torch's own path on the gathered dense
+    latent of the same layers in bf16 (batched matmul over 576, softmax in fp32, batched matmul over 512).  Reported
+    are microseconds per layer with the spread (max - min) / median, ``gsx_TBps`` (rows of 576 elements) and
+    ``gsx_TFLOPs`` (2 * Hq * (576 + 512) per cached token); ``gsx_beats_torch`` says whether ``gsx`` is faster than
+    ``torch`` by more than the row's largest spread."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    dk, dv = 576, 512
+    cfgs = {}
+    while (name := hip.mla_decode_attn_cfg_name(len(cfgs))) is not None:
+        cfgs[len(cfgs)] = (name, *hip.mla_decode_attn_cfg_shape(len(cfgs)))
+    scale = 192 ** -0.5
+    for kind in kinds:
+        kdt = torch.bfloat16 if kind == "bf16" else torch.float8_e4m3fn
+        for b, ctx in shapes:
+            per_seq = -(-ctx // page)
+            pages = b * per_seq
+            per = pages * page * dk * (2 if kind == "bf16" else 1)
+            layers = max(2, -(-ring_bytes // per))
+            kv = torch.empty(layers, pages, page, dk, device="cuda", dtype=kdt)
+            for i in range(layers):
+                kv[i].copy_(torch.randn(pages, page, dk, device="cuda", dtype=torch.bfloat16).to(kdt))
+            table = torch.randperm(pages, device="cuda").to(torch.int32).view(b, per_seq).contiguous()
+            lens = torch.full((b,), ctx, device="cuda", dtype=torch.int32)
+            lb = kv[0].numel() * kv.element_size()
+            # the dense latent of every layer, gathered and in bf16: [layers][B][ctx][576]
+            idx = table.long()
+            raw = kv if kind == "bf16" else kv.view(torch.uint8)  # gathered as bytes: the values are the same
+            dense = torch.stack([raw[i][idx].view(kdt).reshape(b, per_seq * page, dk)[:, :ctx].to(torch.bfloat16)
+                                 for i in range(layers)]).contiguous()
+            for hq in heads:
+                q = torch.randn(b, hq, dk, device="cuda", dtype=torch.bfloat16)
+                o = torch.empty(b, hq, dv, device="cuda", dtype=torch.bfloat16)
+                ws = torch.empty(max(b * hq * max(splits) * 2056, 16), device="cuda", dtype=torch.uint8)
+                torch.cuda.synchronize()
+
+                def ours(cfg, sp):
+                    for i in range(layers):
+                        args = (s, kind, q.data_ptr(), kv.data_ptr() + i * lb, table.data_ptr(), lens.data_ptr(),
+                                o.data_ptr(), b, hq, page, pages, per_seq, ctx, scale)
+                        if cfg is None:
+                            hip.mla_decode_attn(*args, 1.0, ws.data_ptr(), ws.numel())
+                        else:
+                            hip.mla_decode_attn_launch_cfg(*args, cfg, sp, 1.0, ws.data_ptr(), ws.numel())
+
+                def torch_pass():
+                    for i in range(layers):
+                        p = torch.softmax(torch.matmul(q, dense[i].transpose(1, 2)).float() * scale, dim=-1)
+                        o.copy_(torch.matmul(p.to(torch.bfloat16), dense[i][:, :, :dv]))
+
+                tiles, nhb = -(-ctx // 32), 2 if hq > 64 else 1
+                variants = {f"cfg{cfg}_{name}_s{sp}": (lambda cfg=cfg, sp=sp: ours(cfg, sp))
+                            for cfg, (name, _, _) in cfgs.items() for sp in splits
+                            if sp * 8 <= tiles and 16 <= b * nhb * sp <= 4096}
+                variants.update({"gsx": lambda: ours(None, None), "torch": torch_pass})
+
+                def timed(fn):
+                    torch.cuda.synchronize()
+                    with torch.cuda.stream(ts):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(ts)
+                        for _ in range(reps):
+                            fn()
+                        e1.record(ts)
+                    e1.synchronize()
+                    return e0.elapsed_time(e1) * 1e3 / (reps * layers)  # microseconds per layer
+
+                # the two agree (on the ring's last layer) before they are compared for speed
+                ours(None, None)
+                s.sync()
+                got = o.float().clone()
+                with torch.cuda.stream(ts):
+                    torch_pass()
+                torch.cuda.synchronize()
+                row = {"kind": kind, "b": b, "context": ctx, "heads": hq, "page": page, "layers": layers,
+                       "ring_bytes": layers * per, "max_abs_diff_vs_torch": round((got - o.float()).abs().max().item(), 5)}
+                runs = {name: [] for name in variants}
+                for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                    for name, fn in variants.items():
+                        us = timed(fn)
+                        if r:
+                            runs[name].append(us)
+                for name, v in runs.items():
+                    med = statistics.median(v)
+                    row[f"{name}_us"] = round(med, 2)
+                    row[f"{name}_spread"] = round((max(v) - min(v)) / med, 3)
+                margin = max(v for k, v in row.items() if k.endswith("_spread"))
+                row["spread"] = margin
+                row["gsx_TBps"] = round(per / (row["gsx_us"] * 1e-6) / 1e12, 3)
+                row["gsx_TFLOPs"] = round(2.0 * b * ctx * hq * (dk + dv) / (row["gsx_us"] * 1e-6) / 1e12, 1)
+                row["best"] = min((k for k in runs if k.startswith("cfg")), key=lambda k: row[f"{k}_us"])
+                row["gsx_over_best"] = round(row["gsx_us"] / row[row["best"] + "_us"], 3)
+                row["gsx_beats_torch"] = row["gsx_us"] * (1 + margin) < row["torch_us"]
+                out.append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                del q, o, ws
+            del kv, dense, table, lens
+            torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 KV_APPEND_SHAPES = [(8, 2048), (64, 512), (1, 16384)]  # (sequences, new tokens each): prefill chunks of 16384 tokens
 KV_APPEND_DECODE = (8, 64, 256)  # sequences of a decode step (T = 1)
 
@@ -1406,7 +1515,7 @@ if __name__ == "__main__":
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
                 "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "gemm_skinny": gemm_skinny,
-                "attn_decode": attn_decode, "attn_multi": attn_multi,
+                "attn_decode": attn_decode, "attn_multi": attn_multi, "attn_mla": attn_mla,
                 "kv_append": kv_append, "norm_act": norm_act, "attn_prefill": attn_prefill, "sample": sample,
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
