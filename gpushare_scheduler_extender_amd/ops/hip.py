@@ -147,6 +147,8 @@ def lib():
         _pf_gemm_sig = [vp, vp, i32, vp, vp, vp] + [i32] * 5
         # stream, kind, A, B, C; M, N, K; scale_a, scale_b, scale_mode; workspace, workspace_bytes
         _skinny_sig = [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, u64]
+        # stream, A, B, C; M, N, K; scale_a, sa_stride, scale_b
+        _fp8_block_sig = [vp, vp, vp, vp, i32, i32, i32, vp, ctypes.c_int64, vp]
         sig = {
             "gsx_last_error": ([], ctypes.c_char_p),
             "gsx_device_count": ([ctypes.POINTER(i32)], i32),
@@ -177,6 +179,12 @@ def lib():
             "gsx_gemm_fp8_cfg_name": ([i32], ctypes.c_char_p),
             "gsx_event_time_gemm_fp8": ([vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32,
                                          ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_gemm_fp8_block_nt": (_fp8_block_sig, i32),
+            "gsx_gemm_fp8_block_nt_launch_cfg": ([*_fp8_block_sig, i32], i32),
+            "gsx_gemm_fp8_block_cfg_tile": ([i32, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
+            "gsx_gemm_fp8_block_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_event_time_gemm_fp8_block": ([*_fp8_block_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_quant_fp8_block": ([vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, i32, i32], i32),
             "gsx_gemm_mxfp4_nt": ([vp, vp, vp, vp, i32, i32, i32, vp, vp], i32),
             "gsx_gemm_mxfp4_nt_launch_cfg": ([vp, vp, vp, vp, i32, i32, i32, vp, vp, i32], i32),
             "gsx_gemm_mxfp4_cfg_tile": ([i32, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
@@ -589,6 +597,55 @@ def time_gemm_fp8(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int
                                       m, n, k, ctypes.c_void_p(scale_a), ctypes.c_void_p(scale_b), scale_mode, iters,
                                       ctypes.byref(ms)), "time_gemm_fp8")
     return ms.value
+
+
+def _fp8_block_args(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, scale_a: int, sa_stride: int,
+                    scale_b: int) -> tuple:
+    return (stream.handle, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m, n, k,
+            ctypes.c_void_p(scale_a), sa_stride, ctypes.c_void_p(scale_b))
+
+
+def gemm_fp8_block_nt(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, scale_a: int, sa_stride: int,
+                      scale_b: int):
+    """``C`` (bf16) ``= A * B^T`` on block-scaled OCP e4m3 operands: ``scale_a[m][k / 128]`` (fp32, rows
+    ``sa_stride`` elements apart) holds one scale per 1 x 128 group of ``A``, ``scale_b[n / 128][k / 128]`` one per
+    128 x 128 block of ``B``; every K block is scaled before it is added (gsx_kernels.h).  Not synchronised."""
+    _ck(lib().gsx_gemm_fp8_block_nt(*_fp8_block_args(stream, a, b, c, m, n, k, scale_a, sa_stride, scale_b)),
+        "gemm_fp8_block_nt")
+
+
+def gemm_fp8_block_cfgs() -> dict[int, str]:
+    """``{index: name}`` of the block-scaled fp8 configurations, read from the library's table
+    (native/kernels/gemm_fp8_block.hip)."""
+    out: dict[int, str] = {}
+    while (name := lib().gsx_gemm_fp8_block_cfg_name(len(out))) is not None:
+        out[len(out)] = name.decode()
+    return out
+
+
+def gemm_fp8_block_nt_cfg(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, cfg: int, scale_a: int,
+                          sa_stride: int, scale_b: int):
+    """Launch one configuration of the block-scaled fp8 GEMM; an unknown config or a shape it cannot take raises
+    HipError."""
+    _ck(lib().gsx_gemm_fp8_block_nt_launch_cfg(*_fp8_block_args(stream, a, b, c, m, n, k, scale_a, sa_stride, scale_b),
+                                               cfg), f"gemm fp8 block cfg {cfg}")
+
+
+def time_gemm_fp8_block(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, iters: int, scale_a: int,
+                        sa_stride: int, scale_b: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_gemm_fp8_block(*_fp8_block_args(stream, a, b, c, m, n, k, scale_a, sa_stride, scale_b),
+                                            iters, ctypes.byref(ms)), "time_gemm_fp8_block")
+    return ms.value
+
+
+def quant_fp8_block(stream: Stream, x: int, x_stride: int, q: int, q_stride: int, s: int, s_stride: int, rows: int,
+                    k: int):
+    """Quantise bf16 ``x[rows][x_stride]`` (``k`` a multiple of 128) to OCP e4m3 ``q[rows][q_stride]`` with one fp32
+    scale per group of 128 elements in ``s[rows][s_stride]``, by the rule of the ``"fp8"`` activation outputs applied
+    per group: the ``A`` and ``scale_a`` of :func:`gemm_fp8_block_nt`.  Strides are in elements.  Not synchronised."""
+    _ck(lib().gsx_quant_fp8_block(stream.handle, ctypes.c_void_p(x), x_stride, ctypes.c_void_p(q), q_stride,
+                                  ctypes.c_void_p(s), s_stride, rows, k), "quant_fp8_block")
 
 
 def gemm_mxfp4_nt(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, scale_a: int, scale_b: int):

@@ -21,6 +21,9 @@
 //                          (throughput under per-pod CU partitions);
 //  * fp8 MFMA GEMM       — the same workload on OCP e4m3 operands and the K=128
 //                          MFMA, with per-tensor or per-row scales (gemm_fp8.hip);
+//  * block-scaled fp8 GEMM — e4m3 operands with one fp32 scale per 1 x 128 group of A and per
+//                          128 x 128 block of B, every K block scaled before it is added, and
+//                          the activation quantiser for it (gemm_fp8_block.hip);
 //  * MXFP4 MFMA GEMM     — the same workload on e2m1 operands with e8m0 block scales
 //                          on the block-scaled MFMA, and the quantiser that makes
 //                          such operands from bf16 (gemm_mxfp4.hip);
@@ -163,6 +166,46 @@ int gsx_gemm_fp8_nt_launch_cfg(void* stream, const void* A, const void* B, void*
 // elapsed milliseconds of `iters` back-to-back gsx_gemm_fp8_nt on `stream`, by hip events (for benches)
 int gsx_event_time_gemm_fp8(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
                             const float* scale_a, const float* scale_b, int scale_mode, int iters, float* ms);
+
+// Block-scaled fp8 GEMM (gemm_fp8_block.hip): C[M][N] (bf16) = A[M][K] * B[N][K]^T with A and B in OCP e4m3,
+// row-major, and scales that change along K, the format of the DeepSeek-V3 / R1, Kimi K2 and Qwen3 "-FP8" checkpoints:
+//   scale_a[M][K / 128]        fp32, row-major with a row stride of sa_stride >= K / 128 elements: one scale per
+//                              1 x 128 group of a row of A, the plain layout a per-token quantiser writes
+//   scale_b[N / 128][K / 128]  fp32, contiguous: one scale per 128 x 128 block of B
+// Per element (i, j), with nb = j / 128, over the blocks g = 0 .. K / 128 - 1 in ascending order:
+//   p_g = sum over the 128 k of block g of A[i][k] B[j][k]    fp32, v_mfma_f32_16x16x128_f8f6f4 from a zero accumulator
+//   s_g = fl(scale_a[i][g] * scale_b[nb][g])
+//   acc = fma(p_g, s_g, acc)                                  one rounding; acc starts at 0
+//   C   = bf16(acc)                                           round to nearest even, once
+// The result is deterministic and does not depend on where workgroups run: no atomics and no split of K.
+// Requires M % 128 == 0, N % 128 == 0, K % 128 == 0; A, B and C 16-B aligned, the scales 4-B aligned, no pointer
+// NULL; C overlaps none of the inputs.  K is limited as for gsx_gemm_fp8_nt: (max(BM, BN) - 1) * K + 112 < 2^31; a
+// longer K is rejected.  Launches on `stream` and returns without synchronising; everything is validated before the
+// first device call.  gsx_gemm_fp8_block_nt dispatches to the 256x256 tile when M and N are multiples of 256 and to
+// the 128x128 tile otherwise.
+// Out of scope: block-scaled operands for the decode, skinny and MoE GEMMs, and e8m0 (power-of-two) scales on the
+// hardware-scaled MFMA.
+int gsx_gemm_fp8_block_nt(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
+                          const float* scale_a, int64_t sa_stride, const float* scale_b);
+// The configurations, a table of their own in gemm_fp8_block.hip: 0 "128x128/4w", 1 "256x128/8w", 2 "256x256/8w".
+// Same conventions as the fp8 table; _launch_cfg requires M % BM == 0, N % BN == 0, K % 128 == 0.
+const char* gsx_gemm_fp8_block_cfg_name(int cfg);
+int gsx_gemm_fp8_block_cfg_tile(int cfg, int* bm, int* bn);
+int gsx_gemm_fp8_block_nt_launch_cfg(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
+                                     const float* scale_a, int64_t sa_stride, const float* scale_b, int cfg);
+// elapsed milliseconds of `iters` back-to-back gsx_gemm_fp8_block_nt on `stream`, by hip events (for benches)
+int gsx_event_time_gemm_fp8_block(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
+                                  const float* scale_a, int64_t sa_stride, const float* scale_b, int iters,
+                                  float* ms);
+// The activation quantiser: bf16 X[R][x_stride] -> e4m3 Q[R][q_stride] and fp32 S[R][s_stride], one scale per group
+// of 128 elements of a row, by the rule of GSX_ACT_OUT_FP8_ROW applied per group: amax over the group,
+// S = fl(amax / 448), Q = e4m3(fl(x * fl(448 / amax))), round to nearest even, saturating; a group of zeros gets
+// scale 1.0f and codes 0x00.  Requires K % 128 == 0, x_stride and q_stride >= K and multiples of 8,
+// s_stride >= K / 128; X and Q 16-B aligned, S 4-B aligned; X, Q and S do not overlap.  Row offsets are 64-bit.  One
+// launch, no workspace, not synchronised.  Q and S are the A and scale_a of gsx_gemm_fp8_block_nt with
+// sa_stride = s_stride (and q_stride = K).  Weights are quantised by the caller.
+int gsx_quant_fp8_block(void* stream, const void* X, int64_t x_stride, void* Q, int64_t q_stride, float* S,
+                        int64_t s_stride, int R, int K);
 
 // MXFP4 GEMM (gemm_mxfp4.hip), on v_mfma_scale_f32_16x16x128_f8f6f4 with the same schedules as the other families.
 // The operand format:

@@ -14,6 +14,10 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   ``$GSX_KERNELS_LIB``, or in the repository's build tree) or ``torch.matmul`` / hipBLASLt (``--kernel torch``);
   ``auto`` (default) takes the MFMA kernel when the library is there and says so when it falls back;
 * ``--dtype fp8`` runs the same loop on OCP e4m3 operands: the library's fp8 GEMM, or ``torch._scaled_mm``;
+* ``--dtype fp8-block`` runs it on block-scaled e4m3 operands (one fp32 scale per 1 x 128 group of an activation row
+  and per 128 x 128 block of the weights, the format of the DeepSeek-V3 and Qwen3 ``-FP8`` checkpoints): the weights are
+  block-quantised in torch once, the activations by ``gsx_quant_fp8_block`` once, and the loop is
+  ``gsx_gemm_fp8_block_nt``; ``--workload gemm`` and ``--kernel gsx`` only;
 * ``--dtype mxfp4`` runs it on MXFP4 operands (e2m1 with e8m0 block scales), made by quantising the random bf16
   matrices with the library's ``gsx_quant_mxfp4``: the library's mxfp4 GEMM only, ``--kernel torch`` has none;
 * ``--workload decode`` is an inference server's decode phase instead of the large GEMM: ``--batch`` (1..16)
@@ -282,6 +286,10 @@ class Kernels:
             L.gsx_gemm_mxfp4_nt.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
             L.gsx_quant_mxfp4.argtypes = [vp, vp, vp, vp, i32, i32]
             L.gsx_gemm_mxfp4_nt.restype = L.gsx_quant_mxfp4.restype = i32
+        if hasattr(L, "gsx_gemm_fp8_block_nt"):  # likewise: an image built before the block-scaled fp8 kernels
+            L.gsx_gemm_fp8_block_nt.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, ctypes.c_int64, vp]
+            L.gsx_quant_fp8_block.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, i32, i32]
+            L.gsx_gemm_fp8_block_nt.restype = L.gsx_quant_fp8_block.restype = i32
         if hasattr(L, "gsx_decode_gemm_nt"):  # likewise: an image built before the decode kernels
             L.gsx_decode_gemm_nt.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32]
             L.gsx_decode_gemm_nt.restype = i32
@@ -373,6 +381,20 @@ class Kernels:
             raise RuntimeError(f"{self.path} has no gsx_gemm_fp8_nt: rebuild it")
         self._ck(self.L.gsx_gemm_fp8_nt(s, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m, n, k,
                                         None, None, 0), "gemm_fp8_nt")
+
+    def quant_fp8_block(self, s, x: int, q: int, sc: int, rows: int, k: int):
+        """bf16 ``x[rows][k]`` -> e4m3 ``q[rows][k]`` and one fp32 scale per 128 elements, ``sc[rows][k / 128]``."""
+        if not hasattr(self.L, "gsx_quant_fp8_block"):
+            raise RuntimeError(f"{self.path} has no gsx_quant_fp8_block: rebuild it")
+        self._ck(self.L.gsx_quant_fp8_block(s, ctypes.c_void_p(x), k, ctypes.c_void_p(q), k, ctypes.c_void_p(sc),
+                                            k // 128, rows, k), "quant_fp8_block")
+
+    def gemm_fp8_block(self, s, a: int, b: int, c: int, m: int, n: int, k: int, sa: int, sb: int):
+        """e4m3 operands with ``sa[m][k / 128]`` and ``sb[n / 128][k / 128]`` fp32 block scales."""
+        if not hasattr(self.L, "gsx_gemm_fp8_block_nt"):
+            raise RuntimeError(f"{self.path} has no gsx_gemm_fp8_block_nt: rebuild it")
+        self._ck(self.L.gsx_gemm_fp8_block_nt(s, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m, n, k,
+                                              ctypes.c_void_p(sa), k // 128, ctypes.c_void_p(sb)), "gemm_fp8_block_nt")
 
     def has_mxfp4(self) -> bool:
         return hasattr(self.L, "gsx_gemm_mxfp4_nt")
@@ -1304,8 +1326,10 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         hold = torch.empty(int(allocated * (1 << 30) * 0.9) // 2, dtype=torch.bfloat16, device=dev)
         hold.fill_(1)
     m = n = k = size
-    if dtype not in ("bf16", "fp8", "mxfp4"):
-        raise SystemExit(f"--dtype {dtype}: bf16, fp8 or mxfp4")
+    if dtype not in ("bf16", "fp8", "fp8-block", "mxfp4"):
+        raise SystemExit(f"--dtype {dtype}: bf16, fp8, fp8-block or mxfp4")
+    if why := fp8_block_refusal(workload, dtype, kernel, size):
+        raise SystemExit(why)
     if workload not in ("gemm", "decode", "decode-wide", "attn", "server", "layer", "prefill", "prefill-moe",
                         "generate"):
         raise SystemExit(f"--workload {workload}: gemm, decode, decode-wide, attn, server, layer, prefill, prefill-moe "
@@ -1441,6 +1465,20 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
 
             def gemm(s, pa, pb, pc, m, n, k):
                 kl.gemm_mxfp4(s, pa, pb, pc, m, n, k, sa.data_ptr(), sb.data_ptr())
+        if dtype == "fp8-block":  # weights block-quantised in torch, activations by the library, both once
+            blocks = b.float().view(n // 128, 128, k // 128, 128)
+            sb = (blocks.abs().amax(dim=(1, 3)).clamp_min(2.0 ** -100) / 448.0).contiguous()
+            qb = (blocks / sb[:, None, :, None]).clamp(-448.0, 448.0).view(n, k).to(torch.float8_e4m3fn)
+            qa = torch.empty(m, k, device=dev, dtype=torch.float8_e4m3fn)
+            sa = torch.empty(m, k // 128, device=dev, dtype=torch.float32)
+            torch.cuda.synchronize()
+            kl.quant_fp8_block(gs, a.data_ptr(), qa.data_ptr(), sa.data_ptr(), m, k)
+            kl.sync(gs)
+            a, b = qa, qb
+            del blocks
+
+            def gemm(s, pa, pb, pc, m, n, k):
+                kl.gemm_fp8_block(s, pa, pb, pc, m, n, k, sa.data_ptr(), sb.data_ptr())
 
         def step():
             gemm(gs, a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k)
@@ -1558,6 +1596,20 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     return out
 
 
+def fp8_block_refusal(workload: str, dtype: str, kernel: str, size: int) -> str | None:
+    """Why ``--dtype fp8-block`` cannot run, or None: the block-scaled GEMM is the large-GEMM workload's only."""
+    if dtype != "fp8-block":
+        return None
+    if workload != "gemm":
+        return (f"--workload {workload} --dtype fp8-block: block-scaled operands are the gemm workload's only (the "
+                "decode, skinny and MoE GEMMs take none)")
+    if kernel == "torch":
+        return "--dtype fp8-block needs the library's kernels (--kernel gsx)"
+    if size < 128 or size % 128:
+        return f"--dtype fp8-block --size {size}: a multiple of 128"
+    return None
+
+
 class _Parser(argparse.ArgumentParser):
     """``--batch`` has a range per workload: 1..16 rows (gemm ignores it, decode uses it), 1..128 rows for decode-wide,
     1..256 sequences for attn
@@ -1573,6 +1625,8 @@ class _Parser(argparse.ArgumentParser):
             self.error(f"argument --batch: {ns.batch} is not in 1..{top} (--workload {ns.workload})")
         if ns.workload == "generate" and (why := generate_refusal(ns.batch, ns.vocab)):
             self.error(f"--workload generate: {why}")
+        if why := fp8_block_refusal(ns.workload, ns.dtype, getattr(ns, "kernel", "gsx"), ns.size):
+            self.error(why)
         if why := moe_refusal(ns.workload, getattr(ns, "experts", 0), getattr(ns, "experts_active", MOE_MAX_ACTIVE)):
             self.error(why)
         if ns.workload in ("prefill", "prefill-moe"):
@@ -1632,8 +1686,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--allocated", type=float, default=float(os.environ.get(f"{p}_CONTAINER", "0") or 0),
                     help="this container's share (the device plugin's *_CONTAINER env)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "gsx", "torch"])
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"],
-                    help="operand type of the GEMM: bf16, fp8 (OCP e4m3) or mxfp4 (e2m1 with e8m0 block scales, "
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "fp8-block", "mxfp4"],
+                    help="operand type of the GEMM: bf16, fp8 (OCP e4m3), fp8-block (e4m3 with fp32 scales per 1x128 "
+                         "group of the activations and per 128x128 block of the weights; --workload gemm and "
+                         "--kernel gsx only) or mxfp4 (e2m1 with e8m0 block scales, "
                          "quantised from bf16 by the library; --kernel gsx only); the output stays bf16")
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--workload", default="gemm",

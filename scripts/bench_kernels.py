@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Micro-benchmarks of the HIP kernels on one MI355X: bf16, fp8 and mxfp4 GEMM (ours vs torch/hipBLASLt), the decode
+"""Micro-benchmarks of the HIP kernels on one MI355X: bf16, fp8, block-scaled fp8 and mxfp4 GEMM (ours vs torch/hipBLASLt), the decode
 GEMM (every configuration vs torch and a read-bandwidth yardstick), the decode attention over a paged KV cache (every
 configuration and split count vs torch SDPA and the same yardstick), RoPE + KV append and the fused add + RMSNorm and
 SwiGLU (vs a read-and-rewrite yardstick), the causal prefill attention over the paged cache (vs torch SDPA on a
@@ -122,6 +122,93 @@ def gemm_fp8(size_list, iters=20, rounds=3):
             row[f"{name}_tflops"] = round(statistics.median(r), 1)
         out.append(row)
         del a, b, a16, b16, c
+    s.destroy()
+    return out
+
+
+FP8_BLOCK_SHAPES = [(4096, 4096, 4096), (8192, 8192, 8192),
+                    # M = 4096 against the DeepSeek-V3 projections (N, K); the last has four K-tiles
+                    (4096, 7168, 2048), (4096, 4096, 7168), (4096, 24576, 1536), (4096, 7168, 16384), (4096, 32768, 512)]
+
+
+def gemm_fp8_block(shapes=FP8_BLOCK_SHAPES, iters=20, rounds=5):
+    """The block-scaled fp8 GEMM (every configuration and the dispatching entry point) on activations quantised by
+    ``gsx_quant_fp8_block`` and weights block-quantised in torch, against ``gsx_gemm_fp8_nt`` with per-row scales on
+    the same bytes (the ceiling: the same MFMA work without the fold), ``gsx_gemm_bf16_nt`` on the dequantised
+    operands (what a user runs today) and torch's own block-scaled ``_scaled_mm`` where this build takes the call (its
+    refusal otherwise).  The variants alternate inside every round of one process; per variant the median TFLOP/s of
+    ``rounds`` rounds after a warm-up round, and ``spread_pct``, the largest (max - min) / median of any variant."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    for m, n, k in shapes:
+        g = k // 128
+        x = torch.randn(m, k, device="cuda", dtype=torch.bfloat16)
+        blocks = torch.randn(n, k, device="cuda").view(n // 128, 128, g, 128)
+        sb = (blocks.abs().amax(dim=(1, 3)) / 448.0).contiguous()
+        b = (blocks / sb[:, None, :, None]).reshape(n, k).to(torch.float8_e4m3fn)
+        del blocks
+        a = torch.empty(m, k, device="cuda", dtype=torch.float8_e4m3fn)
+        sa = torch.empty(m, g, device="cuda", dtype=torch.float32)
+        c = torch.empty(m, n, device="cuda", dtype=torch.bfloat16)
+        torch.cuda.synchronize()
+        hip.quant_fp8_block(s, x.data_ptr(), k, a.data_ptr(), k, sa.data_ptr(), g, m, k)
+        s.sync()
+        a16 = (a.float() * sa.repeat_interleave(128, dim=1)).bfloat16()
+        b16 = (b.float() * sb.repeat_interleave(128, dim=0).repeat_interleave(128, dim=1)).bfloat16()
+        row_a, row_b = sa[:, 0].contiguous(), torch.ones(n, device="cuda")
+        ref = a16.float() @ b16.float().t()
+        torch.cuda.synchronize()
+        ptrs = (a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k)
+        scales = (sa.data_ptr(), g, sb.data_ptr())
+        row = {"m": m, "n": n, "k": k}
+        variants = {}
+        for cfg, name in hip.gemm_fp8_block_cfgs().items():
+            try:
+                hip.gemm_fp8_block_nt_cfg(s, *ptrs, cfg, *scales)
+            except hip.HipError:
+                continue
+            variants[f"cfg{cfg}_{name}"] = lambda cfg=cfg: hip.gemm_fp8_block_nt_cfg(s, *ptrs, cfg, *scales)
+        variants["gsx"] = lambda: hip.gemm_fp8_block_nt(s, *ptrs, *scales)
+        variants["fp8_row_gsx"] = lambda: hip.gemm_fp8_nt(s, *ptrs, row_a.data_ptr(), row_b.data_ptr(), hip.SCALE_ROW)
+        variants["bf16_gsx"] = lambda: hip.gemm_bf16_nt(s, a16.data_ptr(), b16.data_ptr(), c.data_ptr(), m, n, k)
+        c.zero_()
+        torch.cuda.synchronize()
+        variants["gsx"]()
+        s.sync()
+        row["gsx_rel_err"] = round(((c.float() - ref).abs().max() / ref.abs().max()).item(), 5)
+        del ref
+        try:  # torch's block-scaled path: scale_a [m][k / 128], scale_b [k / 128][n / 128]
+            sbt = sb.t().contiguous()
+            torch._scaled_mm(a, b.t(), scale_a=sa, scale_b=sbt, out_dtype=torch.bfloat16)
+            variants["torch"] = lambda: torch._scaled_mm(a, b.t(), scale_a=sa, scale_b=sbt, out_dtype=torch.bfloat16,
+                                                         out=c)
+        except Exception as e:  # noqa: BLE001 - whatever this build answers is the record
+            row["torch_refusal"] = str(e).splitlines()[0][:300]
+
+        def timed(fn):
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(ts)
+                for _ in range(iters):
+                    fn()
+                e1.record(ts)
+            e1.synchronize()
+            return 2 * m * n * k / (e0.elapsed_time(e1) / iters) / 1e9
+
+        runs = {name: [] for name in variants}
+        for r in range(rounds + 1):  # the first round warms up clocks and code objects
+            for name, fn in variants.items():
+                t = timed(fn)
+                if r:
+                    runs[name].append(t)
+        for name, r in runs.items():
+            row[f"{name}_tflops"] = round(statistics.median(r), 1)
+        row["spread_pct"] = round(max((max(r) - min(r)) / statistics.median(r) for r in runs.values()) * 100, 2)
+        out.append(row)
+        del x, a, b, a16, b16, c
+        torch.cuda.empty_cache()
     s.destroy()
     return out
 
@@ -1514,7 +1601,7 @@ if __name__ == "__main__":
     sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (2048, 8192, 4096), (16384, 16384, 8192)]
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
-                "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "gemm_skinny": gemm_skinny,
+                "gemm_fp8_block": gemm_fp8_block, "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "gemm_skinny": gemm_skinny,
                 "attn_decode": attn_decode, "attn_multi": attn_multi, "attn_mla": attn_mla,
                 "kv_append": kv_append, "norm_act": norm_act, "attn_prefill": attn_prefill, "sample": sample,
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
