@@ -149,6 +149,7 @@ def lib():
         _skinny_sig = [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, u64]
         # stream, A, B, C; M, N, K; scale_a, sa_stride, scale_b
         _fp8_block_sig = [vp, vp, vp, vp, i32, i32, i32, vp, ctypes.c_int64, vp]
+        _skinny_fp8_block_sig = [*_fp8_block_sig, vp, u64]  # and workspace, workspace_bytes
         sig = {
             "gsx_last_error": ([], ctypes.c_char_p),
             "gsx_device_count": ([ctypes.POINTER(i32)], i32),
@@ -205,6 +206,14 @@ def lib():
             "gsx_skinny_gemm_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
             "gsx_skinny_gemm_nt_launch_cfg": ([*_skinny_sig, i32, i32], i32),
             "gsx_event_time_skinny_gemm": ([*_skinny_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_skinny_gemm_fp8_block_nt": (_skinny_fp8_block_sig, i32),
+            "gsx_skinny_gemm_fp8_block_workspace_bytes": ([i32, i32, i32, ctypes.POINTER(u64)], i32),
+            "gsx_skinny_gemm_fp8_block_pick": ([i32] * 3 + [ctypes.POINTER(i32)] * 2, i32),
+            "gsx_skinny_gemm_fp8_block_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_skinny_gemm_fp8_block_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
+            "gsx_skinny_gemm_fp8_block_nt_launch_cfg": ([*_skinny_fp8_block_sig, i32, i32], i32),
+            "gsx_event_time_skinny_gemm_fp8_block": ([*_skinny_fp8_block_sig, i32, ctypes.POINTER(ctypes.c_float)],
+                                                     i32),
             "gsx_decode_attn": (_attn_sig, i32),
             "gsx_decode_attn_launch_cfg": ([*_attn_sig, i32, i32], i32),
             "gsx_decode_attn_workspace_bytes": ([i32] * 5 + [ctypes.POINTER(u64)], i32),
@@ -803,6 +812,71 @@ def time_skinny_gemm(stream: Stream, kind: str, a: int, b: int, c: int, m: int, 
     _ck(lib().gsx_event_time_skinny_gemm(*_skinny_args(stream, kind, a, b, c, m, n, k, scale_a, scale_b, scale_mode,
                                                        workspace, workspace_bytes), iters, ctypes.byref(ms)),
         "time_skinny_gemm")
+    return ms.value
+
+
+def _skinny_fp8_block_args(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, scale_a: int,
+                           sa_stride: int, scale_b: int, workspace: int, workspace_bytes: int) -> tuple:
+    return (*_fp8_block_args(stream, a, b, c, m, n, k, scale_a, sa_stride, scale_b), ctypes.c_void_p(workspace),
+            workspace_bytes)
+
+
+def skinny_gemm_fp8_block_nt(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, scale_a: int,
+                             sa_stride: int, scale_b: int, workspace: int = 0, workspace_bytes: int = 0):
+    """``C[m][n]`` (bf16) ``= A[m][k] * B[n][k]^T`` for ``1 <= m <= 128`` on the block-scaled e4m3 operands of
+    :func:`gemm_fp8_block_nt` (``scale_a[m][k / 128]`` with rows ``sa_stride`` elements apart,
+    ``scale_b[ceil(n / 128)][k / 128]``): the skinny GEMM's plan, ``b`` streamed from HBM once.  ``workspace`` is device
+    memory of at least :func:`skinny_gemm_fp8_block_workspace_bytes` bytes.  Not synchronised."""
+    _ck(lib().gsx_skinny_gemm_fp8_block_nt(*_skinny_fp8_block_args(stream, a, b, c, m, n, k, scale_a, sa_stride,
+                                                                   scale_b, workspace, workspace_bytes)),
+        "skinny_gemm_fp8_block_nt")
+
+
+def skinny_gemm_fp8_block_workspace_bytes(m: int, n: int, k: int) -> int:
+    """Bytes of workspace :func:`skinny_gemm_fp8_block_nt` needs for this shape (0: none)."""
+    v = ctypes.c_uint64(0)
+    _ck(lib().gsx_skinny_gemm_fp8_block_workspace_bytes(m, n, k, ctypes.byref(v)),
+        "skinny_gemm_fp8_block_workspace_bytes")
+    return v.value
+
+
+def skinny_gemm_fp8_block_pick(m: int, n: int, k: int) -> tuple[int, int]:
+    """``(cfg, splits)`` that :func:`skinny_gemm_fp8_block_nt` takes for this shape."""
+    cfg, splits = ctypes.c_int(0), ctypes.c_int(0)
+    _ck(lib().gsx_skinny_gemm_fp8_block_pick(m, n, k, ctypes.byref(cfg), ctypes.byref(splits)),
+        "skinny_gemm_fp8_block_pick")
+    return cfg.value, splits.value
+
+
+def skinny_gemm_fp8_block_cfgs() -> dict[int, tuple[str, int, int, int]]:
+    """``{index: (name, bn, waves, inflight)}`` of the block-scaled skinny configurations, read from the library's
+    table (native/kernels/gemm_skinny_fp8_block.hip)."""
+    out: dict[int, tuple[str, int, int, int]] = {}
+    while (name := lib().gsx_skinny_gemm_fp8_block_cfg_name(len(out))) is not None:
+        v = [ctypes.c_int(0) for _ in range(3)]
+        if lib().gsx_skinny_gemm_fp8_block_cfg_shape(len(out), *map(ctypes.byref, v)) != 0:
+            raise HipError(f"skinny fp8 block cfg {len(out)} has a name and no shape")
+        out[len(out)] = (name.decode(), *(x.value for x in v))
+    return out
+
+
+def skinny_gemm_fp8_block_nt_cfg(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, cfg: int,
+                                 splits: int, scale_a: int, sa_stride: int, scale_b: int, workspace: int = 0,
+                                 workspace_bytes: int = 0):
+    """Launch one configuration of the block-scaled skinny GEMM with ``splits`` (1..16) splits of K; the workspace
+    needs ``splits * m * n * 4`` bytes when ``splits > 1``.  An unknown config raises HipError."""
+    _ck(lib().gsx_skinny_gemm_fp8_block_nt_launch_cfg(
+        *_skinny_fp8_block_args(stream, a, b, c, m, n, k, scale_a, sa_stride, scale_b, workspace, workspace_bytes),
+        cfg, splits), f"skinny gemm fp8 block cfg {cfg} splits {splits}")
+
+
+def time_skinny_gemm_fp8_block(stream: Stream, a: int, b: int, c: int, m: int, n: int, k: int, iters: int,
+                               scale_a: int, sa_stride: int, scale_b: int, workspace: int = 0,
+                               workspace_bytes: int = 0) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_skinny_gemm_fp8_block(
+        *_skinny_fp8_block_args(stream, a, b, c, m, n, k, scale_a, sa_stride, scale_b, workspace, workspace_bytes),
+        iters, ctypes.byref(ms)), "time_skinny_gemm_fp8_block")
     return ms.value
 
 

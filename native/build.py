@@ -14,7 +14,8 @@ Targets (outputs land in ``gpushare_scheduler_extender_amd/_native/``):
                 HBM touch/verify, HBM memory test, compute (MFMA / VALU / LDS) test, bf16, fp8 and MXFP4 MFMA GEMM
                 workload with the MXFP4 quantiser, the block-scaled fp8 GEMM (1x128 and 128x128 scales) with its
                 activation quantiser (gemm_fp8_block.hip), the decode GEMM (M <= 16) on the same operands, the skinny GEMM
-                (M <= 128, bf16 and fp8, with a split of K; gemm_skinny.hip), decode attention over a
+                (M <= 128, bf16 and fp8, with a split of K; gemm_skinny.hip) and its block-scaled fp8 form
+                (gemm_skinny_fp8_block.hip), decode attention over a
                 paged KV cache (attn_decode.hip) and its multi-token form (attn_decode_multi.hip), multi-head latent
                 attention decode over a paged latent cache (attn_mla.hip), RoPE + KV-cache
                 append (kv_append.hip), fused residual add + RMSNorm and SwiGLU (norm_act.hip), causal prefill attention over the same cache (attn_prefill.hip), the token

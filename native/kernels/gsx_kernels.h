@@ -32,6 +32,8 @@
 //                          over a paged KV cache in bf16 or e4m3 (attn_decode.hip);
 //  * skinny GEMM         — 17 to 128 rows (any M <= 128) against weights streamed from HBM
 //                          once, bf16 and e4m3, with a split of K (gemm_skinny.hip);
+//  * block-scaled fp8 skinny GEMM — the same row counts on the block-scaled operands (1 x 128 and 128 x 128 fp32
+//                          scales), every K block scaled as it is folded (gemm_skinny_fp8_block.hip);
 //  * RoPE + KV append    — rotates Q and K and writes the new tokens' K and V into
 //                          their page slots, quantised for an e4m3 cache: what makes
 //                          the cache the attention reads (kv_append.hip);
@@ -183,8 +185,8 @@ int gsx_event_time_gemm_fp8(void* stream, const void* A, const void* B, void* C,
 // longer K is rejected.  Launches on `stream` and returns without synchronising; everything is validated before the
 // first device call.  gsx_gemm_fp8_block_nt dispatches to the 256x256 tile when M and N are multiples of 256 and to
 // the 128x128 tile otherwise.
-// Out of scope: block-scaled operands for the decode, skinny and MoE GEMMs, and e8m0 (power-of-two) scales on the
-// hardware-scaled MFMA.
+// Out of scope: block-scaled operands for the decode and MoE GEMMs, and e8m0 (power-of-two) scales on the
+// hardware-scaled MFMA.  1 <= M <= 128 is gsx_skinny_gemm_fp8_block_nt (below).
 int gsx_gemm_fp8_block_nt(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
                           const float* scale_a, int64_t sa_stride, const float* scale_b);
 // The configurations, a table of their own in gemm_fp8_block.hip: 0 "128x128/4w", 1 "256x128/8w", 2 "256x256/8w".
@@ -314,6 +316,53 @@ int gsx_skinny_gemm_nt_launch_cfg(void* stream, int kind, const void* A, const v
 int gsx_event_time_skinny_gemm(void* stream, int kind, const void* A, const void* B, void* C, int M, int N, int K,
                                const void* scale_a, const void* scale_b, int scale_mode, void* workspace,
                                uint64_t workspace_bytes, int iters, float* ms);
+
+// Block-scaled fp8 skinny GEMM (gemm_skinny_fp8_block.hip): C[M][N] (bf16) = A[M][K] * B[N][K]^T with 1 <= M <= 128 on
+// exactly the operands of gsx_gemm_fp8_block_nt: A and B OCP e4m3, row-major; scale_a[M][K / 128] fp32 with a row stride
+// of sa_stride >= K / 128 elements (what gsx_quant_fp8_block writes for any row count; exactly M rows of it, nothing of
+// it or of A is read past row M - 1, and nothing of C is written past it); scale_b[ceil(N / 128)][K / 128] fp32,
+// contiguous, whose last block row may cover fewer than 128 columns.  The plan is the skinny GEMM's: B streamed from HBM
+// once, a workgroup per strip of 32 or 64 columns and one of `splits` runs of K, the partials of splits > 1 in
+// `workspace`, part[split][M][N], and a second launch on the same stream.
+// Per element (i, j), with nb = j / 128, over the K-tiles g of 128 k each:
+//   p_g = sum over the 128 k of K-tile g of A[i][k] B[j][k]   fp32, one v_mfma_f32_16x16x128_f8f6f4 from a zero accumulator
+//   s_g = fl(scale_a[i][g] * scale_b[nb][g])
+//   a wave folds the K-tiles it owns (g = first + w, first + w + W, ... of its split's run) in ascending order:
+//         acc = fma(p_g, s_g, acc), starting from 0
+//   the W waves' accumulators are added in the order of the wave index, the splits' sums in the order of the split index
+//   C = bf16(sum)                                             round to nearest even, once
+// There are no atomics and no workgroup waits for another.  The partials in the workspace are already scaled, so the
+// reduce launch only adds and rounds.  The result depends on the configuration and on `splits` and on nothing else: row i
+// has the same bits at every M that contains it, wherever workgroups run.  For general scales the fold order differs from
+// gsx_gemm_fp8_block_nt (one chain over all g), and so may the last bits.
+// Requirements: 1 <= M <= 128; N % 64 == 0 (_launch_cfg: N % BN == 0 too), so that a strip never crosses a 128-column
+// scale block; K % 128 == 0; 1 <= splits <= 16; A, B, C and the workspace 16-B aligned, the scales 4-B aligned; no
+// pointer NULL but a workspace that is not needed; the workspace holds splits * M * N * 4 bytes when splits > 1 (a
+// smaller one is refused with the bytes needed in the text); ceil(M / 16) * 16 rows of A, and as many of scale_a, stay
+// inside a 32-bit buffer range; C overlaps none of A, B, the scales and the workspace.  Row offsets into B, scale_b, C and
+// the workspace are 64-bit.  Launches on `stream` and returns without synchronising; everything is validated before the
+// first device call.  gsx_skinny_gemm_fp8_block_nt picks configuration and splits by ceil(M / 16), N and K (sfb_pick() in
+// gemm_skinny_fp8_block.hip; _pick returns its choice); where padding A to 128 rows and calling gsx_gemm_fp8_block_nt
+// measured faster is listed in profiles/gemm_skinny_fp8_block/README.md.
+int gsx_skinny_gemm_fp8_block_nt(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
+                                 const float* scale_a, int64_t sa_stride, const float* scale_b, void* workspace,
+                                 uint64_t workspace_bytes);
+// bytes of workspace gsx_skinny_gemm_fp8_block_nt needs for this shape (0: none)
+int gsx_skinny_gemm_fp8_block_workspace_bytes(int M, int N, int K, uint64_t* bytes);
+// the configuration and the splits gsx_skinny_gemm_fp8_block_nt takes for this shape
+int gsx_skinny_gemm_fp8_block_pick(int M, int N, int K, int* cfg, int* splits);
+// The configurations, a table of the kernel's own: 0 "32/4w-f2", 1 "64/4w-f1", 2 "32/4w-f1": columns of a strip (BN) /
+// waves per workgroup - K-tiles a wave keeps in flight.  _cfg_name returns NULL and _cfg_shape nonzero outside the table.
+// _launch_cfg runs one configuration with `splits` splits of K.
+const char* gsx_skinny_gemm_fp8_block_cfg_name(int cfg);
+int gsx_skinny_gemm_fp8_block_cfg_shape(int cfg, int* bn, int* waves, int* inflight);
+int gsx_skinny_gemm_fp8_block_nt_launch_cfg(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
+                                            const float* scale_a, int64_t sa_stride, const float* scale_b,
+                                            void* workspace, uint64_t workspace_bytes, int cfg, int splits);
+// elapsed milliseconds of `iters` back-to-back gsx_skinny_gemm_fp8_block_nt on `stream`, by hip events (for benches)
+int gsx_event_time_skinny_gemm_fp8_block(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
+                                         const float* scale_a, int64_t sa_stride, const float* scale_b,
+                                         void* workspace, uint64_t workspace_bytes, int iters, float* ms);
 
 // Decode attention over a paged KV cache (attn_decode.hip): one new token per sequence, grouped-query attention in
 // which Hq query heads share Hkv KV heads in groups of G = Hq / Hkv.

@@ -17,7 +17,7 @@ builds; nothing else of this repository): counterpart of the reference's sample 
 * ``--dtype fp8-block`` runs it on block-scaled e4m3 operands (one fp32 scale per 1 x 128 group of an activation row
   and per 128 x 128 block of the weights, the format of the DeepSeek-V3 and Qwen3 ``-FP8`` checkpoints): the weights are
   block-quantised in torch once, the activations by ``gsx_quant_fp8_block`` once, and the loop is
-  ``gsx_gemm_fp8_block_nt``; ``--workload gemm`` and ``--kernel gsx`` only;
+  ``gsx_gemm_fp8_block_nt``; ``--workload gemm`` and ``--workload decode-wide`` (below), ``--kernel gsx`` only;
 * ``--dtype mxfp4`` runs it on MXFP4 operands (e2m1 with e8m0 block scales), made by quantising the random bf16
   matrices with the library's ``gsx_quant_mxfp4``: the library's mxfp4 GEMM only, ``--kernel torch`` has none;
 * ``--workload decode`` is an inference server's decode phase instead of the large GEMM: ``--batch`` (1..16)
@@ -29,7 +29,8 @@ builds; nothing else of this repository): counterpart of the reference's sample 
 * ``--workload decode-wide`` is the decode workload at the row counts of continuous batching: ``--batch`` (1..128)
   rows against the same ring through the library's skinny GEMM (``gsx_skinny_gemm_nt``), whose workspace for the split
   of K is allocated once.  ``--dtype`` is bf16 or fp8 (the skinny GEMM has no mxfp4 form); ``--kernel torch`` runs the
-  decode workload's comparator.  It reports the decode workload's fields;
+  decode workload's comparator.  ``--dtype fp8-block`` (``--kernel gsx``, ``--size`` a multiple of 128) runs the ring
+  block-quantised through ``gsx_skinny_gemm_fp8_block_nt``.  It reports the decode workload's fields;
 * ``--workload attn`` is the other half of a decode step: attention of one new token per sequence over a paged KV
   cache.  ``--batch`` sequences (1..256) of ``--context`` tokens each, ``--heads`` query heads sharing ``--kv-heads``
   KV heads at D = 128, pages of ``--page`` tokens handed out through a random permutation, as an allocator leaves
@@ -297,6 +298,10 @@ class Kernels:
             L.gsx_skinny_gemm_nt.argtypes = [*L.gsx_decode_gemm_nt.argtypes, vp, ctypes.c_uint64]
             L.gsx_skinny_gemm_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_uint64)]
             L.gsx_skinny_gemm_nt.restype = L.gsx_skinny_gemm_workspace_bytes.restype = i32
+        if hasattr(L, "gsx_skinny_gemm_fp8_block_nt"):  # likewise: an image built before its block-scaled form
+            L.gsx_skinny_gemm_fp8_block_nt.argtypes = [*L.gsx_gemm_fp8_block_nt.argtypes, vp, ctypes.c_uint64]
+            L.gsx_skinny_gemm_fp8_block_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_uint64)]
+            L.gsx_skinny_gemm_fp8_block_nt.restype = L.gsx_skinny_gemm_fp8_block_workspace_bytes.restype = i32
         if hasattr(L, "gsx_decode_attn"):  # likewise: an image built before the attention kernel
             L.gsx_decode_attn.argtypes = ([vp, i32] + [vp] * 6 + [i32] * 8 + [ctypes.c_float] * 3
                                           + [vp, ctypes.c_uint64])
@@ -432,6 +437,22 @@ class Kernels:
         self._ck(self.L.gsx_skinny_gemm_nt(s, DECODE_KINDS[dtype], ctypes.c_void_p(a), ctypes.c_void_p(b),
                                            ctypes.c_void_p(c), m, n, k, None, None, 0, ctypes.c_void_p(ws), ws_bytes),
                  "skinny_gemm_nt")
+
+    def skinny_fp8_block_workspace_bytes(self, m: int, n: int, k: int) -> int:
+        if not hasattr(self.L, "gsx_skinny_gemm_fp8_block_nt"):
+            raise RuntimeError(f"{self.path} has no gsx_skinny_gemm_fp8_block_nt: rebuild it")
+        v = ctypes.c_uint64(0)
+        self._ck(self.L.gsx_skinny_gemm_fp8_block_workspace_bytes(m, n, k, ctypes.byref(v)),
+                 "skinny_gemm_fp8_block_workspace_bytes")
+        return v.value
+
+    def skinny_gemm_fp8_block(self, s, a: int, b: int, c: int, m: int, n: int, k: int, sa: int, sb: int, ws: int,
+                              ws_bytes: int):
+        """``c[m][n] = a[m][k] * b[n][k]^T`` for m <= 128 on block-scaled e4m3 operands: ``sa[m][k / 128]``,
+        ``sb[n / 128][k / 128]``."""
+        self._ck(self.L.gsx_skinny_gemm_fp8_block_nt(s, ctypes.c_void_p(a), ctypes.c_void_p(b), ctypes.c_void_p(c), m,
+                                                     n, k, ctypes.c_void_p(sa), k // 128, ctypes.c_void_p(sb),
+                                                     ctypes.c_void_p(ws), ws_bytes), "skinny_gemm_fp8_block_nt")
 
     def attn_workspace_bytes(self, b: int, hq: int, page: int, max_seq_len: int) -> int:
         if not hasattr(self.L, "gsx_decode_attn"):
@@ -668,8 +689,36 @@ def decode_steps(torch, kl, gs, stream, dev, dtype: str, a, c, layers: int, wide
     instead of its decode GEMM, with one workspace for all launches."""
     m, k = a.shape
     n = c.shape[1]
-    wdt = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn, "mxfp4": torch.uint8}[dtype]
+    wdt = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn, "fp8-block": torch.float8_e4m3fn,
+           "mxfp4": torch.uint8}[dtype]
     w = torch.empty(layers, n, k // 2 if dtype == "mxfp4" else k, device=dev, dtype=wdt)
+    if dtype == "fp8-block":  # decode-wide only: weights block-quantised in torch, the rows by the library, both once
+        ws = torch.empty(layers, n // 128, k // 128, device=dev, dtype=torch.float32)
+        qa = torch.empty(m, k, device=dev, dtype=torch.float8_e4m3fn)
+        sa = torch.empty(m, k // 128, device=dev, dtype=torch.float32)
+        torch.cuda.synchronize()
+        kl.quant_fp8_block(gs, a.data_ptr(), qa.data_ptr(), sa.data_ptr(), m, k)
+        kl.sync(gs)
+        for i in range(layers):
+            blocks = torch.randn(n, k, device=dev, dtype=torch.bfloat16).float().view(n // 128, 128, k // 128, 128)
+            ws[i].copy_(blocks.abs().amax(dim=(1, 3)).clamp_min(2.0 ** -100) / 448.0)
+            w[i].copy_((blocks / ws[i][:, None, :, None]).clamp(-448.0, 448.0).view(n, k).to(wdt))
+            del blocks
+        part_bytes = kl.skinny_fp8_block_workspace_bytes(m, n, k)
+        part = torch.empty(max(part_bytes, 16), device=dev, dtype=torch.uint8)
+        torch.cuda.synchronize()
+
+        def step():
+            for i in range(layers):
+                kl.skinny_gemm_fp8_block(gs, qa.data_ptr(), w.data_ptr() + i * n * k, c.data_ptr(), m, n, k,
+                                         sa.data_ptr(), ws.data_ptr() + i * (n // 128) * (k // 128) * 4,
+                                         part.data_ptr(), part_bytes)
+
+        def sync():
+            kl.sync(gs)
+
+        step.keep = (w, ws, qa, sa, part)
+        return step, sync
     if dtype == "mxfp4":  # the library's quantiser makes weights and activations; it takes any row count
         ws = torch.empty(layers, n, k // 32, device=dev, dtype=torch.uint8)
         qa = torch.empty(m, k // 2, device=dev, dtype=torch.uint8)
@@ -1597,12 +1646,13 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
 
 
 def fp8_block_refusal(workload: str, dtype: str, kernel: str, size: int) -> str | None:
-    """Why ``--dtype fp8-block`` cannot run, or None: the block-scaled GEMM is the large-GEMM workload's only."""
+    """Why ``--dtype fp8-block`` cannot run, or None: the block-scaled GEMMs are the large one (``gemm``) and the
+    skinny one (``decode-wide``)."""
     if dtype != "fp8-block":
         return None
-    if workload != "gemm":
-        return (f"--workload {workload} --dtype fp8-block: block-scaled operands are the gemm workload's only (the "
-                "decode, skinny and MoE GEMMs take none)")
+    if workload not in ("gemm", "decode-wide"):
+        return (f"--workload {workload} --dtype fp8-block: block-scaled operands are the gemm workload's only among "
+                "the large GEMMs, and decode-wide's among the streaming ones (the decode and MoE GEMMs take none)")
     if kernel == "torch":
         return "--dtype fp8-block needs the library's kernels (--kernel gsx)"
     if size < 128 or size % 128:

@@ -530,6 +530,102 @@ def gemm_skinny(shapes=SKINNY_SHAPES, ms=(17, 32, 64, 128), kinds=("bf16", "fp8"
     return out
 
 
+def gemm_skinny_fp8_block(shapes=(*SKINNY_SHAPES, FP8_BLOCK_SHAPES[3][1:], FP8_BLOCK_SHAPES[5][1:]),
+                          ms=(17, 32, 64, 128), ring_bytes=(2 << 30) + 1, reps=3, rounds=3):
+    """The block-scaled fp8 skinny GEMM on the method of :func:`gemm_skinny` (a ring of weight matrices of more than
+    2 GiB, variants alternating inside a round, one warm-up round, median TB/s of weight bytes and the spread): every
+    configuration with the dispatched splits, the dispatched configuration with the neighbouring splits
+    (``gsx_s<splits>``), the dispatching entry point (``gsx``), the bar (``pad128``: ``gsx_gemm_fp8_block_nt`` on A
+    and scale_a padded to 128 rows, the only way to run these shapes without this kernel) and the ceiling
+    (``skinny_fp8_row``: ``gsx_skinny_gemm_nt`` in fp8 with per-row scales on the same codes)."""
+    out = []
+    s = hip.Stream(0)
+    for n, k in shapes:
+        per, g = n * k, k // 128
+        layers = max(2, -(-ring_bytes // per))
+        w = torch.empty(layers, n, k, device="cuda", dtype=torch.float8_e4m3fn)
+        wsb = torch.empty(layers, -(-n // 128), g, device="cuda", dtype=torch.float32).uniform_(0.5, 2.0)
+        for i in range(layers):
+            w[i].copy_(torch.randn(n, k, device="cuda", dtype=torch.bfloat16).to(torch.float8_e4m3fn))
+        part = torch.empty(16 * 128 * n * 4, device="cuda", dtype=torch.uint8)
+        ws = {"workspace": part.data_ptr(), "workspace_bytes": part.numel()}
+        sb_row = torch.ones(n, device="cuda", dtype=torch.float32)
+        for m in ms:
+            x = torch.zeros(128, k, device="cuda", dtype=torch.bfloat16)  # rows m .. 127: the padding of the bar
+            x[:m] = torch.randn(m, k, device="cuda", dtype=torch.bfloat16)
+            a = torch.empty(128, k, device="cuda", dtype=torch.uint8)
+            sa = torch.empty(128, g, device="cuda", dtype=torch.float32)
+            sa_row = torch.ones(128, device="cuda", dtype=torch.float32)
+            c = torch.empty(128, n, device="cuda", dtype=torch.bfloat16)
+            torch.cuda.synchronize()
+            hip.quant_fp8_block(s, x.data_ptr(), k, a.data_ptr(), k, sa.data_ptr(), g, 128, k)
+            s.sync()
+
+            def skinny(cfg, splits):
+                for i in range(layers):
+                    args = (s, a.data_ptr(), w.data_ptr() + i * per, c.data_ptr(), m, n, k)
+                    sc = {"scale_a": sa.data_ptr(), "sa_stride": g, "scale_b": wsb[i].data_ptr()}
+                    if cfg is None:
+                        hip.skinny_gemm_fp8_block_nt(*args, **sc, **ws)
+                    else:
+                        hip.skinny_gemm_fp8_block_nt_cfg(*args, cfg, splits, **sc, **ws)
+
+            def pad128():
+                for i in range(layers):
+                    hip.gemm_fp8_block_nt(s, a.data_ptr(), w.data_ptr() + i * per, c.data_ptr(), 128, n, k,
+                                          sa.data_ptr(), g, wsb[i].data_ptr())
+
+            def skinny_fp8_row():
+                for i in range(layers):
+                    hip.skinny_gemm_nt(s, "fp8", a.data_ptr(), w.data_ptr() + i * per, c.data_ptr(), m, n, k,
+                                       scale_a=sa_row.data_ptr(), scale_b=sb_row.data_ptr(), scale_mode=hip.SCALE_ROW,
+                                       **ws)
+
+            cfg0, splits0 = hip.skinny_gemm_fp8_block_pick(m, n, k)
+            cfgs = hip.skinny_gemm_fp8_block_cfgs()
+            variants = {f"cfg{cfg}_{name}": (lambda cfg=cfg: skinny(cfg, splits0))
+                        for cfg, (name, bn, _, _) in cfgs.items() if n % bn == 0}
+            variants.update({f"gsx_s{sp}": (lambda sp=sp: skinny(cfg0, sp))
+                             for sp in {max(1, splits0 // 2), min(16, splits0 * 2)} - {splits0}})
+            variants.update({"gsx": lambda: skinny(None, 0), "skinny_fp8_row": skinny_fp8_row})
+            if n % 128 == 0:
+                variants["pad128"] = pad128
+            row = {"m": m, "n": n, "k": k, "layers": layers, "ring_bytes": layers * per, "picked": cfgs[cfg0][0],
+                   "picked_splits": splits0}
+
+            def timed(fn):
+                s.sync()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ts = torch.cuda.ExternalStream(s.ptr)
+                e0.record(ts)
+                for _ in range(reps):
+                    fn()
+                e1.record(ts)
+                e1.synchronize()
+                return reps * layers * per / (e0.elapsed_time(e1) * 1e-3) / 1e12
+
+            runs = {name: [] for name in variants}
+            for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                for name, fn in variants.items():
+                    t = timed(fn)
+                    if r:
+                        runs[name].append(t)
+            for name, v in runs.items():
+                med = statistics.median(v)
+                row[f"{name}_TBps"] = round(med, 3)
+                row[f"{name}_spread"] = round((max(v) - min(v)) / med, 3)
+            row["spread"] = max(v for key, v in row.items() if key.endswith("_spread"))
+            if "pad128_TBps" in row:
+                row["beats_pad128"] = row["gsx_TBps"] > row["pad128_TBps"] * (1 + row["spread"])
+            row["of_skinny_fp8_row"] = round(row["gsx_TBps"] / row["skinny_fp8_row_TBps"], 3)
+            out.append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+            del x, a, sa, c
+        del w, wsb, part
+    s.destroy()
+    return out
+
+
 ATTN_SHAPES =[(1, 32768), (8, 8192), (64, 2048), (256, 1024)]  # (sequences, tokens each)
 ATTN_HEADS = [(64, 8), (32, 32)]  # (query heads, KV heads): groups of 8, and plain multi-head attention
 ATTN_SPLITS = (1, 2, 4, 8, 16, 32, 64)
@@ -1602,6 +1698,7 @@ if __name__ == "__main__":
     fp8_sizes = [(4096, 4096, 4096), (8192, 8192, 8192), (16384, 16384, 8192)]
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
                 "gemm_fp8_block": gemm_fp8_block, "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "gemm_skinny": gemm_skinny,
+                "gemm_skinny_fp8_block": gemm_skinny_fp8_block,
                 "attn_decode": attn_decode, "attn_multi": attn_multi, "attn_mla": attn_mla,
                 "kv_append": kv_append, "norm_act": norm_act, "attn_prefill": attn_prefill, "sample": sample,
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
