@@ -137,8 +137,10 @@ def lib():
         _moe_route_sig = [vp, vp, ctypes.c_int64, vp, vp, vp, i32, i32, i32]
         # stream, kind, A, a_div, B, C, plan; M, topk, E, N, K; scale_a, scale_b, scale_mode
         _moe_gemm_sig = [vp, i32, vp, i32, vp, vp, vp] + [i32] * 5 + [vp, vp, i32]
+        # stream, A, a_div, B, C, plan; M, topk, E, N, K; scale_a, sa_stride, scale_b
+        _moe_fp8_block_sig = [vp, vp, i32, vp, vp, vp] + [i32] * 5 + [vp, ctypes.c_int64, vp]
         # stream, Y, y_stride, topk_w, out, out_stride; M, topk, H
-        _moe_combine_sig = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i32, i32, i32]
+        _moe_combine_sig =[vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i32, i32, i32]
         # stream, logits, logits_stride, topk_ids, topk_w; M, E, topk
         _pf_route_sig = [vp, vp, ctypes.c_int64, vp, vp, i32, i32, i32]
         # stream, topk_ids, plan; M, topk, E; workspace, workspace_bytes
@@ -254,6 +256,11 @@ def lib():
             "gsx_moe_gemm_cfg_name": ([i32], ctypes.c_char_p),
             "gsx_moe_gemm_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 4, i32),
             "gsx_event_time_moe_gemm": ([*_moe_gemm_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_moe_gemm_fp8_block_nt": (_moe_fp8_block_sig, i32),
+            "gsx_moe_gemm_fp8_block_nt_launch_cfg": ([*_moe_fp8_block_sig, i32], i32),
+            "gsx_moe_gemm_fp8_block_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_moe_gemm_fp8_block_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
+            "gsx_event_time_moe_gemm_fp8_block": ([*_moe_fp8_block_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_moe_combine": (_moe_combine_sig, i32),
             "gsx_event_time_moe_combine": ([*_moe_combine_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_moe_prefill_route": (_pf_route_sig, i32),
@@ -1382,6 +1389,52 @@ def time_moe_gemm(stream: Stream, kind: str, a: int, a_div: int, b: int, c: int,
     ms = ctypes.c_float(0)
     _ck(lib().gsx_event_time_moe_gemm(*_moe_gemm_args(stream, kind, a, a_div, b, c, plan, m, topk, e, n, k, scale_a,
                                                       scale_b, scale_mode), iters, ctypes.byref(ms)), "time_moe_gemm")
+    return ms.value
+
+
+def _moe_fp8_block_args(stream: Stream, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                        n: int, k: int, scale_a: int, sa_stride: int, scale_b: int) -> tuple:
+    return (stream.handle, ctypes.c_void_p(a), a_div, ctypes.c_void_p(b), ctypes.c_void_p(c), ctypes.c_void_p(plan),
+            m, topk, e, n, k, ctypes.c_void_p(scale_a), sa_stride, ctypes.c_void_p(scale_b))
+
+
+def moe_gemm_fp8_block_nt(stream: Stream, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                          n: int, k: int, scale_a: int, sa_stride: int, scale_b: int):
+    """The grouped expert GEMM on block-scaled fp8 operands: :func:`moe_gemm_nt` with ``A`` e4m3 and
+    ``scale_a[rows of A][sa_stride]`` fp32 (what :func:`quant_fp8_block` writes), ``B[e][n][k]`` e4m3 and
+    ``scale_b[e][ceil(n / 128)][k / 128]`` fp32, ``C[p][n]`` bf16.  ``n % 64 == 0``, ``k % 128 == 0``.  Only the
+    experts the plan names are read, weights and scales.  Not synchronised."""
+    _ck(lib().gsx_moe_gemm_fp8_block_nt(*_moe_fp8_block_args(stream, a, a_div, b, c, plan, m, topk, e, n, k, scale_a,
+                                                             sa_stride, scale_b)), "moe_gemm_fp8_block_nt")
+
+
+def moe_gemm_fp8_block_cfgs() -> dict[int, tuple[str, int, int, int]]:
+    """``{index: (name, bn, waves, inflight)}`` of the block-scaled grouped GEMM's configurations, read from the
+    library's table."""
+    out: dict[int, tuple[str, int, int, int]] = {}
+    while (name := lib().gsx_moe_gemm_fp8_block_cfg_name(len(out))) is not None:
+        v = [ctypes.c_int(0) for _ in range(3)]
+        if lib().gsx_moe_gemm_fp8_block_cfg_shape(len(out), *map(ctypes.byref, v)) != 0:
+            raise HipError(f"moe gemm fp8 block cfg {len(out)} has a name and no shape")
+        out[len(out)] = (name.decode(), *(x.value for x in v))
+    return out
+
+
+def moe_gemm_fp8_block_nt_cfg(stream: Stream, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                              n: int, k: int, cfg: int, scale_a: int, sa_stride: int, scale_b: int):
+    """Launch one configuration of the block-scaled grouped GEMM; an unknown config or a shape it cannot take raises
+    HipError."""
+    _ck(lib().gsx_moe_gemm_fp8_block_nt_launch_cfg(
+        *_moe_fp8_block_args(stream, a, a_div, b, c, plan, m, topk, e, n, k, scale_a, sa_stride, scale_b), cfg),
+        f"moe gemm fp8 block cfg {cfg}")
+
+
+def time_moe_gemm_fp8_block(stream: Stream, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                            n: int, k: int, iters: int, scale_a: int, sa_stride: int, scale_b: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_moe_gemm_fp8_block(
+        *_moe_fp8_block_args(stream, a, a_div, b, c, plan, m, topk, e, n, k, scale_a, sa_stride, scale_b), iters,
+        ctypes.byref(ms)), "time_moe_gemm_fp8_block")
     return ms.value
 
 

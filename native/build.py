@@ -20,7 +20,8 @@ Targets (outputs land in ``gpushare_scheduler_extender_amd/_native/``):
                 attention decode over a paged latent cache (attn_mla.hip), RoPE + KV-cache
                 append (kv_append.hip), fused residual add + RMSNorm and SwiGLU (norm_act.hip), causal prefill attention over the same cache (attn_prefill.hip), the token
                 sampler and the embedding gather (sample.hip), the MoE router and combine (moe.hip; the grouped expert
-                GEMM is a form of the decode kernel in gemm_decode.hip), MoE prefill: the many-token router, the tile
+                GEMM is a form of the decode kernel in gemm_decode.hip; its block-scaled fp8 form is
+                moe_fp8_block.hip), MoE prefill: the many-token router, the tile
                 plan, the grouped 128x128 GEMM and the combine (moe_prefill.hip), CU-masked streams.
 * ``tools``   – standalone HIP executables (``gsx-cuprobe``, ``gsx-memprobe``, ``gsx-memtest``, ``gsx-cutest``).
 * ``isolate`` – ``libgsx_isolate.so``, the HSA tools library that enforces a pod's CU partition and HBM share

@@ -53,6 +53,9 @@
 //  * MoE prefill         — a mixture-of-experts layer at prefill row counts: a router over thousands
 //                          of tokens, a tile plan built on the device, and a compute-bound grouped
 //                          128x128 GEMM whose A rows are gathered by expert (moe_prefill.hip);
+//  * block-scaled fp8 MoE decode GEMM — the grouped expert GEMM of MoE decode on the block-scaled operands (1 x 128
+//                          and 128 x 128 fp32 scales per expert): only the experts a plan hits are streamed, rows
+//                          gathered through the plan, every K block scaled as it is folded (moe_fp8_block.hip);
 //  * CU-masked streams   — hipExtStreamCreateWithCUMask.
 //
 // All functions return 0 or a hipError_t value; gsx_last_error() has text.
@@ -185,8 +188,9 @@ int gsx_event_time_gemm_fp8(void* stream, const void* A, const void* B, void* C,
 // longer K is rejected.  Launches on `stream` and returns without synchronising; everything is validated before the
 // first device call.  gsx_gemm_fp8_block_nt dispatches to the 256x256 tile when M and N are multiples of 256 and to
 // the 128x128 tile otherwise.
-// Out of scope: block-scaled operands for the decode and MoE GEMMs, and e8m0 (power-of-two) scales on the
-// hardware-scaled MFMA.  1 <= M <= 128 is gsx_skinny_gemm_fp8_block_nt (below).
+// Out of scope: block-scaled operands for the dense decode GEMM (gsx_decode_gemm_nt) and for MoE prefill, and e8m0
+// (power-of-two) scales on the hardware-scaled MFMA.  1 <= M <= 128 is gsx_skinny_gemm_fp8_block_nt and the grouped
+// expert GEMM of MoE decode gsx_moe_gemm_fp8_block_nt (both below).
 int gsx_gemm_fp8_block_nt(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
                           const float* scale_a, int64_t sa_stride, const float* scale_b);
 // The configurations, a table of their own in gemm_fp8_block.hip: 0 "128x128/4w", 1 "256x128/8w", 2 "256x256/8w".
@@ -801,6 +805,54 @@ int gsx_event_time_moe_gemm(void* stream, int kind, const void* A, int a_div, co
                             const void* scale_b, int scale_mode, int iters, float* ms);
 int gsx_event_time_moe_combine(void* stream, const void* Y, int64_t y_stride, const float* topk_w, void* out,
                                int64_t out_stride, int M, int topk, int H, int iters, float* ms);
+
+// Block-scaled fp8 grouped expert GEMM for MoE decode (moe_fp8_block.hip): gsx_moe_gemm_nt on the operands of
+// gsx_gemm_fp8_block_nt, grouped by expert.  For every pair p of a plan of gsx_moe_route, with e its slot's expert,
+// C[p][0..N) = A[p / a_div][0..K) * B[e][N][K]^T; a_div = topk is the up projection, a_div = 1 the down projection.
+//   A[ceil(P / a_div)][K]                          OCP e4m3, contiguous rows
+//   scale_a[ceil(P / a_div)][sa_stride]            fp32, sa_stride >= K / 128: what gsx_quant_fp8_block writes; exactly
+//                                                  as many rows as A, and nothing of it or of A is read behind them
+//   B[E][N][K]                                     e4m3, the experts' matrices back to back
+//   scale_b[E][ceil(N / 128)][K / 128]             fp32, contiguous; an expert's last block row may cover 64 columns
+//   C[P][N]                                        bf16, contiguous; rows without a pair in the plan are not written
+// One launch of (N / BN, min(E, P)) workgroups, one per (strip of BN columns, slot of the plan), whatever the plan
+// holds: a workgroup whose slot is not active returns at once, so the host never learns n_active, and an inactive
+// expert's weights and scales are never read.  No split of K, no workspace, no atomics.
+// Per element (pair p, column j), with nb = j / 128 and r = p / a_div, over the K-tiles g of 128 k each:
+//   p_g = sum over the 128 k of K-tile g of A[r][k] B[e][j][k]   fp32, one v_mfma_f32_16x16x128_f8f6f4 from a zero accumulator
+//   s_g = fl(scale_a[r][g] * scale_b[e][nb][g])
+//   wave w of the configuration's W folds g = w, w + W, ... in ascending order: acc = fma(p_g, s_g, acc), from 0
+//   the W waves' accumulators are added in the order of the wave index
+//   C = bf16(sum)                                                round to nearest even, once
+// The result depends on the configuration's W and on nothing else: not on M, the routing, the slot or where workgroups
+// run.  Where W = 4, a pair's row has the bits that gsx_skinny_gemm_fp8_block_nt_launch_cfg gives at splits = 1 (any of
+// its configurations) for the same row of A against that expert's matrix and scales.
+// The plan is device memory anyone may have written, and no content of it makes the kernel read outside A, B or the
+// scales or write outside C: a slot >= n_active or >= GSX_MOE_MAX_PAIRS returns, a slot whose expert is outside [0, E)
+// is skipped, slot_count is clamped to [0, 16], an index into rows outside [0, GSX_MOE_MAX_PAIRS) and a pair outside
+// [0, P) are dropped (no load, no store).  The same pair listed twice is a race: the caller's business.
+// Requirements: 1 <= M <= 16; E >= 1; 1 <= topk <= min(8, E); a_div >= 1; K % 128 == 0; N % 64 == 0 (_launch_cfg:
+// N % BN == 0 too, BN being 16, 32 or 64), so that a strip never crosses a 128-column scale block; no pointer NULL; A, B
+// and C 16-B aligned, the scales and the plan 4-B aligned; sa_stride >= K / 128; A's rows and scale_a's, and one row
+// more of each (where a lane without a pair points), fit a 32-bit buffer range; C overlaps none of A, B, the scales and
+// the plan.  Offsets into B, scale_b and C are 64-bit: B may exceed 4 GiB.  Launches on `stream` and returns without
+// synchronising; everything is validated before the first device call.
+// The configurations, a table of the kernel's own: 0 "16/4w-f8", 1 "16/8w-f4", 2 "32/4w-f4", 3 "32/8w-f2",
+// 4 "64/4w-f2": columns of a strip (BN) / waves per workgroup - K-tiles a wave keeps in flight.  _cfg_name returns NULL
+// and _cfg_shape nonzero outside the table.  gsx_moe_gemm_fp8_block_nt picks by N and K / 128 alone (mfb_pick() in
+// moe_fp8_block.hip; profiles/moe_fp8_block/README.md has the measurements).
+int gsx_moe_gemm_fp8_block_nt(void* stream, const void* A, int a_div, const void* B, void* C, const int32_t* plan,
+                              int M, int topk, int E, int N, int K, const float* scale_a, int64_t sa_stride,
+                              const float* scale_b);
+const char* gsx_moe_gemm_fp8_block_cfg_name(int cfg);
+int gsx_moe_gemm_fp8_block_cfg_shape(int cfg, int* bn, int* waves, int* inflight);
+int gsx_moe_gemm_fp8_block_nt_launch_cfg(void* stream, const void* A, int a_div, const void* B, void* C,
+                                         const int32_t* plan, int M, int topk, int E, int N, int K,
+                                         const float* scale_a, int64_t sa_stride, const float* scale_b, int cfg);
+// elapsed milliseconds of `iters` back-to-back gsx_moe_gemm_fp8_block_nt on `stream`, by hip events (for benches)
+int gsx_event_time_moe_gemm_fp8_block(void* stream, const void* A, int a_div, const void* B, void* C,
+                                      const int32_t* plan, int M, int topk, int E, int N, int K, const float* scale_a,
+                                      int64_t sa_stride, const float* scale_b, int iters, float* ms);
 
 // Mixture-of-experts prefill (moe_prefill.hip): the same layer for 1 <= M <= 32768 tokens, 8 <= E <= 1024 experts with
 // E % 8 == 0 and 1 <= topk <= min(8, E); P = M topk pairs, pair p = m topk + j as in decode.  Four entry points that

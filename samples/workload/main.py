@@ -84,6 +84,15 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   closes the layer.  It reports the prefill workload's fields (``tflops`` counts real pairs only), ``experts``,
   ``experts_active`` and ``pad_share``, the share of the grouped GEMM's 128-row tiles that the last step's routing
   left as padding.
+* ``--workload moe`` is the MoE MLP of a decode step alone, where such a model's weight bytes are: ``--batch`` rows
+  (1..16) of hidden size ``--size`` against a ring (``--weights-gib``) of layers of ``--experts`` experts (a multiple of
+  16 up to 1024) of width ``--ffn``, of which a row picks ``--experts-active`` (1..8).  A layer's routing is made once
+  at set-up by the router GEMM and ``gsx_moe_route`` on random rows; a step runs, per layer, the grouped up projection,
+  ``gsx_silu_mul``, the grouped down projection and ``gsx_moe_combine`` through device memory.  ``--dtype bf16`` runs
+  the projections on ``gsx_moe_gemm_nt``; ``--dtype fp8-block`` (``--size`` and ``--ffn`` multiples of 128) block-
+  quantises the experts in torch once, quantises the rows in front of each projection with ``gsx_quant_fp8_block`` and
+  runs them on ``gsx_moe_gemm_fp8_block_nt``.  ``--kernel gsx`` only.  It reports ``experts``, ``experts_active``,
+  ``n_active`` (the experts each layer's plan hits) and ``tbps`` over the bytes of those experts.
 """
 from __future__ import annotations
 
@@ -232,6 +241,13 @@ def moe_refusal(workload: str, experts: int, experts_active: int) -> str | None:
         if not 1 <= experts_active <= MOE_MAX_ACTIVE:
             return f"--experts-active {experts_active}: 1..{MOE_MAX_ACTIVE}"
         return None
+    if workload == "moe":
+        if not 16 <= experts <= MOE_MAX_EXPERTS or experts % 16:
+            return (f"--workload moe --experts {experts}: a multiple of 16 in 16..{MOE_MAX_EXPERTS} "
+                    "(the router is the decode GEMM)")
+        if not 1 <= experts_active <= MOE_MAX_ACTIVE:
+            return f"--experts-active {experts_active}: 1..{MOE_MAX_ACTIVE}"
+        return None
     if experts == 0:
         return None
     if workload == "prefill":
@@ -242,6 +258,28 @@ def moe_refusal(workload: str, experts: int, experts_active: int) -> str | None:
         return f"--experts {experts}: 0, or a multiple of 16 in 16..{MOE_MAX_EXPERTS} (the router is the decode GEMM)"
     if not 1 <= experts_active <= MOE_MAX_ACTIVE:
         return f"--experts-active {experts_active}: 1..{MOE_MAX_ACTIVE}"
+    return None
+
+
+def moe_mlp_expert_bytes(dtype: str, hidden: int, ffn: int) -> int:
+    """Bytes of one expert of ``--workload moe``: its gate / up projection ``[2 ffn][hidden]`` and its down projection
+    ``[hidden][ffn]``, in bf16, or in e4m3 with one fp32 scale per 128 x 128 block."""
+    if dtype == "bf16":
+        return 3 * ffn * hidden * 2
+    return 3 * ffn * hidden + 4 * ((2 * ffn // 128) * (hidden // 128) + -(-hidden // 128) * (ffn // 128))
+
+
+def moe_mlp_refusal(dtype: str, kernel: str, hidden: int, ffn: int) -> str | None:
+    """Why ``--workload moe`` cannot run with these options, or None: known before anything touches the device."""
+    if kernel == "torch":
+        return "--workload moe runs on the library's kernels only (--kernel gsx)"
+    if dtype not in ("bf16", "fp8-block"):
+        return f"--workload moe --dtype {dtype}: bf16 or fp8-block"
+    unit = 128 if dtype == "fp8-block" else 64
+    if hidden < unit or hidden % unit:
+        return f"--workload moe --dtype {dtype} --size {hidden}: the hidden size is a multiple of {unit}"
+    if ffn < unit or ffn % unit:
+        return f"--workload moe --dtype {dtype} --ffn {ffn}: a multiple of {unit}"
     return None
 
 
@@ -352,6 +390,9 @@ class Kernels:
                       L.gsx_moe_gemm_cfg_shape, L.gsx_event_time_moe_route, L.gsx_event_time_moe_gemm,
                       L.gsx_event_time_moe_combine):
                 f.restype = i32
+        if hasattr(L, "gsx_moe_gemm_fp8_block_nt"):  # likewise: an image built before the block-scaled grouped GEMM
+            L.gsx_moe_gemm_fp8_block_nt.argtypes = [vp, vp, i32, vp, vp, vp] + [i32] * 5 + [vp, ctypes.c_int64, vp]
+            L.gsx_moe_gemm_fp8_block_nt.restype = i32
         if hasattr(L, "gsx_moe_prefill_route"):  # likewise: an image built before the MoE prefill kernels
             i64, u64 = ctypes.c_int64, ctypes.c_uint64
             L.gsx_moe_prefill_route.argtypes = [vp, vp, i64, vp, vp, i32, i32, i32]
@@ -629,6 +670,16 @@ class Kernels:
                  "time_moe_gemm")
         return ms.value
 
+    def moe_gemm_fp8_block(self, s, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int, n: int,
+                           k: int, sa: int, sb: int):
+        """:meth:`moe_gemm_nt` on block-scaled e4m3 operands: ``sa[rows of a][k / 128]`` and
+        ``sb[e][ceil(n / 128)][k / 128]`` fp32."""
+        if not hasattr(self.L, "gsx_moe_gemm_fp8_block_nt"):
+            raise RuntimeError(f"{self.path} has no gsx_moe_gemm_fp8_block_nt: rebuild it")
+        self._ck(self.L.gsx_moe_gemm_fp8_block_nt(s, ctypes.c_void_p(a), a_div, ctypes.c_void_p(b), ctypes.c_void_p(c),
+                                                  ctypes.c_void_p(plan), m, topk, e, n, k, ctypes.c_void_p(sa),
+                                                  k // 128, ctypes.c_void_p(sb)), "moe_gemm_fp8_block_nt")
+
     def _moe_combine_args(self, s, y: int, w: int, out: int, m: int, topk: int, h: int) -> tuple:
         if not hasattr(self.L, "gsx_moe_combine"):
             raise RuntimeError(f"{self.path} has no gsx_moe_combine: rebuild it")
@@ -791,6 +842,89 @@ def decode_steps(torch, kl, gs, stream, dev, dtype: str, a, c, layers: int, wide
         (stream or torch.cuda.current_stream()).synchronize()
 
     return step, sync
+
+
+def moe_mlp_steps(torch, kl, gs, dev, dtype: str, batch: int, hidden: int, ffn: int, experts: int, active: int,
+                  layers: int):
+    """``(step, sync, finite)`` of ``--workload moe``: the MoE MLP of a decode step over a ring of ``layers`` layers'
+    experts.  A layer's routing is made once, here: the router GEMM on the random input rows and ``gsx_moe_route``
+    leave its ids, weights and plan in device memory.  A step runs, per layer, the grouped up projection to ``2 ffn``
+    columns, ``gsx_silu_mul`` and the grouped down projection on the layer's plan, and ``gsx_moe_combine``; with
+    ``fp8-block`` the experts are block-quantised in torch once and ``gsx_quant_fp8_block`` quantises the input rows
+    and the ``P`` activation rows in front of the two projections.  Every layer starts from the same input rows, so an
+    endless run stays finite.  ``step.n_active()`` gives the experts each layer's plan hits."""
+    m, e, pairs = batch, experts, batch * active
+    block = dtype == "fp8-block"
+    wdt = torch.float8_e4m3fn if block else torch.bfloat16
+    x = torch.randn(m, hidden, device=dev, dtype=torch.bfloat16)
+    w_up = torch.empty(layers, e, 2 * ffn, hidden, device=dev, dtype=wdt)
+    w_dn = torch.empty(layers, e, hidden, ffn, device=dev, dtype=wdt)
+    gb = hidden // 128, ffn // 128  # K-tiles of the up and of the down projection
+    s_up = torch.empty(layers, e, 2 * ffn // 128, gb[0], device=dev, dtype=torch.float32) if block else None
+    s_dn = torch.empty(layers, e, -(-hidden // 128), gb[1], device=dev, dtype=torch.float32) if block else None
+
+    def fill(w, s, n, k):  # one expert's matrix, ~ N(0, 1 / k); block-quantised as the decode-wide ring is
+        v = torch.randn(n, k, device=dev, dtype=torch.bfloat16).float() * k ** -0.5
+        if not block:
+            w.copy_(v.to(wdt))
+            return
+        nb = -(-n // 128)
+        pad = torch.zeros(nb * 128, k, device=dev)
+        pad[:n] = v
+        blocks = pad.view(nb, 128, k // 128, 128)
+        s.copy_(blocks.abs().amax(dim=(1, 3)).clamp_min(2.0 ** -100) / 448.0)
+        w.copy_((blocks / s[:, None, :, None]).clamp(-448.0, 448.0).view(nb * 128, k)[:n].to(wdt))
+
+    for i in range(layers):
+        for j in range(e):
+            fill(w_up[i, j], s_up[i, j] if block else None, 2 * ffn, hidden)
+            fill(w_dn[i, j], s_dn[i, j] if block else None, hidden, ffn)
+    router = torch.randn(layers, e, hidden, device=dev, dtype=torch.bfloat16)
+    logits = torch.empty(m, e, device=dev, dtype=torch.bfloat16)
+    ids = torch.empty(layers, m, active, device=dev, dtype=torch.int32)
+    tw = torch.empty(layers, m, active, device=dev, dtype=torch.float32)
+    plan = torch.empty(layers, MOE_PLAN_INTS, device=dev, dtype=torch.int32)
+    gu = torch.empty(pairs, 2 * ffn, device=dev, dtype=torch.bfloat16)
+    act = torch.empty(pairs, ffn, device=dev, dtype=torch.bfloat16)
+    y = torch.empty(pairs, hidden, device=dev, dtype=torch.bfloat16)
+    out = torch.empty(m, hidden, device=dev, dtype=torch.bfloat16)
+    if block:
+        qx = torch.empty(m, hidden, device=dev, dtype=wdt)
+        sx = torch.empty(m, gb[0], device=dev, dtype=torch.float32)
+        qact = torch.empty(pairs, ffn, device=dev, dtype=wdt)
+        sact = torch.empty(pairs, gb[1], device=dev, dtype=torch.float32)
+    torch.cuda.synchronize()
+    for i in range(layers):
+        kl.decode_gemm(gs, "bf16", x.data_ptr(), router[i].data_ptr(), logits.data_ptr(), m, e, hidden)
+        kl.moe_route(gs, logits.data_ptr(), ids[i].data_ptr(), tw[i].data_ptr(), plan[i].data_ptr(), m, e, active)
+    kl.sync(gs)
+    up_bytes, dn_bytes = (t[0].numel() * t.element_size() for t in (w_up, w_dn))
+
+    def step():
+        for i in range(layers):
+            pl, up, dn = plan[i].data_ptr(), w_up.data_ptr() + i * up_bytes, w_dn.data_ptr() + i * dn_bytes
+            if block:
+                kl.quant_fp8_block(gs, x.data_ptr(), qx.data_ptr(), sx.data_ptr(), m, hidden)
+                kl.moe_gemm_fp8_block(gs, qx.data_ptr(), active, up, gu.data_ptr(), pl, m, active, e, 2 * ffn, hidden,
+                                      sx.data_ptr(), s_up[i].data_ptr())
+                kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), pairs, ffn)
+                kl.quant_fp8_block(gs, act.data_ptr(), qact.data_ptr(), sact.data_ptr(), pairs, ffn)
+                kl.moe_gemm_fp8_block(gs, qact.data_ptr(), 1, dn, y.data_ptr(), pl, m, active, e, hidden, ffn,
+                                      sact.data_ptr(), s_dn[i].data_ptr())
+            else:
+                kl.moe_gemm_nt(gs, "bf16", x.data_ptr(), active, up, gu.data_ptr(), pl, m, active, e, 2 * ffn, hidden)
+                kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), pairs, ffn)
+                kl.moe_gemm_nt(gs, "bf16", act.data_ptr(), 1, dn, y.data_ptr(), pl, m, active, e, hidden, ffn)
+            kl.moe_combine(gs, y.data_ptr(), tw[i].data_ptr(), out.data_ptr(), m, active, hidden)
+
+    def sync():
+        kl.sync(gs)
+
+    def finite():
+        return bool(torch.isfinite(out.float()).all())
+
+    step.n_active = lambda: [int(v) for v in plan[:, 0].cpu()]
+    return step, sync, finite
 
 
 def new_tokens_refusal(workload: str, kernel: str, new_tokens: int, context: int, heads: int,
@@ -1380,9 +1514,16 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     if why := fp8_block_refusal(workload, dtype, kernel, size):
         raise SystemExit(why)
     if workload not in ("gemm", "decode", "decode-wide", "attn", "server", "layer", "prefill", "prefill-moe",
-                        "generate"):
-        raise SystemExit(f"--workload {workload}: gemm, decode, decode-wide, attn, server, layer, prefill, prefill-moe "
-                         "or generate")
+                        "generate", "moe"):
+        raise SystemExit(f"--workload {workload}: gemm, decode, decode-wide, attn, server, layer, prefill, prefill-moe, "
+                         "generate or moe")
+    moe_mlp = workload == "moe"  # the MoE MLP alone, over a ring of layers' experts
+    if moe_mlp:
+        ffn = default_ffn(size) if ffn is None else ffn
+        if why := moe_mlp_refusal(dtype, kernel, size, ffn):
+            raise SystemExit(why)
+        if not 1 <= batch <= 16:
+            raise SystemExit(f"--batch {batch}: 1..16")
     wide = workload == "decode-wide"  # the decode workload on the skinny GEMM
     decode = workload == "decode" or wide
     prefill = workload in ("prefill", "prefill-moe")  # the MoE form is the same layer with another MLP
@@ -1415,6 +1556,8 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         if page % 16 or not 16 <= page <= 256:
             raise SystemExit(f"--page {page}: a multiple of 16 in 16..256")
         m, n, k = batch, heads, ATTN_D  # nothing of the GEMM's operands is needed: keep them tiny
+    if moe_mlp:
+        m, n, k = batch, 16, 128  # likewise
     if decode:
         if not 1 <= batch <= (128 if wide else 16):
             raise SystemExit(f"--batch {batch}: 1..{128 if wide else 16}")
@@ -1439,7 +1582,13 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         own = None if hip_stream is not None else gs
     layers = 1
     finite = None
-    if prefill:
+    if moe_mlp:
+        weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
+        active = moe_active(experts, experts_active)
+        expert_bytes = moe_mlp_expert_bytes(dtype, size, ffn)
+        layers = ring_layers(weights_bytes, experts * expert_bytes)
+        step, sync, finite = moe_mlp_steps(torch, kl, gs, dev, dtype, batch, size, ffn, experts, active, layers)
+    elif prefill:
         weights_bytes = default_weights_bytes(allocated) if weights_gib is None else int(weights_gib * GIB)
         active = moe_active(experts, experts_active)
         one_layer_bytes = (moe_layer_weight_bytes(heads, kv_heads, ffn, experts) if experts
@@ -1560,6 +1709,8 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     flops = 2.0 * m * n * k * layers  # of one step: decode launches once per matrix of the ring
     if attn:
         flops = flops_attn
+    if moe_mlp:  # a pair meets one expert: 3 ffn x hidden weights, 2 flops each
+        flops = 2.0 * batch * active * 3 * ffn * size * layers
     done = 0
     t0 = last = time.perf_counter()
     last_done = 0
@@ -1585,7 +1736,13 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     if decode:
         out.update({"workload": workload, "batch": m, "layers": layers,
                     "tbps": done * layers * matrix_bytes(dtype, n, k) / el / 1e12})
-    if prefill:
+    if moe_mlp:  # a step reads the experts its layers' plans hit, weights and weight scales
+        n_active = step.n_active()
+        out.update({"workload": workload, "batch": batch, "layers": layers, "ffn": ffn, "experts": experts,
+                    "experts_active": active, "n_active": n_active,
+                    "tbps": done * sum(n_active) * expert_bytes / el / 1e12, "tokens_per_s": done * batch / el,
+                    "activations_finite": finite()})
+    elif prefill:
         step_bytes = layers * (one_layer_bytes + kv_layer_bytes(kv_dtype, batch, context, kv_heads))
         out.update({"workload": workload, "batch": batch, "chunk": chunk, "layers": layers, "weight_layers": w_layers,
                     "kv_layers": kv_layers, "context": context, "heads": heads, "kv_heads": kv_heads,
@@ -1646,13 +1803,14 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
 
 
 def fp8_block_refusal(workload: str, dtype: str, kernel: str, size: int) -> str | None:
-    """Why ``--dtype fp8-block`` cannot run, or None: the block-scaled GEMMs are the large one (``gemm``) and the
-    skinny one (``decode-wide``)."""
+    """Why ``--dtype fp8-block`` cannot run, or None: the block-scaled GEMMs are the large one (``gemm``), the skinny
+    one (``decode-wide``) and the grouped expert GEMM of MoE decode (``moe``)."""
     if dtype != "fp8-block":
         return None
-    if workload not in ("gemm", "decode-wide"):
+    if workload not in ("gemm", "decode-wide", "moe"):
         return (f"--workload {workload} --dtype fp8-block: block-scaled operands are the gemm workload's only among "
-                "the large GEMMs, and decode-wide's among the streaming ones (the decode and MoE GEMMs take none)")
+                "the large GEMMs, and decode-wide's and moe's among the streaming ones (the decode GEMM and the MoE "
+                "GEMMs of the layer and prefill workloads take none)")
     if kernel == "torch":
         return "--dtype fp8-block needs the library's kernels (--kernel gsx)"
     if size < 128 or size % 128:
@@ -1678,6 +1836,10 @@ class _Parser(argparse.ArgumentParser):
         if why := fp8_block_refusal(ns.workload, ns.dtype, getattr(ns, "kernel", "gsx"), ns.size):
             self.error(why)
         if why := moe_refusal(ns.workload, getattr(ns, "experts", 0), getattr(ns, "experts_active", MOE_MAX_ACTIVE)):
+            self.error(why)
+        if ns.workload == "moe" and (why := moe_mlp_refusal(
+                ns.dtype, getattr(ns, "kernel", "gsx"), ns.size,
+                default_ffn(ns.size) if getattr(ns, "ffn", None) is None else ns.ffn)):
             self.error(why)
         if ns.workload in ("prefill", "prefill-moe"):
             # --context means something else here, the length AFTER the chunk, and the chunk's place follows from it:
@@ -1744,7 +1906,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--workload", default="gemm",
                     choices=["gemm", "decode", "decode-wide", "attn", "server", "layer", "prefill", "prefill-moe",
-                             "generate"],
+                             "generate", "moe"],
                     help="gemm: one large square GEMM per step (compute-bound); decode: --batch activation rows "
                          "against a ring of --size x --size weight matrices, one launch each (HBM-bandwidth-bound); "
                          "decode-wide: the same with up to 128 rows, on the skinny GEMM (bf16 and fp8); "
@@ -1756,7 +1918,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "(compute-bound); prefill-moe: that prefill layer with a mixture-of-experts MLP (--experts, a "
                          "multiple of 128; --experts-active) on the grouped 128x128 GEMM; generate: the layer workload closed into generation: the embedding lookup of "
                          "the last step's tokens, the layers, a final RMSNorm, the LM head (--vocab columns) and the "
-                         "sampler, token to token through device memory")
+                         "sampler, token to token through device memory; moe: the MoE MLP of a decode step over a ring "
+                         "of layers' experts (--size is the hidden size, --ffn, --experts, --experts-active; --dtype "
+                         "bf16 or fp8-block, --kernel gsx only)")
     ap.add_argument("--batch", type=int, default=8, metavar="N",
                     help="--workload decode, server, layer and generate: the activation rows (M), 1..16; --workload "
                          "decode-wide: the rows, 1..128; --workload attn and "

@@ -1568,6 +1568,136 @@ def moe(shapes=MOE_SHAPES, ms=(1, 8, 16), kinds=("bf16", "fp8", "mxfp4"), ring_b
     return out
 
 
+def moe_fp8_block(shapes=MOE_SHAPES, ms=(1, 8, 16), ring_bytes=(2 << 30) + 1, reps=3, rounds=3):
+    """The block-scaled fp8 grouped expert GEMM by the protocol of :func:`moe`: rings of more than 2 GiB of e4m3 experts
+    for both projections, the routing of ``moe_route`` on random logits, the variants interleaved in one process, the
+    median of ``rounds`` repeats after a warm-up and their spread.  TB/s is over the ACTIVE experts' e4m3 bytes for
+    every variant, whatever it reads: every configuration, the dispatching entry point (``gsx``), and three yardsticks:
+    ``fp8_row``, ``gsx_moe_gemm_nt`` with per-row scales on the same bytes (the same traffic without the fold);
+    ``bf16``, ``gsx_moe_gemm_nt`` on a bf16 ring of the same shapes (twice the bytes: the library's only route to such
+    experts before); ``per_expert``, one ``gsx_skinny_gemm_fp8_block_nt`` per hit expert on rows gathered beforehand,
+    the hit set known to the host in advance, neither of which is timed."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    f8 = torch.float8_e4m3fn
+    for hidden, ffn, e, topk in shapes:
+        if hidden % 128 or ffn % 128:
+            continue
+        gen = torch.Generator(device="cuda").manual_seed(hidden + e)
+        rw = torch.randn(e, hidden, device="cuda", generator=gen) / math.sqrt(hidden)
+        ring = {}
+        for name, (n, k) in {"up": (2 * ffn, hidden), "down": (hidden, ffn)}.items():
+            layers, nb, g = max(2, -(-ring_bytes // (e * n * k))), -(-n // 128), k // 128
+            w = torch.empty(layers, e * n, k, device="cuda", dtype=f8)
+            wb = torch.empty(layers, e * n, k, device="cuda", dtype=torch.bfloat16)
+            for i in range(layers):
+                for x0 in range(e):  # an expert at a time
+                    t = torch.randn(n, k, device="cuda", dtype=torch.bfloat16)
+                    w[i, x0 * n:(x0 + 1) * n].copy_(t.to(f8))
+                    wb[i, x0 * n:(x0 + 1) * n].copy_(t)
+            sb = torch.rand(layers, e, nb, g, device="cuda") + 0.5
+            sbr = torch.rand(layers, e * n, device="cuda") + 0.5
+            ring[name] = (n, k, layers, w, wb, sb, sbr)
+        for m in ms:
+            pairs = m * topk
+            logits = (torch.randn(m, hidden, device="cuda", generator=gen) @ rw.t()).bfloat16().contiguous()
+            ids = torch.empty(pairs, device="cuda", dtype=torch.int32)
+            tw = torch.empty(pairs, device="cuda", dtype=torch.float32)
+            plan = torch.empty(hip.MOE_PLAN_INTS, device="cuda", dtype=torch.int32)
+            torch.cuda.synchronize()
+            hip.moe_route(s, logits.data_ptr(), e, ids.data_ptr(), tw.data_ptr(), plan.data_ptr(), m, e, topk)
+            s.sync()
+            ph = plan.cpu().numpy()
+            n_active = int(ph[0])
+            row = {"hidden": hidden, "ffn": ffn, "experts": e, "topk": topk, "m": m, "n_active": n_active}
+            for name, (n, k, layers, w, wb, sb, sbr) in ring.items():
+                a_div, g = (topk if name == "up" else 1), k // 128
+                rows = -(-pairs // a_div)
+                x = torch.randn(rows, k, device="cuda", dtype=torch.bfloat16)
+                a, sa = torch.empty(rows, k, device="cuda", dtype=f8), torch.empty(rows, g, device="cuda")
+                sar = torch.rand(rows, device="cuda") + 0.5
+                c = torch.empty(pairs, n, device="cuda", dtype=torch.bfloat16)
+                torch.cuda.synchronize()
+                hip.quant_fp8_block(s, x.data_ptr(), k, a.data_ptr(), k, sa.data_ptr(), g, rows, k)
+                s.sync()
+                slots = []
+                for sl in range(n_active):  # the per-expert loop's operands, gathered beforehand
+                    x0, b0, cnt = int(ph[4 + sl]), int(ph[4 + 128 + sl]), int(ph[4 + 256 + sl])
+                    src = torch.from_numpy(ph[4 + 384 + b0:4 + 384 + b0 + cnt] // a_div).cuda().long()
+                    slots.append((x0, cnt, a[src].contiguous(), sa[src].contiguous(),
+                                  torch.empty(cnt, n, device="cuda", dtype=torch.bfloat16)))
+                part = torch.empty(max(16, max(hip.skinny_gemm_fp8_block_workspace_bytes(cnt, n, k)
+                                               for _, cnt, *_ in slots)), device="cuda", dtype=torch.uint8)
+                torch.cuda.synchronize()
+                wbytes, sbytes = e * n * k, sb[0].numel() * 4
+
+                def grouped(cfg):
+                    for i in range(layers):
+                        args = (s, a.data_ptr(), a_div, w.data_ptr() + i * wbytes, c.data_ptr(), plan.data_ptr(), m,
+                                topk, e, n, k)
+                        tail = (sa.data_ptr(), g, sb.data_ptr() + i * sbytes)
+                        if cfg is None:
+                            hip.moe_gemm_fp8_block_nt(*args, *tail)
+                        else:
+                            hip.moe_gemm_fp8_block_nt_cfg(*args, cfg, *tail)
+
+                def fp8_row():
+                    for i in range(layers):
+                        hip.moe_gemm_nt(s, "fp8", a.data_ptr(), a_div, w.data_ptr() + i * wbytes, c.data_ptr(),
+                                        plan.data_ptr(), m, topk, e, n, k, sar.data_ptr(),
+                                        sbr.data_ptr() + i * e * n * 4, hip.SCALE_ROW)
+
+                def bf16():
+                    for i in range(layers):
+                        hip.moe_gemm_nt(s, "bf16", x.data_ptr(), a_div, wb.data_ptr() + i * 2 * wbytes, c.data_ptr(),
+                                        plan.data_ptr(), m, topk, e, n, k)
+
+                def per_expert():
+                    for i in range(layers):
+                        for x0, cnt, ga, gsa, gc_ in slots:
+                            hip.skinny_gemm_fp8_block_nt(s, ga.data_ptr(), w.data_ptr() + i * wbytes + x0 * n * k,
+                                                         gc_.data_ptr(), cnt, n, k, gsa.data_ptr(), g,
+                                                         sb.data_ptr() + i * sbytes + x0 * (sbytes // e),
+                                                         part.data_ptr(), part.numel())
+
+                variants = {f"cfg{cfg}_{cn}": (lambda cfg=cfg: grouped(cfg))
+                            for cfg, (cn, *_) in hip.moe_gemm_fp8_block_cfgs().items()}
+                variants.update({"gsx": lambda: grouped(None), "fp8_row": fp8_row, "bf16": bf16,
+                                 "per_expert": per_expert})
+                moved = layers * n_active * n * k
+
+                def timed(fn):
+                    torch.cuda.synchronize()
+                    with torch.cuda.stream(ts):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(ts)
+                        for _ in range(reps):
+                            fn()
+                        e1.record(ts)
+                    e1.synchronize()
+                    return reps * moved / (e0.elapsed_time(e1) * 1e-3) / 1e12
+
+                runs = {v: [] for v in variants}
+                for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                    for v, fn in variants.items():
+                        t = timed(fn)
+                        if r:
+                            runs[v].append(t)
+                row[f"{name}_layers"], row[f"{name}_active_bytes"] = layers, moved
+                for v, ts_ in runs.items():
+                    med = statistics.median(ts_)
+                    row[f"{name}_{v}_TBps"] = round(med, 3)
+                    row[f"{name}_{v}_spread"] = round((max(ts_) - min(ts_)) / med, 3)
+                del slots, a, sa, c, x
+            out.append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+        del ring
+        torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 def moe_prefill(shapes=((2048, 768, 128, 8), (4096, 14336, 8, 2)), ms=(1024, 8192), rounds=3, window_ms=30.0):
     """The MoE prefill kernels.  Routing comes from random router weights and inputs through ``moe_prefill_route`` and
     ``moe_prefill_plan``.  Per shape, ``m`` and projection the grouped 128x128 GEMM is timed against the dense
@@ -1704,7 +1834,7 @@ if __name__ == "__main__":
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
                 "moe": moe, "moe_128": lambda: moe(shapes=MOE_SHAPES[:1]),  # the 128-expert shape alone
-                "moe_prefill": moe_prefill,
+                "moe_prefill": moe_prefill, "moe_fp8_block": moe_fp8_block,
                 "hbm": hbm}
     only = sys.argv[2].split(",") if len(sys.argv) > 2 else list(sections)  # [out.json [section,section..]]
     res = {name: sections[name]() for name in only}
