@@ -274,6 +274,12 @@ def lib():
             "gsx_moe_prefill_gemm_cfg_name": ([i32], ctypes.c_char_p),
             "gsx_moe_prefill_gemm_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
             "gsx_event_time_moe_prefill_gemm": ([*_pf_gemm_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_moe_prefill_gemm_fp8_block_nt": (_moe_fp8_block_sig, i32),
+            "gsx_moe_prefill_gemm_fp8_block_nt_launch_cfg": ([*_moe_fp8_block_sig, i32], i32),
+            "gsx_moe_prefill_gemm_fp8_block_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_moe_prefill_gemm_fp8_block_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 3, i32),
+            "gsx_event_time_moe_prefill_gemm_fp8_block": ([*_moe_fp8_block_sig, i32, ctypes.POINTER(ctypes.c_float)],
+                                                          i32),
             "gsx_moe_prefill_combine": (_moe_combine_sig, i32),
             "gsx_event_time_moe_prefill_combine": ([*_moe_combine_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_memtest_write": ([vp, vp, u64, u64, i32, ctypes.c_uint32, i32], i32),
@@ -1565,6 +1571,48 @@ def time_moe_prefill_gemm(stream: Stream, a: int, a_div: int, b: int, c: int, pl
     ms = ctypes.c_float(0)
     _ck(lib().gsx_event_time_moe_prefill_gemm(*_moe_prefill_gemm_args(stream, a, a_div, b, c, plan, m, topk, e, n, k),
                                               iters, ctypes.byref(ms)), "time_moe_prefill_gemm")
+    return ms.value
+
+
+def moe_prefill_gemm_fp8_block_nt(stream: Stream, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int,
+                                  e: int, n: int, k: int, scale_a: int, sa_stride: int, scale_b: int):
+    """The grouped prefill GEMM on block-scaled fp8 operands, over a plan of :func:`moe_prefill_plan`:
+    :func:`moe_prefill_gemm_nt` with ``A`` e4m3 and ``scale_a[rows of A][sa_stride]`` fp32 (what :func:`quant_fp8_block`
+    writes), ``B[e][n][k]`` e4m3 and ``scale_b[e][n / 128][k / 128]`` fp32, ``C[p][n]`` bf16.  ``n % 128 == 0``,
+    ``k % 128 == 0``.  A pair's row has the bits of :func:`gemm_fp8_block_nt_cfg` on its row of ``A`` against its
+    expert.  Not synchronised."""
+    _ck(lib().gsx_moe_prefill_gemm_fp8_block_nt(*_moe_fp8_block_args(stream, a, a_div, b, c, plan, m, topk, e, n, k,
+                                                                     scale_a, sa_stride, scale_b)),
+        "moe_prefill_gemm_fp8_block_nt")
+
+
+def moe_prefill_gemm_fp8_block_cfgs() -> dict[int, tuple[str, int, int, int]]:
+    """``{index: (name, bm, bn, waves)}`` of the block-scaled grouped prefill GEMM's configurations, read from the
+    library."""
+    out: dict[int, tuple[str, int, int, int]] = {}
+    while (name := lib().gsx_moe_prefill_gemm_fp8_block_cfg_name(len(out))) is not None:
+        v = [ctypes.c_int(0) for _ in range(3)]
+        if lib().gsx_moe_prefill_gemm_fp8_block_cfg_shape(len(out), *map(ctypes.byref, v)) != 0:
+            raise HipError(f"moe prefill gemm fp8 block cfg {len(out)} has a name and no shape")
+        out[len(out)] = (name.decode(), *(x.value for x in v))
+    return out
+
+
+def moe_prefill_gemm_fp8_block_nt_cfg(stream: Stream, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int,
+                                      e: int, n: int, k: int, cfg: int, scale_a: int, sa_stride: int, scale_b: int):
+    """Launch one configuration of the block-scaled grouped prefill GEMM; an unknown config raises HipError."""
+    _ck(lib().gsx_moe_prefill_gemm_fp8_block_nt_launch_cfg(
+        *_moe_fp8_block_args(stream, a, a_div, b, c, plan, m, topk, e, n, k, scale_a, sa_stride, scale_b), cfg),
+        f"moe prefill gemm fp8 block cfg {cfg}")
+
+
+def time_moe_prefill_gemm_fp8_block(stream: Stream, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int,
+                                    e: int, n: int, k: int, iters: int, scale_a: int, sa_stride: int,
+                                    scale_b: int) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_moe_prefill_gemm_fp8_block(
+        *_moe_fp8_block_args(stream, a, a_div, b, c, plan, m, topk, e, n, k, scale_a, sa_stride, scale_b), iters,
+        ctypes.byref(ms)), "time_moe_prefill_gemm_fp8_block")
     return ms.value
 
 

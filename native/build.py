@@ -22,7 +22,8 @@ Targets (outputs land in ``gpushare_scheduler_extender_amd/_native/``):
                 sampler and the embedding gather (sample.hip), the MoE router and combine (moe.hip; the grouped expert
                 GEMM is a form of the decode kernel in gemm_decode.hip; its block-scaled fp8 form is
                 moe_fp8_block.hip), MoE prefill: the many-token router, the tile
-                plan, the grouped 128x128 GEMM and the combine (moe_prefill.hip), CU-masked streams.
+                plan, the grouped 128x128 GEMM and the combine (moe_prefill.hip) and that GEMM on block-scaled fp8
+                operands (moe_prefill_fp8_block.hip), CU-masked streams.
 * ``tools``   – standalone HIP executables (``gsx-cuprobe``, ``gsx-memprobe``, ``gsx-memtest``, ``gsx-cutest``).
 * ``isolate`` – ``libgsx_isolate.so``, the HSA tools library that enforces a pod's CU partition and HBM share
                 inside every HIP/HSA process of the pod, plus its host-only test driver (fake HSA runtime).

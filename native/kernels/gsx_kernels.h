@@ -56,6 +56,9 @@
 //  * block-scaled fp8 MoE decode GEMM — the grouped expert GEMM of MoE decode on the block-scaled operands (1 x 128
 //                          and 128 x 128 fp32 scales per expert): only the experts a plan hits are streamed, rows
 //                          gathered through the plan, every K block scaled as it is folded (moe_fp8_block.hip);
+//  * block-scaled fp8 MoE prefill GEMM — the grouped 128x128 GEMM of MoE prefill on the same operands: rows of A and
+//                          rows of scale_a gathered through the tile plan, scale_b through the expert's block
+//                          row (moe_prefill_fp8_block.hip);
 //  * CU-masked streams   — hipExtStreamCreateWithCUMask.
 //
 // All functions return 0 or a hipError_t value; gsx_last_error() has text.
@@ -188,9 +191,9 @@ int gsx_event_time_gemm_fp8(void* stream, const void* A, const void* B, void* C,
 // longer K is rejected.  Launches on `stream` and returns without synchronising; everything is validated before the
 // first device call.  gsx_gemm_fp8_block_nt dispatches to the 256x256 tile when M and N are multiples of 256 and to
 // the 128x128 tile otherwise.
-// Out of scope: block-scaled operands for the dense decode GEMM (gsx_decode_gemm_nt) and for MoE prefill, and e8m0
-// (power-of-two) scales on the hardware-scaled MFMA.  1 <= M <= 128 is gsx_skinny_gemm_fp8_block_nt and the grouped
-// expert GEMM of MoE decode gsx_moe_gemm_fp8_block_nt (both below).
+// Out of scope: block-scaled operands for the dense decode GEMM (gsx_decode_gemm_nt), and e8m0 (power-of-two) scales on
+// the hardware-scaled MFMA.  1 <= M <= 128 is gsx_skinny_gemm_fp8_block_nt, the grouped expert GEMM of MoE decode
+// gsx_moe_gemm_fp8_block_nt and that of MoE prefill gsx_moe_prefill_gemm_fp8_block_nt (all below).
 int gsx_gemm_fp8_block_nt(void* stream, const void* A, const void* B, void* C, int M, int N, int K,
                           const float* scale_a, int64_t sa_stride, const float* scale_b);
 // The configurations, a table of their own in gemm_fp8_block.hip: 0 "128x128/4w", 1 "256x128/8w", 2 "256x256/8w".
@@ -856,9 +859,10 @@ int gsx_event_time_moe_gemm_fp8_block(void* stream, const void* A, int a_div, co
 
 // Mixture-of-experts prefill (moe_prefill.hip): the same layer for 1 <= M <= 32768 tokens, 8 <= E <= 1024 experts with
 // E % 8 == 0 and 1 <= topk <= min(8, E); P = M topk pairs, pair p = m topk + j as in decode.  Four entry points that
-// hand ids, weights and a tile plan to each other through device memory; none synchronises.  bf16 operands only: fp8
-// and mxfp4 experts are out of scope here, as they are for the dense prefill workload.  The decode entry points above,
-// their limits and their refusals are unchanged.
+// hand ids, weights and a tile plan to each other through device memory; none synchronises.  These take bf16 operands;
+// block-scaled fp8 experts run on gsx_moe_prefill_gemm_fp8_block_nt (below) over the same plan, and per-row fp8 and
+// mxfp4 experts are out of scope, as they are for the dense prefill workload.  The decode entry points above, their
+// limits and their refusals are unchanged.
 //
 // gsx_moe_prefill_route: logits[M][logits_stride] bf16 (the large GEMM's output against the router matrix),
 // topk_ids[M][topk] int32, topk_w[M][topk] fp32.  Per row exactly gsx_moe_route's rules: selection by the sampler's key
@@ -929,6 +933,55 @@ int gsx_event_time_moe_prefill_gemm(void* stream, const void* A, int a_div, cons
                                     const int32_t* plan, int M, int topk, int E, int N, int K, int iters, float* ms);
 int gsx_event_time_moe_prefill_combine(void* stream, const void* Y, int64_t y_stride, const float* topk_w, void* out,
                                        int64_t out_stride, int M, int topk, int H, int iters, float* ms);
+
+// Block-scaled fp8 grouped GEMM for MoE prefill (moe_prefill_fp8_block.hip): gsx_moe_prefill_gemm_nt on the operands of
+// gsx_gemm_fp8_block_nt, over an unchanged plan of gsx_moe_prefill_plan.  For every pair p of the plan, with e its tile's
+// expert, C[p][0..N) = A[p / a_div][0..K) * B[e][N][K]^T; a_div = topk is the up projection, a_div = 1 the down
+// projection.  With P = M topk:
+//   A[ceil(P / a_div)][K]                    OCP e4m3, contiguous rows
+//   scale_a[ceil(P / a_div)][sa_stride]      fp32, sa_stride >= K / 128: what gsx_quant_fp8_block writes; exactly as many
+//                                            rows as A, and of a row nothing behind its K / 128 entries is read
+//   B[E][N][K]                               e4m3, the experts' matrices back to back
+//   scale_b[E][N / 128][K / 128]             fp32, contiguous
+//   C[P][N]                                  bf16, contiguous
+// Per element (pair p, column j), with r = p / a_div and nb = j / 128, over the K-tiles g = 0 .. K / 128 - 1 in
+// ascending order, the numerics of gsx_gemm_fp8_block_nt:
+//   p_g = sum over the 128 k of K-tile g of A[r][k] B[e][j][k]   fp32, one v_mfma_f32_16x16x128_f8f6f4 from a zero accumulator
+//   s_g = fl(scale_a[r][g] * scale_b[e][nb][g])
+//   acc = fma(p_g, s_g, acc)                                     one rounding; acc starts at 0
+//   C   = bf16(acc)                                              round to nearest even, once
+// No split of K, no atomics, no workspace: the result does not depend on the routing, the tile a pair landed in or where
+// workgroups run, and a pair's row has the bits that gsx_gemm_fp8_block_nt_launch_cfg gives, in any of its
+// configurations, for the same row of A and of scale_a against that expert's matrix and scales.  A pair that no tile
+// lists keeps what C held.
+// One configuration, 0 "128x128/4w-gather": a 128x128 block tile (a plan tile is 128 pairs of one expert), 4 waves as
+// 2x2, two LDS stages filled by 16-B global_load_lds; the tile's rows of A and its rows of scale_a are gathered through
+// the plan (64-bit addresses made once per workgroup: A may exceed 2 GiB), scale_b is read through the expert's block
+// row, and every output row is stored to its pair's row of C.  Offsets into A, B, scale_a, scale_b and C are 64-bit.
+// The grid is (N / 128) * T_max workgroups, fixed by the host; nothing of the plan is read on the host.  _cfg_name
+// returns NULL and _cfg_shape nonzero outside the table.
+// The plan is device memory anyone may have written, and no content of it makes the kernel read outside A, B or the
+// scales or write outside C: n_tiles is clamped to T_max, a tile whose expert is outside [0, E) is skipped, a row
+// outside [0, P) is padding (it reads row 0 of A and of scale_a and stores nothing), and a workgroup whose tile is unused
+// returns before any barrier.  The same pair listed twice is a race: the caller's business.
+// Requirements: the sizes of MoE prefill; a_div >= 1; N % 128 == 0, K % 128 == 0; 127 K + 112 < 2^31 (a lane's offset
+// inside a tile of B is 32-bit) and (N / 128) T_max < 2^31; sa_stride >= K / 128; no pointer NULL; A, B and C 16-B
+// aligned, the scales and the plan 4-B aligned; C overlaps none of A, B, the scales and the plan.  Launches on `stream`
+// and returns without synchronising; everything is validated before the first device call.
+int gsx_moe_prefill_gemm_fp8_block_nt(void* stream, const void* A, int a_div, const void* B, void* C,
+                                      const int32_t* plan, int M, int topk, int E, int N, int K, const float* scale_a,
+                                      int64_t sa_stride, const float* scale_b);
+const char* gsx_moe_prefill_gemm_fp8_block_cfg_name(int cfg);
+int gsx_moe_prefill_gemm_fp8_block_cfg_shape(int cfg, int* bm, int* bn, int* waves);
+int gsx_moe_prefill_gemm_fp8_block_nt_launch_cfg(void* stream, const void* A, int a_div, const void* B, void* C,
+                                                 const int32_t* plan, int M, int topk, int E, int N, int K,
+                                                 const float* scale_a, int64_t sa_stride, const float* scale_b,
+                                                 int cfg);
+// elapsed milliseconds of `iters` back-to-back gsx_moe_prefill_gemm_fp8_block_nt on `stream`, by hip events (for benches)
+int gsx_event_time_moe_prefill_gemm_fp8_block(void* stream, const void* A, int a_div, const void* B, void* C,
+                                              const int32_t* plan, int M, int topk, int E, int N, int K,
+                                              const float* scale_a, int64_t sa_stride, const float* scale_b, int iters,
+                                              float* ms);
 
 // HBM pre-flight memory test (memtest.hip).  The expected content of 16-byte word W = origin/16 + word index is
 // generated from (pattern, seed, invert, W) and never stored; `origin` is the byte offset of `base` in the whole

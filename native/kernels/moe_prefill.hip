@@ -2,7 +2,8 @@
 // at prefill row counts (1 <= M <= 32768 tokens, P = M topk pairs).  The decode forms (moe.hip, gemm_decode.hip) stop at
 // 16 rows and stream weights past one MFMA fragment; here the grouped GEMM is compute-bound and an expert owns whole
 // 128-row tiles.  Ids, weights, plan and scratch stay on the device: the chain needs no host synchronisation.  C ABI
-// and numeric contract in gsx_kernels.h.  bf16 only: fp8 and mxfp4 operands are out of scope, as in the dense prefill.
+// and numeric contract in gsx_kernels.h.  bf16 only here; the grouped GEMM on block-scaled fp8 operands is
+// moe_prefill_fp8_block.hip, over the same plan.
 //
 // pf_route_kernel: 4 waves per workgroup, a wave owns a token.  moe_route_kernel's selection and weights, operation by
 //   operation: a lane holds the E / 64 logits l, l + 64, .. of the row as (key << 10 | 1023 - index) + 1, topk rounds of
@@ -31,15 +32,12 @@
 #include "gemm_tile.h"
 #include "gsx_internal.h"
 #include "gsx_kernels.h"
+#include "moe_prefill_plan.h"
 
 #pragma clang fp contract(off)
 
 namespace gsxgemm {
 
-constexpr int PF_MAX_M = 32768;
-constexpr int PF_MAX_E = 1024;
-constexpr int PF_MAX_TOPK = 8;
-constexpr int PF_BM = 128, PF_BN = 128;  // the grouped GEMM's block tile; BM is the plan's padding unit
 constexpr int PF_ROUTE_WAVES = 4;
 constexpr int PF_PER_LANE = PF_MAX_E / 64;
 constexpr int PF_BLOCK = 1024;  // pairs per block of the plan's passes
@@ -351,40 +349,8 @@ __global__ __launch_bounds__(PF_COMBINE_THREADS) void pf_combine_kernel(const ui
 // Host side
 // ---------------------------------------------------------------------------
 
-struct PfSpan {  // [p, p + bytes)
-  const void* p;
-  uint64_t bytes;
-};
+// PfSpan, pf_overlap, pf_bits, pf_refuse, pf_sizes, pf_tmax and pf_plan_ints: moe_prefill_plan.h
 
-static bool pf_overlap(const PfSpan& a, const PfSpan& b) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
-  return x < y + b.bytes && y < x + a.bytes;
-}
-
-static uintptr_t pf_bits(const void* p) { return reinterpret_cast<uintptr_t>(p); }
-
-static int pf_refuse(const char* who, const char* rule) {
-  char msg[240];
-  std::snprintf(msg, sizeof(msg), "%s: %s", who, rule);
-  return fail_arg(msg);
-}
-
-// the sizes every entry point but the combine shares
-static int pf_sizes(const char* who, int M, int topk, int E) {
-  if (M < 1 || M > PF_MAX_M) return pf_refuse(who, "need 1 <= M <= 32768");
-  if (E < 8 || E > PF_MAX_E || E % 8) return pf_refuse(who, "need 8 <= E <= 1024 and E % 8 == 0");
-  if (topk < 1 || topk > PF_MAX_TOPK || topk > E) return pf_refuse(who, "need 1 <= topk <= min(8, E)");
-  return 0;
-}
-
-static int64_t pf_tmax(int M, int topk, int E) {
-  const int64_t P = static_cast<int64_t>(M) * topk;
-  return (P + (E < P ? E : P) * (PF_BM - 1)) / PF_BM;
-}
-static uint64_t pf_plan_ints(int M, int topk, int E) {
-  const uint64_t t = static_cast<uint64_t>(pf_tmax(M, topk, E));
-  return 4 + t + PF_BM * t;
-}
 static int pf_blocks(int M, int topk) { return (M * topk + PF_BLOCK - 1) / PF_BLOCK; }
 static uint64_t pf_ws_bytes(int M, int topk, int E) { return static_cast<uint64_t>(pf_blocks(M, topk)) * E * 4; }
 

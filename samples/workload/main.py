@@ -83,7 +83,10 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   projections through the grouped 128x128 GEMM with SwiGLU on the pairs between them, and ``gsx_moe_prefill_combine``
   closes the layer.  It reports the prefill workload's fields (``tflops`` counts real pairs only), ``experts``,
   ``experts_active`` and ``pad_share``, the share of the grouped GEMM's 128-row tiles that the last step's routing
-  left as padding.
+  left as padding.  ``--dtype fp8-block`` (``--kernel gsx``, ``--size`` and ``--ffn`` multiples of 128) block-quantises
+  the experts in torch once, quantises the chunk's rows in front of the up projection and the SwiGLU output in front of
+  the down projection with ``gsx_quant_fp8_block`` and runs both on ``gsx_moe_prefill_gemm_fp8_block_nt``; attention,
+  the router, routing, plan and combine stay bf16.
 * ``--workload moe`` is the MoE MLP of a decode step alone, where such a model's weight bytes are: ``--batch`` rows
   (1..16) of hidden size ``--size`` against a ring (``--weights-gib``) of layers of ``--experts`` experts (a multiple of
   16 up to 1024) of width ``--ffn``, of which a row picks ``--experts-active`` (1..8).  A layer's routing is made once
@@ -404,6 +407,10 @@ class Kernels:
             for f in (L.gsx_moe_prefill_route, L.gsx_moe_prefill_plan_ints, L.gsx_moe_prefill_workspace_bytes,
                       L.gsx_moe_prefill_plan, L.gsx_moe_prefill_gemm_nt, L.gsx_moe_prefill_combine):
                 f.restype = i32
+        if hasattr(L, "gsx_moe_prefill_gemm_fp8_block_nt"):  # likewise: an image built before its block-scaled form
+            L.gsx_moe_prefill_gemm_fp8_block_nt.argtypes = ([vp, vp, i32, vp, vp, vp] + [i32] * 5
+                                                            + [vp, ctypes.c_int64, vp])
+            L.gsx_moe_prefill_gemm_fp8_block_nt.restype = i32
         L.gsx_last_error.argtypes, L.gsx_last_error.restype = [], ctypes.c_char_p
         self.L, self.path = L, path
 
@@ -720,6 +727,16 @@ class Kernels:
         """``c[p][n] = a[p // a_div][k] * b[expert of p][n][k]^T`` for every pair ``p`` of the tile plan (bf16)."""
         self._ck(self.L.gsx_moe_prefill_gemm_nt(s, ctypes.c_void_p(a), a_div, ctypes.c_void_p(b), ctypes.c_void_p(c),
                                                 ctypes.c_void_p(plan), m, topk, e, n, k), "moe_prefill_gemm_nt")
+
+    def moe_prefill_gemm_fp8_block(self, s, a: int, a_div: int, b: int, c: int, plan: int, m: int, topk: int, e: int,
+                                   n: int, k: int, sa: int, sb: int):
+        """:meth:`moe_prefill_gemm_nt` on block-scaled e4m3 operands: ``sa[rows of a][k / 128]`` and
+        ``sb[e][n / 128][k / 128]`` fp32."""
+        if not hasattr(self.L, "gsx_moe_prefill_gemm_fp8_block_nt"):
+            raise RuntimeError(f"{self.path} has no gsx_moe_prefill_gemm_fp8_block_nt: rebuild it")
+        self._ck(self.L.gsx_moe_prefill_gemm_fp8_block_nt(
+            s, ctypes.c_void_p(a), a_div, ctypes.c_void_p(b), ctypes.c_void_p(c), ctypes.c_void_p(plan), m, topk, e, n,
+            k, ctypes.c_void_p(sa), k // 128, ctypes.c_void_p(sb)), "moe_prefill_gemm_fp8_block_nt")
 
     def moe_prefill_combine(self, s, y: int, w: int, out: int, m: int, topk: int, h: int):
         self._ck(self.L.gsx_moe_prefill_combine(s, ctypes.c_void_p(y), h, ctypes.c_void_p(w), ctypes.c_void_p(out), h,
@@ -1340,7 +1357,8 @@ def generate_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, 
 
 
 def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, context: int, heads: int, kv_heads: int,
-                  page: int, ffn: int, w_layers: int, kv_layers: int, *, experts: int = 0, active: int = 0):
+                  page: int, ffn: int, w_layers: int, kv_layers: int, *, experts: int = 0, active: int = 0,
+                  block: bool = False):
     """``(step, sync, finite)`` of the prefill workload: :func:`layer_steps` on ``batch * chunk`` rows.  The
     projections go through the large GEMM, the append writes ``chunk`` tokens per sequence at positions
     ``[context - chunk, context)`` and the causal attention reads the lengths the append read: one constant buffer.
@@ -1348,24 +1366,35 @@ def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, con
     With ``experts`` > 0 (``--workload prefill-moe``) the MLP is a mixture of experts of width ``ffn``, of which a
     token picks ``active``: the router (the large GEMM with N = ``experts``), ``moe_prefill_route``, the tile plan, the
     grouped up projection, SwiGLU on the ``rows * active`` pairs, the grouped down projection and the combine; ids,
-    weights and plan never leave the device.  ``step.plan_header()`` reads the last plan's ``(n_tiles, P)``."""
+    weights and plan never leave the device.  ``step.plan_header()`` reads the last plan's ``(n_tiles, P)``.  With
+    ``block`` (``--dtype fp8-block``) the experts are e4m3 with one fp32 scale per 128 x 128 block, quantised here once,
+    ``gsx_quant_fp8_block`` quantises the rows in front of each of the two projections and both run on
+    ``gsx_moe_prefill_gemm_fp8_block_nt``; everything else is as without it."""
     hidden, nqkv = heads * ATTN_D, (heads + 2 * kv_heads) * ATTN_D
     rows = batch * chunk
     per_seq, pages = kv_pages(batch, context, page)
     layers = max(w_layers, kv_layers)
     bf = torch.bfloat16
+    edt = torch.float8_e4m3fn if block else bf  # the experts' type
     nexp, pairs = max(experts, 1), rows * max(active, 1)  # a dense MLP is one expert that every row takes once
     wqkv = torch.empty(w_layers, nqkv, hidden, device=dev, dtype=bf)
     wo = torch.empty(w_layers, hidden, hidden, device=dev, dtype=bf)
-    wgu = torch.empty(w_layers, nexp * 2 * ffn, hidden, device=dev, dtype=bf)
-    wdown = torch.empty(w_layers, nexp * hidden, ffn, device=dev, dtype=bf)
+    wgu = torch.empty(w_layers, nexp * 2 * ffn, hidden, device=dev, dtype=edt)
+    wdown = torch.empty(w_layers, nexp * hidden, ffn, device=dev, dtype=edt)
     router = torch.empty(w_layers, experts, hidden, device=dev, dtype=bf)
+    sgu = torch.empty(w_layers, nexp, 2 * ffn // 128, hidden // 128, device=dev) if block else None
+    sdown = torch.empty(w_layers, nexp, hidden // 128, ffn // 128, device=dev) if block else None
     for i in range(w_layers):  # one matrix at a time: nothing larger is ever held in fp32
-        for w, k, per in ((wqkv, hidden, 1), (wo, hidden, 1), (wgu, hidden, nexp), (wdown, ffn, nexp),
-                          (router, hidden, 1)):
+        for w, k, per, s in ((wqkv, hidden, 1, None), (wo, hidden, 1, None), (wgu, hidden, nexp, sgu),
+                             (wdown, ffn, nexp, sdown), (router, hidden, 1, None)):
             n = w.shape[1] // per  # an expert at a time; a dense layer has no router
             for x in range(per if n else 0):
-                w[i, x * n:(x + 1) * n].copy_(torch.randn(n, k, device=dev) / math.sqrt(k))
+                v = torch.randn(n, k, device=dev) / math.sqrt(k)
+                if s is not None:  # block-quantised as the moe workload's experts are
+                    blocks = v.view(n // 128, 128, k // 128, 128)
+                    s[i, x].copy_(blocks.abs().amax(dim=(1, 3)).clamp_min(2.0 ** -100) / 448.0)
+                    v = (blocks / s[i, x][:, None, :, None]).clamp(-448.0, 448.0).reshape(n, k)
+                w[i, x * n:(x + 1) * n].copy_(v)
     ln = torch.ones(w_layers, 2, hidden, device=dev, dtype=bf)
     kdt = bf if kv_dtype == "bf16" else torch.float8_e4m3fn
     kc = torch.empty(kv_layers, pages, kv_heads, page, ATTN_D, device=dev, dtype=kdt)
@@ -1385,7 +1414,7 @@ def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, con
     o = torch.empty_like(q)
     gu = torch.empty(pairs, 2 * ffn, device=dev, dtype=bf)
     act = torch.empty(pairs, ffn, device=dev, dtype=bf)
-    wqkv_b, wo_b, wgu_b, wdown_b = (w[0].numel() * 2 for w in (wqkv, wo, wgu, wdown))
+    wqkv_b, wo_b, wgu_b, wdown_b = (w[0].numel() * w.element_size() for w in (wqkv, wo, wgu, wdown))
     cache_bytes = kc[0].numel() * kc.element_size()
     scale = 1.0 / math.sqrt(ATTN_D)
     if experts:
@@ -1396,6 +1425,11 @@ def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, con
         plan = torch.zeros(plan_ints, device=dev, dtype=torch.int32)
         ws = torch.empty(max(ws_bytes, 4) // 4, device=dev, dtype=torch.int32)
         yexp = torch.empty(pairs, hidden, device=dev, dtype=bf)
+    if block:  # the quantised rows in front of the two projections, and their scales
+        qxn = torch.empty(rows, hidden, device=dev, dtype=edt)
+        sxn = torch.empty(rows, hidden // 128, device=dev)
+        qact = torch.empty(pairs, ffn, device=dev, dtype=edt)
+        sact = torch.empty(pairs, ffn // 128, device=dev)
     torch.cuda.synchronize()
 
     def moe_mlp(wi):
@@ -1403,11 +1437,22 @@ def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, con
                 hidden)
         kl.moe_prefill_route(gs, rlogits.data_ptr(), ids.data_ptr(), tw.data_ptr(), rows, experts, active)
         kl.moe_prefill_plan(gs, ids.data_ptr(), plan.data_ptr(), rows, active, experts, ws.data_ptr(), ws_bytes)
-        kl.moe_prefill_gemm_nt(gs, xn.data_ptr(), active, wgu.data_ptr() + wi * wgu_b, gu.data_ptr(), plan.data_ptr(),
-                               rows, active, experts, 2 * ffn, hidden)
-        kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), pairs, ffn)
-        kl.moe_prefill_gemm_nt(gs, act.data_ptr(), 1, wdown.data_ptr() + wi * wdown_b, yexp.data_ptr(),
-                               plan.data_ptr(), rows, active, experts, hidden, ffn)
+        if block:
+            kl.quant_fp8_block(gs, xn.data_ptr(), qxn.data_ptr(), sxn.data_ptr(), rows, hidden)
+            kl.moe_prefill_gemm_fp8_block(gs, qxn.data_ptr(), active, wgu.data_ptr() + wi * wgu_b, gu.data_ptr(),
+                                          plan.data_ptr(), rows, active, experts, 2 * ffn, hidden, sxn.data_ptr(),
+                                          sgu[wi].data_ptr())
+            kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), pairs, ffn)
+            kl.quant_fp8_block(gs, act.data_ptr(), qact.data_ptr(), sact.data_ptr(), pairs, ffn)
+            kl.moe_prefill_gemm_fp8_block(gs, qact.data_ptr(), 1, wdown.data_ptr() + wi * wdown_b, yexp.data_ptr(),
+                                          plan.data_ptr(), rows, active, experts, hidden, ffn, sact.data_ptr(),
+                                          sdown[wi].data_ptr())
+        else:
+            kl.moe_prefill_gemm_nt(gs, xn.data_ptr(), active, wgu.data_ptr() + wi * wgu_b, gu.data_ptr(),
+                                   plan.data_ptr(), rows, active, experts, 2 * ffn, hidden)
+            kl.silu_mul(gs, gu.data_ptr(), act.data_ptr(), pairs, ffn)
+            kl.moe_prefill_gemm_nt(gs, act.data_ptr(), 1, wdown.data_ptr() + wi * wdown_b, yexp.data_ptr(),
+                                   plan.data_ptr(), rows, active, experts, hidden, ffn)
         kl.moe_prefill_combine(gs, yexp.data_ptr(), tw.data_ptr(), sub.data_ptr(), rows, active, hidden)
 
     def step():
@@ -1459,6 +1504,8 @@ def prefill_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, chunk: int, con
         step.keep += (router, rlogits, ids, tw, plan, ws, yexp)
         step.buffers.update({"router": router, "rlogits": rlogits, "ids": ids, "tw": tw, "plan": plan, "yexp": yexp})
         step.plan_header = plan_header
+    if block:
+        step.keep += (sgu, sdown, qxn, sxn, qact, sact)
     return step, sync, finite
 
 
@@ -1534,7 +1581,7 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     if server or prefill:
         if kernel != "gsx":
             raise SystemExit(f"--workload {workload} runs on the library's kernels only (--kernel gsx)")
-        if dtype != "bf16":
+        if dtype != "bf16" and not (workload == "prefill-moe" and dtype == "fp8-block"):
             raise SystemExit(f"--workload {workload}: the weights are bf16 only (the KV cache: --kv-dtype)")
         if server and not 1 <= batch <= 16:
             raise SystemExit(f"--batch {batch}: 1..16")
@@ -1542,6 +1589,8 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         ffn = default_ffn(heads * ATTN_D) if ffn is None else ffn
         if ffn < 64 or ffn % 64:
             raise SystemExit(f"--ffn {ffn}: a multiple of 64, at least 64")
+        if why := fp8_block_refusal(workload, dtype, kernel, size, ffn):  # the default width, too
+            raise SystemExit(why)
     if attn:
         if not 1 <= batch <= 256:
             raise SystemExit(f"--batch {batch}: 1..256 sequences")
@@ -1598,7 +1647,8 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
                                    kv_layer_bytes(kv_dtype, batch, context, kv_heads))
         layers = max(w_layers, kv_layers)
         step, sync, finite = prefill_steps(torch, kl, gs, dev, kv_dtype, batch, chunk, context, heads, kv_heads, page,
-                                           ffn, w_layers, kv_layers, experts=experts, active=active)
+                                           ffn, w_layers, kv_layers, experts=experts, active=active,
+                                           block=dtype == "fp8-block")
         # the projections (2 flops per weight and row: a weight is 2 bytes), and QK^T and PV over the visible pairs;
         # with experts a row meets the dense part, the router and its `active` experts: real pairs only, no padding
         row_bytes = moe_layer_read_bytes(heads, kv_heads, ffn, experts, active) if experts else one_layer_bytes
@@ -1802,19 +1852,22 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     return out
 
 
-def fp8_block_refusal(workload: str, dtype: str, kernel: str, size: int) -> str | None:
+def fp8_block_refusal(workload: str, dtype: str, kernel: str, size: int, ffn: int | None = None) -> str | None:
     """Why ``--dtype fp8-block`` cannot run, or None: the block-scaled GEMMs are the large one (``gemm``), the skinny
-    one (``decode-wide``) and the grouped expert GEMM of MoE decode (``moe``)."""
+    one (``decode-wide``) and the grouped expert GEMMs of MoE decode (``moe``) and of MoE prefill (``prefill-moe``, whose
+    experts are ``ffn`` wide: None where the width is not known yet)."""
     if dtype != "fp8-block":
         return None
-    if workload not in ("gemm", "decode-wide", "moe"):
+    if workload not in ("gemm", "decode-wide", "moe", "prefill-moe"):
         return (f"--workload {workload} --dtype fp8-block: block-scaled operands are the gemm workload's only among "
-                "the large GEMMs, and decode-wide's and moe's among the streaming ones (the decode GEMM and the MoE "
-                "GEMMs of the layer and prefill workloads take none)")
+                "the large GEMMs, prefill-moe's experts' among the grouped ones, and decode-wide's and moe's among the "
+                "streaming ones (the decode GEMM, the dense prefill and the MoE GEMMs of the layer workloads take none)")
     if kernel == "torch":
         return "--dtype fp8-block needs the library's kernels (--kernel gsx)"
     if size < 128 or size % 128:
         return f"--dtype fp8-block --size {size}: a multiple of 128"
+    if workload == "prefill-moe" and ffn is not None and (ffn < 128 or ffn % 128):
+        return f"--workload prefill-moe --dtype fp8-block --ffn {ffn}: a multiple of 128"
     return None
 
 
@@ -1833,7 +1886,8 @@ class _Parser(argparse.ArgumentParser):
             self.error(f"argument --batch: {ns.batch} is not in 1..{top} (--workload {ns.workload})")
         if ns.workload == "generate" and (why := generate_refusal(ns.batch, ns.vocab)):
             self.error(f"--workload generate: {why}")
-        if why := fp8_block_refusal(ns.workload, ns.dtype, getattr(ns, "kernel", "gsx"), ns.size):
+        if why := fp8_block_refusal(ns.workload, ns.dtype, getattr(ns, "kernel", "gsx"), ns.size,
+                                    getattr(ns, "ffn", None)):
             self.error(why)
         if why := moe_refusal(ns.workload, getattr(ns, "experts", 0), getattr(ns, "experts_active", MOE_MAX_ACTIVE)):
             self.error(why)
@@ -1916,7 +1970,8 @@ def build_parser() -> argparse.ArgumentParser:
                          "workload's with a residual stream, two RMSNorms and the SwiGLU MLP); prefill: the same layer on "
                          "--batch sequences of --chunk new tokens each, causal attention over the paged cache "
                          "(compute-bound); prefill-moe: that prefill layer with a mixture-of-experts MLP (--experts, a "
-                         "multiple of 128; --experts-active) on the grouped 128x128 GEMM; generate: the layer workload closed into generation: the embedding lookup of "
+                         "multiple of 128; --experts-active) on the grouped 128x128 GEMM (--dtype bf16, or fp8-block "
+                         "with --ffn a multiple of 128); generate: the layer workload closed into generation: the embedding lookup of "
                          "the last step's tokens, the layers, a final RMSNorm, the LM head (--vocab columns) and the "
                          "sampler, token to token through device memory; moe: the MoE MLP of a decode step over a ring "
                          "of layers' experts (--size is the hidden size, --ffn, --experts, --experts-active; --dtype "

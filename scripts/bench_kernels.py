@@ -1698,6 +1698,22 @@ def moe_fp8_block(shapes=MOE_SHAPES, ms=(1, 8, 16), ring_bytes=(2 << 30) + 1, re
     return out
 
 
+def _windows(ts, call, window_ms):
+    """``(iters, one)``: ``one(iters)`` times a window of ``iters`` calls by the events of the stream ``ts`` and gives
+    the milliseconds per call; ``iters`` fills ``window_ms``, from a first window of 3 calls."""
+    def one(iters):
+        with torch.cuda.stream(ts):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            for _ in range(iters):
+                call()
+            e1.record(ts)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / iters
+    iters = max(5, min(500, int(window_ms / max(one(3), 1e-3))))
+    return iters, one
+
+
 def moe_prefill(shapes=((2048, 768, 128, 8), (4096, 14336, 8, 2)), ms=(1024, 8192), rounds=3, window_ms=30.0):
     """The MoE prefill kernels.  Routing comes from random router weights and inputs through ``moe_prefill_route`` and
     ``moe_prefill_plan``.  Per shape, ``m`` and projection the grouped 128x128 GEMM is timed against the dense
@@ -1712,19 +1728,7 @@ def moe_prefill(shapes=((2048, 768, 128, 8), (4096, 14336, 8, 2)), ms=(1024, 819
     dense = {name: i for i, name in hip.gemm_cfgs().items()}["128x128/4w"]
 
     def windows(call):
-        """``(iters, one)``: ``one(iters)`` times a window of ``iters`` calls by the stream's events and gives the
-        milliseconds per call; ``iters`` fills ``window_ms``, from a first window of 3 calls."""
-        def one(iters):
-            with torch.cuda.stream(ts):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(ts)
-                for _ in range(iters):
-                    call()
-                e1.record(ts)
-            e1.synchronize()
-            return e0.elapsed_time(e1) / iters
-        iters = max(5, min(500, int(window_ms / max(one(3), 1e-3))))
-        return iters, one
+        return _windows(ts, call, window_ms)
 
     for hidden, ffn, e, topk in shapes:
         gen = torch.Generator(device="cuda").manual_seed(hidden + e)
@@ -1797,6 +1801,108 @@ def moe_prefill(shapes=((2048, 768, 128, 8), (4096, 14336, 8, 2)), ms=(1024, 819
     return out
 
 
+def moe_prefill_fp8_block(shapes=((2048, 768, 128, 8), (4096, 14336, 8, 2), (7168, 2048, 256, 8)), ms=(1024, 8192),
+                          rounds=3, window_ms=30.0):
+    """The block-scaled fp8 grouped GEMM of MoE prefill, on :func:`moe_prefill`'s shapes and DeepSeek-V3's expert shape,
+    both projections, routing from ``moe_prefill_route`` and ``moe_prefill_plan``.  Three calls on the same routing,
+    interleaved in one process, the median of ``rounds`` windows of about ``window_ms`` after a warm-up and their
+    spread (max - min over the median):
+    ``fp8``, the new entry point; ``bf16``, ``gsx_moe_prefill_gemm_nt`` on the dequantised operands, the path there was
+    before; ``per_expert``, one ``gsx_gemm_fp8_block_nt`` per expert on rows gathered and padded to 128 beforehand (the
+    gather is not timed and the host knows the plan), what the tile reaches without a gather.  TFLOP/s count the P real
+    pairs.  ``beats_bf16`` holds only where the fp8 median is below the bf16 median by more than the two ranges
+    (max - min) together."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    f8, bf = torch.float8_e4m3fn, torch.bfloat16
+    for hidden, ffn, e, topk in shapes:
+        gen = torch.Generator(device="cuda").manual_seed(hidden + e)
+        rw = torch.randn(e, hidden, device="cuda", generator=gen) / math.sqrt(hidden)
+        plans = {}
+        for m in ms:  # the routings, once per shape
+            pairs = m * topk
+            logits = (torch.randn(m, hidden, device="cuda", generator=gen) @ rw.t()).bfloat16().contiguous()
+            ids = torch.empty(pairs, device="cuda", dtype=torch.int32)
+            tw = torch.empty(pairs, device="cuda", dtype=torch.float32)
+            plan = torch.empty(hip.moe_prefill_plan_ints(m, topk, e), device="cuda", dtype=torch.int32)
+            wsb = hip.moe_prefill_workspace_bytes(m, topk, e)
+            ws = torch.empty(wsb // 4, device="cuda", dtype=torch.int32)
+            torch.cuda.synchronize()
+            hip.moe_prefill_route(s, logits.data_ptr(), e, ids.data_ptr(), tw.data_ptr(), m, e, topk)
+            hip.moe_prefill_plan(s, ids.data_ptr(), plan.data_ptr(), m, topk, e, ws.data_ptr(), wsb)
+            s.sync()
+            plans[m] = plan
+        for name, (n, k) in {"up": (2 * ffn, hidden), "down": (hidden, ffn)}.items():  # a projection's experts at a time
+            g = k // 128
+            w = torch.empty(e * n, k, device="cuda", dtype=f8)
+            wb = torch.empty(e * n, k, device="cuda", dtype=bf)
+            sb = torch.empty(e, n // 128, g, device="cuda")
+            for x0 in range(e):  # an expert at a time: block-quantised, and dequantised for the bf16 call
+                blocks = (torch.randn(n, k, device="cuda", generator=gen) / math.sqrt(k)).view(n // 128, 128, g, 128)
+                sb[x0] = blocks.abs().amax(dim=(1, 3)).clamp_min(2.0 ** -100) / 448.0
+                q = (blocks / sb[x0][:, None, :, None]).clamp(-448.0, 448.0).to(f8)
+                w[x0 * n:(x0 + 1) * n].copy_(q.view(n, k))
+                wb[x0 * n:(x0 + 1) * n].copy_((q.float() * sb[x0][:, None, :, None]).view(n, k))
+            for m in ms:
+                pairs, plan = m * topk, plans[m]
+                a_div = topk if name == "up" else 1
+                rows = pairs // a_div
+                x = torch.randn(rows, k, device="cuda", dtype=bf, generator=gen)
+                a, sa = torch.empty(rows, k, device="cuda", dtype=f8), torch.empty(rows, g, device="cuda")
+                c = torch.empty(pairs, n, device="cuda", dtype=bf)
+                torch.cuda.synchronize()
+                hip.quant_fp8_block(s, x.data_ptr(), k, a.data_ptr(), k, sa.data_ptr(), g, rows, k)
+                s.sync()
+                xb = (a.float().view(rows, g, 128) * sa[:, :, None]).view(rows, k).to(bf)
+                ph = plan.cpu()
+                n_tiles = int(ph[0])
+                t_max = (len(ph) - 4) // 129
+                tile_expert, prow = ph[4:4 + n_tiles], ph[4 + t_max:4 + t_max + 128 * n_tiles].view(n_tiles, 128)
+                per = []  # (expert, padded rows, gathered A, gathered scale_a, C) of every expert with a tile
+                for x0 in tile_expert.unique().tolist():
+                    src = (prow[tile_expert == x0].reshape(-1).clamp_min(0) // a_div).cuda().long()
+                    per.append((x0, len(src), a.view(torch.uint8)[src].view(f8), sa[src].contiguous(),
+                                torch.empty(len(src), n, device="cuda", dtype=bf)))
+                torch.cuda.synchronize()
+
+                def per_expert():
+                    for x0, r, ga, gsa, gc_ in per:
+                        hip.gemm_fp8_block_nt(s, ga.data_ptr(), w.data_ptr() + x0 * n * k, gc_.data_ptr(), r, n, k,
+                                              gsa.data_ptr(), g, sb.data_ptr() + x0 * (n // 128) * g * 4)
+
+                calls = {"fp8": lambda: hip.moe_prefill_gemm_fp8_block_nt(s, a.data_ptr(), a_div, w.data_ptr(),
+                                                                          c.data_ptr(), plan.data_ptr(), m, topk, e, n,
+                                                                          k, sa.data_ptr(), g, sb.data_ptr()),
+                         "bf16": lambda: hip.moe_prefill_gemm_nt(s, xb.data_ptr(), a_div, wb.data_ptr(), c.data_ptr(),
+                                                                 plan.data_ptr(), m, topk, e, n, k),
+                         "per_expert": per_expert}
+                timers = {v: _windows(ts, call, window_ms) for v, call in calls.items()}  # this is the warm-up too
+                got = {v: [] for v in calls}
+                for _ in range(rounds):
+                    for v, (iters, one) in timers.items():  # interleaved
+                        got[v].append(one(iters))
+                med = {v: statistics.median(t) for v, t in got.items()}
+                rng = {v: max(t) - min(t) for v, t in got.items()}
+                row = {"hidden": hidden, "ffn": ffn, "experts": e, "topk": topk, "m": m, "pairs": pairs, "proj": name,
+                       "n": n, "k": k, "n_tiles": n_tiles, "pad_share": round(1 - pairs / (128 * n_tiles), 4)}
+                for v in calls:
+                    row[f"{v}_ms"] = round(med[v], 4)
+                    row[f"{v}_spread"] = round(rng[v] / med[v], 4)
+                    row[f"{v}_tflops_real"] = round(2.0 * pairs * n * k / med[v] / 1e9, 1)
+                row["fp8_over_bf16_speedup"] = round(med["bf16"] / med["fp8"], 3)
+                row["fp8_over_per_expert_time"] = round(med["fp8"] / med["per_expert"], 3)
+                row["beats_bf16"] = bool(med["bf16"] - med["fp8"] > rng["bf16"] + rng["fp8"])
+                out.append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                del a, sa, c, x, xb, per
+                torch.cuda.empty_cache()
+            del w, wb, sb
+            torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 def hbm(nbytes=16 << 30, reps=5):
     s = hip.Stream(0)
     buf = hip.DeviceBuffer(0, nbytes)
@@ -1835,6 +1941,7 @@ if __name__ == "__main__":
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
                 "moe": moe, "moe_128": lambda: moe(shapes=MOE_SHAPES[:1]),  # the 128-expert shape alone
                 "moe_prefill": moe_prefill, "moe_fp8_block": moe_fp8_block,
+                "moe_prefill_fp8_block": moe_prefill_fp8_block,
                 "hbm": hbm}
     only = sys.argv[2].split(",") if len(sys.argv) > 2 else list(sections)  # [out.json [section,section..]]
     res = {name: sections[name]() for name in only}
