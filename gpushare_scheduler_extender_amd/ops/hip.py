@@ -124,6 +124,7 @@ def lib():
         # stream, kind, Q, KV_cache, block_table, seq_lens, O; B, Hq, page, num_pages, table_stride, max_seq_len; scale,
         # kv_scale; workspace, workspace_bytes
         _mla_sig = [vp, i32] + [vp] * 5 + [i32] * 6 + [ctypes.c_float] * 2 + [vp, u64]
+        _mla_multi_sig = [vp, i32] + [vp] * 5 + [i32] * 7 + [ctypes.c_float] * 2 + [vp, u64]  # T after B
         # stream, out_kind, X, x_stride, R_in, R_out, r_stride, W, Y, y_stride, scale_out; M, H; eps
         _norm_sig = [vp, i32, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, i32, i32,
                      ctypes.c_float]
@@ -241,6 +242,12 @@ def lib():
             "gsx_mla_decode_attn_cfg_name": ([i32], ctypes.c_char_p),
             "gsx_mla_decode_attn_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 2, i32),
             "gsx_event_time_mla_decode_attn": ([*_mla_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
+            "gsx_mla_decode_attn_multi": (_mla_multi_sig, i32),
+            "gsx_mla_decode_attn_multi_launch_cfg": ([*_mla_multi_sig, i32, i32], i32),
+            "gsx_mla_decode_attn_multi_workspace_bytes": ([i32] * 5 + [ctypes.POINTER(u64)], i32),
+            "gsx_mla_decode_attn_multi_cfg_name": ([i32], ctypes.c_char_p),
+            "gsx_mla_decode_attn_multi_cfg_shape": ([i32] + [ctypes.POINTER(i32)] * 2, i32),
+            "gsx_event_time_mla_decode_attn_multi": ([*_mla_multi_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_add_rmsnorm": (_norm_sig, i32),
             "gsx_event_time_add_rmsnorm": ([*_norm_sig, i32, ctypes.POINTER(ctypes.c_float)], i32),
             "gsx_silu_mul": (_silu_sig, i32),
@@ -1207,6 +1214,79 @@ def time_mla_decode_attn(stream: Stream, kind: str, q: int, kv_cache: int, block
                                                         page, num_pages, table_stride, max_seq_len, scale, kv_scale,
                                                         workspace, workspace_bytes), iters, ctypes.byref(ms)),
         "time_mla_decode_attn")
+    return ms.value
+
+
+def _mla_multi_args(stream: Stream, kind: str, q: int, kv_cache: int, block_table: int, seq_lens: int, o: int, b: int,
+                    t: int, hq: int, page: int, num_pages: int, table_stride: int, max_seq_len: int, scale: float,
+                    kv_scale: float, workspace: int, workspace_bytes: int) -> tuple:
+    a = _mla_args(stream, kind, q, kv_cache, block_table, seq_lens, o, b, hq, page, num_pages, table_stride,
+                  max_seq_len, scale, kv_scale, workspace, workspace_bytes)
+    return (*a[:8], t, *a[8:])  # T follows B
+
+
+def mla_decode_attn_multi(stream: Stream, kind: str, q: int, kv_cache: int, block_table: int, seq_lens: int, o: int,
+                          b: int, t: int, hq: int, page: int, num_pages: int, table_stride: int, max_seq_len: int,
+                          scale: float, kv_scale: float = 1.0, workspace: int = 0, workspace_bytes: int = 0):
+    """Causal multi-head latent attention of ``t`` new tokens per sequence (1..16) over the paged latent cache, the
+    cache read once for all of them: ``o[b * t][hq][512]`` from ``q[b * t][hq][576]`` and the cache, kinds and scales
+    of :func:`mla_decode_attn`.  ``seq_lens[b]`` is the length BEFORE the chunk, whose ``t`` latent rows are already in
+    the cache; row ``b * t + i`` attends to tokens ``0 .. seq_lens[b] + i`` and is a row of zeros at or past
+    ``max_seq_len``.  ``workspace`` is device memory of at least :func:`mla_decode_attn_multi_workspace_bytes` bytes
+    for the split-KV partials.  Not synchronised."""
+    _ck(lib().gsx_mla_decode_attn_multi(*_mla_multi_args(stream, kind, q, kv_cache, block_table, seq_lens, o, b, t, hq,
+                                                         page, num_pages, table_stride, max_seq_len, scale, kv_scale,
+                                                         workspace, workspace_bytes)), "mla_decode_attn_multi")
+
+
+def mla_decode_attn_multi_workspace_bytes(b: int, t: int, hq: int, page: int, max_seq_len: int) -> int:
+    """Bytes of workspace :func:`mla_decode_attn_multi` needs for these arguments (0: none)."""
+    n = ctypes.c_uint64(0)
+    _ck(lib().gsx_mla_decode_attn_multi_workspace_bytes(b, t, hq, page, max_seq_len, ctypes.byref(n)),
+        "mla_decode_attn_multi_workspace_bytes")
+    return n.value
+
+
+def mla_decode_attn_multi_cfg_name(cfg: int) -> str | None:
+    """The name of multi-token MLA decode attention configuration ``cfg``, or None outside the library's table."""
+    name = lib().gsx_mla_decode_attn_multi_cfg_name(cfg)
+    return None if name is None else name.decode()
+
+
+def mla_decode_attn_multi_cfg_shape(cfg: int) -> tuple[int, int]:
+    """``(waves, inflight)`` of configuration ``cfg`` (native/kernels/attn_mla_multi.hip; the table is 0 "4w-f1": (4,
+    1) and 1 "4w-f2": (4, 2)): waves per workgroup, tiles of 32 tokens a workgroup keeps in flight.  An unknown config
+    raises HipError."""
+    v = [ctypes.c_int(0) for _ in range(2)]
+    if lib().gsx_mla_decode_attn_multi_cfg_shape(cfg, *map(ctypes.byref, v)) != 0:
+        raise HipError(f"mla decode attn multi cfg {cfg}: unknown config")
+    return tuple(x.value for x in v)
+
+
+def mla_decode_attn_multi_launch_cfg(stream: Stream, kind: str, q: int, kv_cache: int, block_table: int,
+                                     seq_lens: int, o: int, b: int, t: int, hq: int, page: int, num_pages: int,
+                                     table_stride: int, max_seq_len: int, scale: float, cfg: int, splits: int,
+                                     kv_scale: float = 1.0, workspace: int = 0, workspace_bytes: int = 0):
+    """Launch one configuration of the multi-token MLA decode attention with ``splits`` (1..64) splits of every
+    sequence; the workspace needs ``b * t * hq * splits * 2056`` bytes when ``splits > 1``.  An unknown config raises
+    HipError."""
+    _ck(lib().gsx_mla_decode_attn_multi_launch_cfg(*_mla_multi_args(stream, kind, q, kv_cache, block_table, seq_lens,
+                                                                    o, b, t, hq, page, num_pages, table_stride,
+                                                                    max_seq_len, scale, kv_scale, workspace,
+                                                                    workspace_bytes), cfg, splits),
+        f"mla decode attn multi cfg {cfg} splits {splits}")
+
+
+def time_mla_decode_attn_multi(stream: Stream, kind: str, q: int, kv_cache: int, block_table: int, seq_lens: int,
+                               o: int, b: int, t: int, hq: int, page: int, num_pages: int, table_stride: int,
+                               max_seq_len: int, scale: float, iters: int, kv_scale: float = 1.0, workspace: int = 0,
+                               workspace_bytes: int = 0) -> float:
+    ms = ctypes.c_float(0)
+    _ck(lib().gsx_event_time_mla_decode_attn_multi(*_mla_multi_args(stream, kind, q, kv_cache, block_table, seq_lens,
+                                                                    o, b, t, hq, page, num_pages, table_stride,
+                                                                    max_seq_len, scale, kv_scale, workspace,
+                                                                    workspace_bytes), iters, ctypes.byref(ms)),
+        "time_mla_decode_attn_multi")
     return ms.value
 
 

@@ -17,7 +17,9 @@ Targets (outputs land in ``gpushare_scheduler_extender_amd/_native/``):
                 (M <= 128, bf16 and fp8, with a split of K; gemm_skinny.hip) and its block-scaled fp8 form
                 (gemm_skinny_fp8_block.hip), decode attention over a
                 paged KV cache (attn_decode.hip) and its multi-token form (attn_decode_multi.hip), multi-head latent
-                attention decode over a paged latent cache (attn_mla.hip), RoPE + KV-cache
+                attention decode over a paged latent cache (attn_mla.hip) and its multi-token form, 2 to 16 new tokens
+                per sequence as columns of the same tile pass (attn_mla_multi.hip; both on the kernel of attn_mla.h),
+                RoPE + KV-cache
                 append (kv_append.hip), fused residual add + RMSNorm and SwiGLU (norm_act.hip), causal prefill attention over the same cache (attn_prefill.hip), the token
                 sampler and the embedding gather (sample.hip), the MoE router and combine (moe.hip; the grouped expert
                 GEMM is a form of the decode kernel in gemm_decode.hip; its block-scaled fp8 form is

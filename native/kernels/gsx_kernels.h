@@ -46,7 +46,8 @@
 //  * MLA decode attention — multi-head latent attention (DeepSeek-V2/V3/R1, Kimi K2) over a paged cache of one
 //                          576-element latent row per token that is K and V for all 1..128 heads, bf16 or e4m3:
 //                          the tile staged in LDS once and read as both operands, the output split by d over the
-//                          waves (attn_mla.hip);
+//                          waves (attn_mla.hip), and its multi-token form, 2 to 16 new tokens per sequence as the
+//                          columns of the same tile pass (attn_mla_multi.hip);
 //  * add + RMSNorm, SwiGLU — the residual stream, the normalisation and the MLP's activation of
 //                          a decoder layer, to bf16 or to e4m3 with a scale per row
 //                          (norm_act.hip);
@@ -616,6 +617,51 @@ int gsx_event_time_mla_decode_attn(void* stream, int kind, const void* Q, const 
                                    const void* seq_lens, void* O, int B, int Hq, int page, int num_pages,
                                    int table_stride, int max_seq_len, float scale, float kv_scale, void* workspace,
                                    uint64_t workspace_bytes, int iters, float* ms);
+
+// Multi-token MLA decode attention (attn_mla_multi.hip): T new tokens per sequence, 1 <= T <= 16, on the plan of
+// gsx_mla_decode_attn: the T * Hq (token, head) pairs of a sequence are the columns of ceil(T * Hq / 64) column blocks,
+// a workgroup per (sequence, column block, split), every tile of 32 cache rows staged once for all columns of a block.
+//   Q[B * T][Hq][576], O[B * T][Hq][512]   bf16; the cache, block_table, seq_lens, kind, scale and kv_scale are exactly
+//                                        those of gsx_mla_decode_attn
+// Semantics: those of gsx_decode_attn_multi.  seq_lens holds the lengths BEFORE the chunk, and the T new tokens' rows
+// are already in the cache (the caller's job); base = clamp(seq_lens[b], 0, max_seq_len); row n = b * T + t is at pos =
+// base + t, is LIVE when pos < max_seq_len and then attends to tokens 0 .. pos of its sequence; a row that is not live
+// gives a row of zeros.
+// Numerics per (row, head): those of gsx_mla_decode_attn.  A token a row may not see has its x replaced by -inf by a
+// select; slots at or past the sequence's end, min(base + T, max_seq_len), are staged as zeros; between a row's pos and
+// that end the latent must be finite (0 * NaN in the PV product would reach the row), as for gsx_decode_attn_multi.
+// The splits cut the sequence's tiles of 32 tokens, counted up to that end, as gsx_mla_decode_attn cuts them up to
+// seq_len, whatever the column block: the result depends on `splits` and on nothing else, not on T, on how columns are
+// grouped or on where workgroups run.  A partial in which a column saw no token has m = -inf, l = 0 and weight 0; the
+// merge goes in split order; no atomics.  T == 1 gives the bits of gsx_mla_decode_attn on seq_lens + 1 for the same
+// configuration and splits.
+// Requirements: those of gsx_mla_decode_attn, and 1 <= T <= 16, B * T * Hq below 2^31 (the merge's grid), B * column
+// blocks * splits below 2^31, O overlapping nothing.  With splits > 1 the workspace holds B * T * Hq * splits * 2056
+// bytes; a workspace too small is refused with the bytes needed in the text.  Everything is validated before the first
+// device call; launches on `stream` and returns without synchronising.  Safety: the clamps of gsx_mla_decode_attn.
+// gsx_mla_decode_attn_multi picks the configuration and `splits` from B, T * Hq and max_seq_len alone (mlm_pick() in
+// attn_mla_multi.hip); gsx_mla_decode_attn_multi_workspace_bytes returns what it then needs.
+int gsx_mla_decode_attn_multi(void* stream, int kind, const void* Q, const void* KV_cache, const void* block_table,
+                              const void* seq_lens, void* O, int B, int T, int Hq, int page, int num_pages,
+                              int table_stride, int max_seq_len, float scale, float kv_scale, void* workspace,
+                              uint64_t workspace_bytes);
+int gsx_mla_decode_attn_multi_workspace_bytes(int B, int T, int Hq, int page, int max_seq_len, uint64_t* bytes);
+// The configurations, one table for both cache types and every fragment count: 0 "4w-f1", 1 "4w-f2", as
+// gsx_mla_decode_attn has them.  _cfg_name returns NULL and _cfg_shape nonzero outside the table.  _launch_cfg takes
+// 1 <= splits <= 64 and otherwise what gsx_mla_decode_attn_multi takes.
+const char* gsx_mla_decode_attn_multi_cfg_name(int cfg);
+int gsx_mla_decode_attn_multi_cfg_shape(int cfg, int* waves, int* inflight);
+int gsx_mla_decode_attn_multi_launch_cfg(void* stream, int kind, const void* Q, const void* KV_cache,
+                                         const void* block_table, const void* seq_lens, void* O, int B, int T, int Hq,
+                                         int page, int num_pages, int table_stride, int max_seq_len, float scale,
+                                         float kv_scale, void* workspace, uint64_t workspace_bytes, int cfg,
+                                         int splits);
+// elapsed milliseconds of `iters` back-to-back gsx_mla_decode_attn_multi on `stream`, by hip events (for benches)
+int gsx_event_time_mla_decode_attn_multi(void* stream, int kind, const void* Q, const void* KV_cache,
+                                         const void* block_table, const void* seq_lens, void* O, int B, int T, int Hq,
+                                         int page, int num_pages, int table_stride, int max_seq_len, float scale,
+                                         float kv_scale, void* workspace, uint64_t workspace_bytes, int iters,
+                                         float* ms);
 
 // Fused residual add + RMSNorm, and SwiGLU (norm_act.hip): what a decoder layer has between its projections.  Both
 // write bf16, or OCP e4m3 with one fp32 scale per row, which is exactly the A and scale_a that

@@ -41,10 +41,12 @@ builds; nothing else of this repository): counterpart of the reference's sample 
   ``scaled_dot_product_attention(enable_gqa=True)`` on a contiguous copy of the same data.  ``--new-tokens T`` (2..16,
   the library only) makes the last T tokens of every sequence new ones and runs ``gsx_decode_attn_multi`` over them:
   the cache is read once for all T, ``tokens_per_s`` counts B * T and ``new_tokens`` is reported.  ``--mla`` (the
-  library only, one new token, ``--kv-heads`` left alone) is the attention of DeepSeek-V2/V3/R1 and Kimi K2 instead:
+  library only, ``--kv-heads`` left alone) is the attention of DeepSeek-V2/V3/R1 and Kimi K2 instead:
   every layer of the ring is one latent cache of 576-element rows (512 latent + 64 RoPE) that all ``--heads`` query
   heads (1..128) share as K and V, and a layer is one ``gsx_mla_decode_attn``; ``tbps`` counts rows of 576 elements,
-  ``tflops`` 2 * heads * (576 + 512) per cached token, and ``"mla": true`` is reported;
+  ``tflops`` 2 * heads * (576 + 512) per cached token, and ``"mla": true`` is reported.  With ``--new-tokens T``
+  (2..16) the ring holds the T new rows as the last of every sequence, a layer is one ``gsx_mla_decode_attn_multi``,
+  and ``new_tokens`` and ``tokens_per_s`` counting B * T are reported;
 * ``--workload server`` is a whole decode layer per ring layer and step, on the library's kernels only: the fused QKV
   projection of ``--batch`` rows (1..16; hidden = ``--heads`` x 128, bf16 weights) through the decode GEMM, RoPE and
   the append of the new token's K and V to the layer's paged cache (``gsx_kv_append``; ``--kv-dtype`` selects the
@@ -362,6 +364,11 @@ class Kernels:
                                               + [vp, ctypes.c_uint64])
             L.gsx_mla_decode_attn_workspace_bytes.argtypes = [i32] * 4 + [ctypes.POINTER(ctypes.c_uint64)]
             L.gsx_mla_decode_attn.restype = L.gsx_mla_decode_attn_workspace_bytes.restype = i32
+        if hasattr(L, "gsx_mla_decode_attn_multi"):  # likewise: an image built before its multi-token form
+            L.gsx_mla_decode_attn_multi.argtypes = ([vp, i32] + [vp] * 5 + [i32] * 7 + [ctypes.c_float] * 2
+                                                    + [vp, ctypes.c_uint64])
+            L.gsx_mla_decode_attn_multi_workspace_bytes.argtypes = [i32] * 5 + [ctypes.POINTER(ctypes.c_uint64)]
+            L.gsx_mla_decode_attn_multi.restype = L.gsx_mla_decode_attn_multi_workspace_bytes.restype = i32
         if hasattr(L, "gsx_prefill_attn"):  # likewise: an image built before the prefill attention
             L.gsx_prefill_attn.argtypes = [vp, i32] + [vp] * 6 + [i32] * 9 + [ctypes.c_float] * 3
             L.gsx_prefill_attn.restype = i32
@@ -553,6 +560,24 @@ class Kernels:
                                                                           (q, kv, table, lens, o)),
                                             b, hq, page, num_pages, table_stride, max_seq_len, scale, 1.0,
                                             ctypes.c_void_p(ws), ws_bytes), "mla_decode_attn")
+
+    def mla_multi_workspace_bytes(self, b: int, t: int, hq: int, page: int, max_seq_len: int) -> int:
+        if not hasattr(self.L, "gsx_mla_decode_attn_multi"):
+            raise RuntimeError(f"{self.path} has no gsx_mla_decode_attn_multi: rebuild it")
+        n = ctypes.c_uint64(0)
+        self._ck(self.L.gsx_mla_decode_attn_multi_workspace_bytes(b, t, hq, page, max_seq_len, ctypes.byref(n)),
+                 "mla_decode_attn_multi_workspace_bytes")
+        return n.value
+
+    def mla_decode_attn_multi(self, s, kv_dtype: str, q: int, kv: int, table: int, lens: int, o: int, b: int, t: int,
+                              hq: int, page: int, num_pages: int, table_stride: int, max_seq_len: int, scale: float,
+                              ws: int, ws_bytes: int):
+        """Causal multi-head latent attention of ``t`` (1..16) new tokens per sequence over a paged latent cache (unit
+        cache scale); ``lens`` are the lengths before the new tokens."""
+        self._ck(self.L.gsx_mla_decode_attn_multi(s, ATTN_KV_KINDS[kv_dtype], *(ctypes.c_void_p(x) for x in
+                                                                                (q, kv, table, lens, o)),
+                                                  b, t, hq, page, num_pages, table_stride, max_seq_len, scale, 1.0,
+                                                  ctypes.c_void_p(ws), ws_bytes), "mla_decode_attn_multi")
 
     def kv_append(self, s, kv_dtype: str, qkv: int, qkv_stride: int, q_out: int, kc: int, vc: int, table: int,
                   lens: int, lens_out: int, cos: int, sin: int, rope_len: int, b: int, t: int, hq: int, hkv: int,
@@ -968,13 +993,13 @@ MLA_KV_HEADS_DEFAULT = 8  # --kv-heads as the parser leaves it: the latent cache
 
 def mla_refusal(workload: str, kernel: str, new_tokens: int, heads: int, kv_heads: int) -> str | None:
     """Why ``--mla`` cannot run, or None: known before torch loads.  The limits are the library's
-    (``gsx_mla_decode_attn``)."""
+    (``gsx_mla_decode_attn``, ``gsx_mla_decode_attn_multi``)."""
     if workload != "attn":
         return "--mla: --workload attn only"
     if kernel != "gsx":
         return "--mla: the library's kernel only (--kernel gsx)"
-    if new_tokens != 1:
-        return f"--mla --new-tokens {new_tokens}: one new token per sequence"
+    if not 1 <= new_tokens <= 16:
+        return f"--mla --new-tokens {new_tokens}: need 1 <= T <= 16"
     if kv_heads != MLA_KV_HEADS_DEFAULT:
         return f"--mla --kv-heads {kv_heads}: the latent cache is one row per token for all heads; leave --kv-heads alone"
     if not 1 <= heads <= 128:
@@ -982,20 +1007,25 @@ def mla_refusal(workload: str, kernel: str, new_tokens: int, heads: int, kv_head
     return None
 
 
-def mla_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, heads: int, page: int, layers: int):
+def mla_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, heads: int, page: int, layers: int,
+              new_tokens: int = 1):
     """``(step, sync)`` of the MLA attention workload: the ring and the block table of :func:`attn_steps`, every layer
     one latent cache ``[pages][page][576]`` filled with random normal rows, and a step that runs one
-    ``gsx_mla_decode_attn`` per layer (scale 192^-0.5, DeepSeek's 128 + 64 query-key width)."""
+    ``gsx_mla_decode_attn`` per layer (scale 192^-0.5, DeepSeek's 128 + 64 query-key width).  With ``new_tokens`` > 1
+    the last ``new_tokens`` rows of every sequence are the new tokens' and a layer is one
+    ``gsx_mla_decode_attn_multi``."""
     per_seq, pages = kv_pages(batch, context, page)
-    q = torch.randn(batch, heads, MLA_DK, device=dev, dtype=torch.bfloat16)
-    o = torch.empty(batch, heads, MLA_DV, device=dev, dtype=torch.bfloat16)
+    q = torch.randn(batch * new_tokens, heads, MLA_DK, device=dev, dtype=torch.bfloat16)
+    o = torch.empty(batch * new_tokens, heads, MLA_DV, device=dev, dtype=torch.bfloat16)
     kdt = torch.bfloat16 if kv_dtype == "bf16" else torch.float8_e4m3fn
     kv = torch.empty(layers, pages, page, MLA_DK, device=dev, dtype=kdt)
     for i in range(layers):  # one layer at a time: nothing larger is ever held in bf16
         kv[i].copy_(torch.randn(pages, page, MLA_DK, device=dev, dtype=torch.bfloat16).to(kdt))
     table = torch.randperm(pages, device=dev).to(torch.int32).view(batch, per_seq).contiguous()
-    lens = torch.full((batch,), context, device=dev, dtype=torch.int32)
-    ws_bytes = kl.mla_workspace_bytes(batch, heads, page, context)
+    multi = new_tokens > 1
+    lens = torch.full((batch,), context - new_tokens if multi else context, device=dev, dtype=torch.int32)
+    ws_bytes = (kl.mla_multi_workspace_bytes(batch, new_tokens, heads, page, context) if multi
+                else kl.mla_workspace_bytes(batch, heads, page, context))
     ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
     layer_bytes = kv[0].numel() * kv.element_size()
     scale = 192 ** -0.5
@@ -1003,6 +1033,11 @@ def mla_steps(torch, kl, gs, dev, kv_dtype: str, batch: int, context: int, heads
 
     def step():
         for i in range(layers):
+            if multi:
+                kl.mla_decode_attn_multi(gs, kv_dtype, q.data_ptr(), kv.data_ptr() + i * layer_bytes,
+                                         table.data_ptr(), lens.data_ptr(), o.data_ptr(), batch, new_tokens, heads,
+                                         page, pages, per_seq, context, scale, ws.data_ptr(), ws_bytes)
+                continue
             kl.mla_decode_attn(gs, kv_dtype, q.data_ptr(), kv.data_ptr() + i * layer_bytes, table.data_ptr(),
                                lens.data_ptr(), o.data_ptr(), batch, heads, page, pages, per_seq, context, scale,
                                ws.data_ptr(), ws_bytes)
@@ -1532,7 +1567,8 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         kernel = "gsx" if lib_path is not None else "torch"
         if lib_path is None and not quiet:
             print("[workload] libgsx_kernels.so not found: torch.matmul (hipBLASLt) instead", flush=True)
-    if why := new_tokens_refusal(workload, kernel, new_tokens, context, heads, kv_heads):
+    # the latent cache has no KV heads: --mla takes the rules of --new-tokens but the one on heads per KV head
+    if why := new_tokens_refusal(workload, kernel, new_tokens, context, *((1, 1) if mla else (heads, kv_heads))):
         raise SystemExit(why)
     kl = None
     if kernel == "gsx" or os.environ.get("GSX_CU_MASK"):
@@ -1684,9 +1720,11 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
     elif mla:
         layer_bytes = mla_layer_bytes(kv_dtype, batch, context)
         layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB), layer_bytes)
-        step, sync = mla_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, page, layers)
-        # QK^T over 576 and PV over 512 elements per (sequence, query head, cached token)
-        flops_attn = 2.0 * batch * heads * (MLA_DK + MLA_DV) * context * layers
+        step, sync = mla_steps(torch, kl, gs, dev, kv_dtype, batch, context, heads, page, layers, new_tokens)
+        # QK^T over 576 and PV over 512 elements per (sequence, query head, cached token); new token t sees
+        # new_tokens - 1 - t fewer
+        flops_attn = 2.0 * batch * heads * (MLA_DK + MLA_DV) * layers * (new_tokens * context
+                                                                         - new_tokens * (new_tokens - 1) / 2.0)
     elif attn:
         layer_bytes = kv_layer_bytes(kv_dtype, batch, context, kv_heads)
         layers = kv_ring_layers(default_kv_bytes(allocated) if kv_gib is None else int(kv_gib * GIB), layer_bytes)
@@ -1829,7 +1867,9 @@ def run(total: float, allocated: float, *, kernel: str = "auto", size: int = 819
         out.update({"workload": workload, "mla": True, "batch": batch, "layers": layers, "context": context,
                     "heads": heads, "kv_dtype": kv_dtype, "page": page,
                     "tbps": done * layers * mla_layer_bytes(kv_dtype, batch, context) / el / 1e12,
-                    "tokens_per_s": done * batch / el})  # tflops: 2 * heads * (576 + 512) per cached token
+                    "tokens_per_s": done * batch * new_tokens / el})  # tflops: 2 * heads * (576 + 512) per cached token
+        if new_tokens > 1:
+            out["new_tokens"] = new_tokens
     elif attn:
         out.update({"workload": workload, "batch": batch, "layers": layers, "context": context, "heads": heads,
                     "kv_heads": kv_heads, "kv_dtype": kv_dtype, "page": page,
@@ -1988,7 +2028,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mla", action="store_true",
                     help="--workload attn: multi-head latent attention (DeepSeek-V2/V3/R1, Kimi K2): every layer is one "
                          "latent cache of 576-element rows shared by all --heads (1..128) query heads and a layer is "
-                         "one gsx_mla_decode_attn (--kernel gsx only, one new token, --kv-heads left alone)")
+                         "one gsx_mla_decode_attn, or with --new-tokens 2..16 one gsx_mla_decode_attn_multi (--kernel "
+                         "gsx only, --kv-heads left alone)")
     ap.add_argument("--weights-gib", type=float, default=None,
                     help="--workload decode, server, layer and prefill: size of the weight ring (default 4, or a quarter of the "
                          "share if that is smaller; never fewer than two matrices or layers)")

@@ -973,6 +973,114 @@ def attn_mla(shapes=ATTN_SHAPES[:3], heads=(16, 128), kinds=("bf16", "fp8"), rin
     return out
 
 
+def attn_mla_multi(shapes=ATTN_SHAPES[:3], heads=(16, 128), new_tokens=(2, 4, 8), kinds=("bf16", "fp8"),
+                   ring_bytes=(1 << 30) + 1, reps=3, rounds=3, page=16, splits=ATTN_SPLITS):
+    """The multi-token MLA decode attention under the protocol of :func:`attn_mla`, against the yardstick that is not
+    the code under test: ``single``, T back-to-back ``gsx_mla_decode_attn`` calls (the dispatching single-token entry
+    point) on the same ring, the same block table and the same base lengths, call t on the lengths ``base + t + 1``
+    and on token t's rows of Q.  ``context`` counts the T new tokens (base = context - T).  Columns: ``gsx``, the
+    dispatching ``gsx_mla_decode_attn_multi``; every configuration at every split count that leaves a split 8 tiles
+    and makes 16 to 4096 workgroups; ``single``.  Reported are microseconds per layer with the spread (max - min) /
+    median, ``single_over_gsx``, and ``gsx_beats_single``: ``gsx`` faster than ``single`` by more than the row's largest
+    spread.  ``max_abs_diff_vs_single`` compares the two on the ring's last layer first."""
+    out = []
+    s = hip.Stream(0)
+    ts = torch.cuda.ExternalStream(s.ptr)
+    dk, dv = 576, 512
+    cfgs = {}
+    while (name := hip.mla_decode_attn_multi_cfg_name(len(cfgs))) is not None:
+        cfgs[len(cfgs)] = (name, *hip.mla_decode_attn_multi_cfg_shape(len(cfgs)))
+    scale = 192 ** -0.5
+    for kind in kinds:
+        kdt = torch.bfloat16 if kind == "bf16" else torch.float8_e4m3fn
+        for b, ctx in shapes:
+            per_seq = -(-ctx // page)
+            pages = b * per_seq
+            per = pages * page * dk * (2 if kind == "bf16" else 1)
+            layers = max(2, -(-ring_bytes // per))
+            kv = torch.empty(layers, pages, page, dk, device="cuda", dtype=kdt)
+            for i in range(layers):
+                kv[i].copy_(torch.randn(pages, page, dk, device="cuda", dtype=torch.bfloat16).to(kdt))
+            table = torch.randperm(pages, device="cuda").to(torch.int32).view(b, per_seq).contiguous()
+            lb = kv[0].numel() * kv.element_size()
+            for hq in heads:
+                for t in new_tokens:
+                    q = torch.randn(b, t, hq, dk, device="cuda", dtype=torch.bfloat16)
+                    o = torch.empty(b, t, hq, dv, device="cuda", dtype=torch.bfloat16)
+                    q1 = [q[:, j].contiguous() for j in range(t)]  # what the single-token calls take: [B][Hq][576]
+                    o1 = torch.empty(t, b, hq, dv, device="cuda", dtype=torch.bfloat16)
+                    before = torch.full((b,), ctx - t, device="cuda", dtype=torch.int32)
+                    lens1 = [before + j + 1 for j in range(t)]
+                    ws = torch.empty(max(b * t * hq * max(splits) * 2056, 16), device="cuda", dtype=torch.uint8)
+                    ws1 = torch.empty(max(hip.mla_decode_attn_workspace_bytes(b, hq, page, ctx), 16), device="cuda",
+                                      dtype=torch.uint8)
+                    torch.cuda.synchronize()
+
+                    def ours(cfg, sp):
+                        for i in range(layers):
+                            args = (s, kind, q.data_ptr(), kv.data_ptr() + i * lb, table.data_ptr(), before.data_ptr(),
+                                    o.data_ptr(), b, t, hq, page, pages, per_seq, ctx, scale)
+                            if cfg is None:
+                                hip.mla_decode_attn_multi(*args, 1.0, ws.data_ptr(), ws.numel())
+                            else:
+                                hip.mla_decode_attn_multi_launch_cfg(*args, cfg, sp, 1.0, ws.data_ptr(), ws.numel())
+
+                    def single():
+                        for i in range(layers):
+                            for j in range(t):
+                                hip.mla_decode_attn(s, kind, q1[j].data_ptr(), kv.data_ptr() + i * lb, table.data_ptr(),
+                                                    lens1[j].data_ptr(), o1[j].data_ptr(), b, hq, page, pages, per_seq,
+                                                    ctx, scale, 1.0, ws1.data_ptr(), ws1.numel())
+
+                    tiles, nblk = -(-ctx // 32), -(-t * hq // 64)
+                    variants = {f"cfg{cfg}_{name}_s{sp}": (lambda cfg=cfg, sp=sp: ours(cfg, sp))
+                                for cfg, (name, _, _) in cfgs.items() for sp in splits
+                                if sp * 8 <= tiles and 16 <= b * nblk * sp <= 4096}
+                    variants.update({"gsx": lambda: ours(None, None), "single": single})
+
+                    def timed(fn):
+                        torch.cuda.synchronize()
+                        with torch.cuda.stream(ts):
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record(ts)
+                            for _ in range(reps):
+                                fn()
+                            e1.record(ts)
+                        e1.synchronize()
+                        return e0.elapsed_time(e1) * 1e3 / (reps * layers)  # microseconds per layer
+
+                    # the two agree (on the ring's last layer) before they are compared for speed
+                    ours(None, None)
+                    single()
+                    s.sync()
+                    diff = (o.float() - o1.float().transpose(0, 1)).abs().max().item()
+                    row = {"kind": kind, "b": b, "context": ctx, "heads": hq, "new_tokens": t, "page": page,
+                           "layers": layers, "ring_bytes": layers * per, "max_abs_diff_vs_single": round(diff, 5)}
+                    runs = {name: [] for name in variants}
+                    for r in range(rounds + 1):  # the first round warms up clocks and code objects
+                        for name, fn in variants.items():
+                            us = timed(fn)
+                            if r:
+                                runs[name].append(us)
+                    for name, v in runs.items():
+                        med = statistics.median(v)
+                        row[f"{name}_us"] = round(med, 2)
+                        row[f"{name}_spread"] = round((max(v) - min(v)) / med, 3)
+                    margin = max(v for k, v in row.items() if k.endswith("_spread"))
+                    row["spread"] = margin
+                    row["best"] = min((k for k in runs if k.startswith("cfg")), key=lambda k: row[f"{k}_us"])
+                    row["gsx_over_best"] = round(row["gsx_us"] / row[row["best"] + "_us"], 3)
+                    row["single_over_gsx"] = round(row["single_us"] / row["gsx_us"], 2)
+                    row["gsx_beats_single"] = row["gsx_us"] * (1 + margin) < row["single_us"]
+                    out.append(row)
+                    print(json.dumps(row), file=sys.stderr, flush=True)
+                    del q, o, q1, o1, ws, ws1
+            del kv, table
+            torch.cuda.empty_cache()
+    s.destroy()
+    return out
+
+
 KV_APPEND_SHAPES = [(8, 2048), (64, 512), (1, 16384)]  # (sequences, new tokens each): prefill chunks of 16384 tokens
 KV_APPEND_DECODE = (8, 64, 256)  # sequences of a decode step (T = 1)
 
@@ -1935,7 +2043,7 @@ if __name__ == "__main__":
     sections = {"gemm_bf16_nt": lambda: gemm(sizes), "gemm_fp8_nt": lambda: gemm_fp8(fp8_sizes),
                 "gemm_fp8_block": gemm_fp8_block, "gemm_mxfp4_nt": lambda: gemm_mxfp4(fp8_sizes), "gemm_decode": gemm_decode, "gemm_skinny": gemm_skinny,
                 "gemm_skinny_fp8_block": gemm_skinny_fp8_block,
-                "attn_decode": attn_decode, "attn_multi": attn_multi, "attn_mla": attn_mla,
+                "attn_decode": attn_decode, "attn_multi": attn_multi, "attn_mla": attn_mla, "attn_mla_multi": attn_mla_multi,
                 "kv_append": kv_append, "norm_act": norm_act, "attn_prefill": attn_prefill, "sample": sample,
                 # short single sequences, where attn_pick()'s cap of 4 tiles per wave decides the split count
                 "attn_decode_short": lambda: attn_decode(shapes=[(1, 8192), (1, 4096)], heads=[(64, 8)]),
